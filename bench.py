@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X-native block-tridiagonal PCG.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, checks what they left (verified, one SpMV outside the timed
+region) and prints the headline line.  --full adds every other measurement listed below.  --dump-outputs DIR
+writes what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64; rank 0's shard).
 
 N > 1 without WORLD_SIZE in the environment: this process is only a LAUNCHER -- it starts N fresh child
 ranks (one per GPU: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set) before making any GPU call, waits for
@@ -18,7 +22,7 @@ A "step" = one batched PCG solve with a fixed iteration count (exit_tol = 0, max
 |eta| < 0 never holds, /root/reference/include/pcg.cuh:195), lambda reset to 0 first, replayed from a
 hipGraph.  value = problem-iterations per second over the whole job (all ranks' units / max elapsed).
 
-Printed JSON line (rank 0) also carries
+Printed JSON line (rank 0) also carries, with --full
   roofline     : the dominant kernel.  pcg_resident_sym_kernel keeps [D|R] of S and Phi^-1 on the CU for the
                  whole solve, so its bound is fp32 vector issue, not HBM: achieved = flop/s against the
                  157.3 TFLOP/s fp32 peak (frac <= 1), with the HBM share of the bytes it really moves and the
@@ -282,6 +286,17 @@ def median(xs):
     return s[len(s) // 2]
 
 
+def dump_outputs(path, tensors):
+    """What the last timed step returned to its caller, one DIR/<name>.npy per buffer, one row per problem: the vectors in
+    their own precision (fp32), the per-problem counts and flags as float64.  22 MB for the 1024-problem shard."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in tensors.items():
+        a = t.cpu().numpy()
+        a = a.astype(np.float64) if a.dtype.kind in "iu" else a.astype(np.float32, copy=False)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # Bounds on the true residual ||gamma - S lambda|| / ||gamma|| of a timed buffer (asserted, outside the timed region):
 # fixed-count runs sit on the rounding floor of their precision (kappa(S) ~ 27: measured 5e-7 in fp32, 1.4e-13 in fp64 at n = 36, N = 256);
 # runs to exit_tol = 1e-6 stop on |r.Pinv r| < 1e-6 (pcg.cuh:195), an ABSOLUTE test: ||r|| <~ 1e-3 against ||gamma|| ~ 40.
@@ -387,6 +402,9 @@ def run_rank(args, world, rank, local_rank):
     elapsed, total_units = sharding.aggregate(elapsed, float(B * iters * args.steps), device=agg_device)
     verified = verify_solve(solver, torch, n, N, B, S, gamma, lam, it_out, fl_out, "fixed", iters)   # outside the timed region
     step_ms = median([a.elapsed_time(b) for a, b in events])   # check kernel + both PCG launches of one replay
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"lambda": lam.view(B, -1), "r": r.view(B, -1), "p": p.view(B, -1),
+                                         "iters": it_out, "max_iter_exit": fl_out})
 
     def time_graph(gr, reps, warm=5, reset=None):
         """Median (and minimum) per-replay HIP-event time of a solve graph on the launch stream."""
@@ -414,11 +432,6 @@ def run_rank(args, world, rank, local_rank):
         gr.close()
         return med, best, ver
 
-    all_symmetric = (int(solver.check_symmetric(n, N, B, S).min()) == 1
-                     and int(solver.check_symmetric(n, N, B, P).min()) == 1)
-    REPS = max(100, args.steps)
-    sym_ms, sym_best, sym_ver = time_mode(1, REPS)   # the dominant kernel alone (caller asserts symmetry: no check launch)
-
     def time_converged(mode, reps):
         """The same kernel run to exit_tol = 1e-6 (what an MPC loop runs: 9 iterations on this generator)."""
         solver.set_symmetric(mode)
@@ -430,19 +443,7 @@ def run_rank(args, world, rank, local_rank):
         gr.close()
         return med, best, ver, mean_it
 
-    # (--no-converged: the kernel-stats pass of tools/profile_round.sh leaves these dispatches out, so that the AverageNs rocprofv3
-    # reports for the dominant kernel is the average of the fixed-25 launches roofline.kernel_ms is measured on)
-    if args.no_converged:
-        conv_ms = conv_best = dflt_ms = conv_it = 1.0   # (unused: the block below says "skipped")
-        conv_ver = dflt_ver = None
-    else:
-        conv_ms, conv_best, conv_ver, conv_it = time_converged(1, REPS)
-        dflt_ms, _, dflt_ver, _ = time_converged(2, REPS)
     flops = pcg_flops_per_launch(n, N, B, iters)
-    pcg_bytes = pcg_bytes_per_launch(n, N, B, iters, 4)
-    resident_bytes = B * (2 * (2 * N - 1) * n * n + 5 * n * N) * 4   # [D|R] of both matrices once per solve + vectors
-    tflops = flops / (sym_ms * 1e-3) / 1e12
-    sq = pmc_valu("pcg_resident_sym_kernel")
     out = None
     if rank == 0:
         # Phi^-1 operand accounting of the resident kernel ("LDS hit rate for the preconditioner", north star):
@@ -477,7 +478,31 @@ def run_rank(args, world, rank, local_rank):
             "solves_per_sec": total_batch * args.steps / elapsed,
             "verified": verified,
             "value_definition": "problem-iterations per second (25 PCG iterations x 1024 problems per GPU per step), default path",
-            "roofline": {
+            "pinv_onchip": {"hit_rate": iters / (iters + 1.0), "from_lds": lds_share, "from_registers": 1.0 - lds_share,
+                            "definition": "Phi^-1 bytes consumed by the (iters+1) products of a solve that are served from "
+                                          "the CU (LDS or registers) / bytes consumed; from_lds + from_registers split the "
+                                          "on-chip part (kernel geometry, pcg_resident_sym.hip)"},
+        }
+
+    if args.full:
+        all_symmetric = (int(solver.check_symmetric(n, N, B, S).min()) == 1
+                         and int(solver.check_symmetric(n, N, B, P).min()) == 1)
+        REPS = max(100, args.steps)
+        sym_ms, sym_best, sym_ver = time_mode(1, REPS)   # the dominant kernel alone (caller asserts symmetry: no check launch)
+        # (--no-converged: the kernel-stats pass of tools/profile_round.sh leaves these dispatches out, so that the AverageNs rocprofv3
+        # reports for the dominant kernel is the average of the fixed-25 launches roofline.kernel_ms is measured on)
+        if args.no_converged:
+            conv_ms = conv_best = dflt_ms = conv_it = 1.0   # (unused: the block below says "skipped")
+            conv_ver = dflt_ver = None
+        else:
+            conv_ms, conv_best, conv_ver, conv_it = time_converged(1, REPS)
+            dflt_ms, _, dflt_ver, _ = time_converged(2, REPS)
+        pcg_bytes = pcg_bytes_per_launch(n, N, B, iters, 4)
+        resident_bytes = B * (2 * (2 * N - 1) * n * n + 5 * n * N) * 4   # [D|R] of both matrices once per solve + vectors
+        tflops = flops / (sym_ms * 1e-3) / 1e12
+        sq = pmc_valu("pcg_resident_sym_kernel")
+        if rank == 0:
+            out["roofline"] = {
                 "bound": "valu",
                 "kernel": "pcg_resident_sym_kernel<14,true> (symmetric S and Pinv resident on the CU; timed alone, "
                           "gbdpcg_set_symmetric(1))",
@@ -511,14 +536,9 @@ def run_rank(args, world, rank, local_rank):
                                       "about 17 us are tile loads at the per-CU ingest rate (401 KB at ~33 GB/s per CU, "
                                       "profiles/r03_resident_stamps.txt) + prologue + write-back, the rest 2.2 us per iteration"},
                 "note": "peak = fp32 vector peak (= dense fp32 MFMA peak) of MI355X_MICROARCH.md; the matrices are read once "
-                        "per solve, so the kernel is bound by VALU issue and on-chip latency, not by HBM"},
-            "pinv_onchip": {"hit_rate": iters / (iters + 1.0), "from_lds": lds_share, "from_registers": 1.0 - lds_share,
-                            "definition": "Phi^-1 bytes consumed by the (iters+1) products of a solve that are served from "
-                                          "the CU (LDS or registers) / bytes consumed; from_lds + from_registers split the "
-                                          "on-chip part (kernel geometry, pcg_resident_sym.hip)"},
-        }
+                        "per solve, so the kernel is bound by VALU issue and on-chip latency, not by HBM"}
 
-    if world == 1:
+    if world == 1 and args.full:
         try:
             # General (not bit-symmetric) storage: gbdpcg_set_symmetric(0) makes every problem take the path a caller-formed
             # Phi^-1 takes.  Since round 2 that is the cluster kernel (both matrices register-resident over two CUs per
@@ -608,10 +628,10 @@ def run_rank(args, world, rank, local_rank):
         except Exception as e:   # noqa: BLE001 -- reported, not swallowed: the key carries the error
             out[key] = {"error": f"{type(e).__name__}: {e}"}
 
-    if world == 1 and not args.no_configs:
+    if world == 1 and args.full and not args.no_configs:
         guarded("configs", bench_configs, solver, torch, binding, synth, dev, stream)
         guarded("mpc_step", bench_mpc_step, solver, torch, binding, synth, dev, stream)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         guarded("cpu_baseline", cpu_baseline, n, N, iters)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -764,14 +784,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, general-storage, SpMV, config, MPC-step and CPU-baseline blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write lambda, r, p, iters and max_iter_exit of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the configs and mpc_step blocks")
     ap.add_argument("--no-converged", action="store_true", help="skip the run-to-tolerance block of the roofline object (profiling passes)")
     ap.add_argument("--dry-run", action="store_true",
                     help="host logic only (rendezvous, sharding, aggregation) with gloo and no GPU; reports no value")
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None:

@@ -5,7 +5,7 @@ rounds=$1; shift
 for r in $(seq 1 $rounds); do
   for lib in default "$@"; do
     if [ "$lib" = default ]; then unset GBDPCG_LIB; else export GBDPCG_LIB=$PWD/$lib; fi
-    python bench.py --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -49,7 +49,7 @@ def main():
     fdir, wdir, cdir, out = sys.argv[1:5]
     fetch, write, cal = per_kernel(fdir, "FETCH_SIZE"), per_kernel(wdir, "WRITE_SIZE"), per_kernel(cdir, "FETCH_SIZE")
     res = {"_how": "rocprofv3 --kernel-trace --pmc FETCH_SIZE and, in a separate pass, --pmc WRITE_SIZE, on "
-                   "`bench.py --steps 3 --warmup 1` (config 3) and on gbd-pcg_amd/tools/bw_probe; MI355X. Counter unit = "
+                   "`bench.py --full --steps 3 --warmup 1` (config 3) and on gbd-pcg_amd/tools/bw_probe; MI355X. Counter unit = "
                    "KiB. gfx950 correction (MI355X_MICROARCH.md, HBM): FETCH_SIZE reports half the bytes of a wide "
                    "streaming read; calibrated below on known-size pure reads in the access shapes and cache policies "
                    "the library uses; read bytes = FETCH_SIZE * 1024 / ratio(0.5). WRITE_SIZE is exact. FETCH_SIZE "

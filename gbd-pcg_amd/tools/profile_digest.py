@@ -4,8 +4,8 @@
     python gbd-pcg_amd/tools/profile_digest.py r02
 
   profiles/<round>_bench.jsonl                 the bench line of that run (appended)
-  profiles/<round>_bench_kernel_stats.csv      rocprofv3 --kernel-trace --stats summary of `bench.py --no-configs` (this library's
-                                               kernels; config 3 dispatches only); ..._with_configs.csv: the default command
+  profiles/<round>_bench_kernel_stats.csv      rocprofv3 --kernel-trace --stats summary of `bench.py --full --no-configs` (this library's
+                                               kernels; config 3 dispatches only); ..._with_configs.csv: `bench.py --full`
   profiles/<round>_pmc_traffic.json            FETCH_SIZE / WRITE_SIZE per launch (pmc_traffic.py)
   profiles/<round>_pmc_sq.json                 SQ counters per launch + derived VALU-issue utilisation and LDS
                                                bank-conflict share (read by bench.py into roofline.valu_issue)
@@ -130,7 +130,7 @@ def main():
                 f.write(head + body)
     # SQ counters
     out = {"_how": "rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU "
-                   "SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE on `bench.py --steps 3 --warmup 1` "
+                   "SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE on `bench.py --full --steps 3 --warmup 1` "
                    "(config 3), one MI355X; mean per dispatch over the long (fixed-25-iteration) dispatches of each kernel. "
                    "valu_issue_utilisation = SQ_INSTS_VALU x 4 cycles / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs): the share of the "
                    "kernel's SIMD-cycles in which a vector instruction of a single wave could have been issued (one wave issues a "

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where a default config-3 step goes, kernel by kernel: digest of a rocprofv3 --kernel-trace of bench.py.
-   cd /tmp && rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -- python3 $REPO/bench.py --no-configs --no-cpu-baseline
-   python3 gbd-pcg_amd/tools/step_timeline.py /tmp/tl
+   rocprofv3 --kernel-trace --output-format csv -d TRACE_DIR -- python3 bench.py --full --no-configs --no-cpu-baseline
+   python3 gbd-pcg_amd/tools/step_timeline.py TRACE_DIR
 Prints, for the last 50 (check, resident, general) triples of the trace: median duration of each kernel and of the gaps
 between them, and the median distance from one step's first kernel to the next step's."""
 import csv

@@ -190,7 +190,7 @@ def test_bench_launcher_two_ranks_share_one_gpu():
     rehearsal form for a one-GPU box; on a multi-GPU node the same command uses RCCL, one rank per GPU)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["GBDPCG_BENCH_BACKEND"] = "gloo"
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     rec = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -212,9 +212,9 @@ def test_multi_device_cpp_driver():
 
 
 def test_bench_line_contract():
-    """`python bench.py` (the driver's command, N = 1): one JSON line with the metric of BASELINE.json, a roofline block
+    """`python bench.py --full` (N = 1): one JSON line with the metric of BASELINE.json, a roofline block
     whose fraction is a fraction, the SpMV block over the 1.23 GB rotation, the per-config block and the CPU baseline."""
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--full"],
                          capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -239,3 +239,34 @@ def test_bench_line_contract():
     for k in ("form_schur", "recover_primal"):
         assert ms[k]["bound"] == "hbm" and 0.1 < ms[k]["frac"] <= 1.0 and abs(ms[k]["frac"] - ms[k]["achieved"] / ms[k]["peak"]) < 1e-12
     assert ms["us_per_step_of_1024_problems"] < ms["form_schur"]["us"] + ms["form_pinv_solve"]["us"] + ms["recover_primal"]["us"] + 50.0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path, orc):
+    """`python bench.py --steps 3 --warmup 1 --dump-outputs DIR`, the plain run: the headline line without the --full blocks,
+    three timed steps, and DIR holding what the last step returned -- every problem ran its 25 iterations, and lambda solves
+    S lambda = gamma (true residual on the host, in fp64, for three problems of the shard)."""
+    out = tmp_path / "outputs"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                         capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert rec["metric"] == base["metric"] and rec["unit"] == "iter/s" and rec["dtype"] == "f32" and rec["higher_is_better"] is True
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["verified"]["ok"] is True
+    assert abs(rec["value"] - 1024 * 25 / (rec["ms_per_step"] * 1e-3)) < 1e-6 * rec["value"]
+    assert not {"roofline", "general_kernel", "spmv", "configs", "mpc_step", "cpu_baseline"} & set(rec)
+    got = {k: np.load(out / f"{k}.npy") for k in ("lambda", "r", "p", "iters", "max_iter_exit")}
+    n, N, B = 14, 128, 1024
+    for k in ("lambda", "r", "p"):
+        assert got[k].dtype == np.float32 and got[k].shape == (B, n * N) and np.isfinite(got[k]).all(), k
+    assert got["iters"].shape == got["max_iter_exit"].shape == (B,)
+    assert (got["iters"] == 25).all() and (got["max_iter_exit"] == 1).all()
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    for i in (0, 1, B - 1):
+        g = synth.gen_torch_seeded(n, N, i, i + 1, "cpu", torch.float32, seed=1234)
+        S, gamma = g["S"].double().numpy(), g["gamma"].double().numpy()
+        gnorm = np.linalg.norm(gamma)
+        true_res = np.linalg.norm(gamma - orc.spmv(n, N, S, got["lambda"][i].astype(np.float64))) / gnorm
+        assert true_res < 1e-5 and np.linalg.norm(got["r"][i]) < 1e-5 * gnorm, (i, true_res)
