@@ -1,6 +1,7 @@
 // api.hip -- the C ABI of libgbdpcg.so (include/gbdpcg.h): handle, dispatch, graphs, host overloads.
 #include <hip/hip_runtime.h>
 
+#include <cassert>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -336,6 +337,29 @@ gbdpcg_status solve_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t bat
             a.symmetric = false;
             a.want = 0;
             HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream));
+        } else if (has_sym && h->symmetric == 2 && resident_sym_verifies<T>(h->dev, n, N, d_S, d_Pinv)) {
+            // AUTO on the CU-resident symmetric kernel: it takes EVERY problem and tests L_{k+1} == R_k^T itself, against the
+            // tiles it holds anyway (no test launch, no second read of R); it writes one verdict byte per problem and leaves
+            // the problems that fail untouched for the general launch, which takes exactly those.  One byte per problem:
+            // verdict_bytes (what gbdpcg_reserve sizes) is never less.
+            if (batch > h->sym_cap) {
+                hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+                if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+                    return GBDPCG_ERR_ALLOC;
+                gbdpcg_status st = ensure_sym_flags(h, batch);
+                if (st != GBDPCG_OK) return st;
+            }
+            a.symmetric = true;
+            a.verdict_out = h->sym_flags;
+            hipError_t rerr = hipSuccess;
+            if (!launch_pcg_resident_sym_verify<T>(h->dev, a, stream, &rerr)) return GBDPCG_ERR_UNSUPPORTED;
+            HIP_TRY(h, rerr);
+            a.verdict_out = nullptr;
+            a.symmetric = false;
+            a.sel_stride = 1;
+            a.sel = h->sym_flags;
+            a.want = 0;
+            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream));
         } else if (has_sym && h->symmetric == 2) {
             // AUTO: test L_{k+1} == R_k^T on the device (S, then Pinv and-ed in), then launch BOTH kernels:
             // the symmetric one takes the problems that passed, the general one the rest.  No host
@@ -410,11 +434,14 @@ gbdpcg_status spmv_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batc
 
 // Verdict bytes a (n, N, batch) solve in symmetric mode 2 may need: the larger of what the test kernel and the
 // one-launch stair kernel write per problem.
+// (never less than one byte per problem: the verifying resident launch writes that many)
 template <typename T> size_t verdict_bytes(uint32_t n, uint32_t N, uint32_t batch)
 {
     const uint32_t a = check_pair_chunks<T>(n, N), b = pinv_verdict_chunks<T>(n, N, GBDPCG_PINV_STAIR);
     const uint32_t m = a > b ? a : b;
-    return (size_t)batch * (m ? m : 1);
+    const size_t bytes = (size_t)batch * (m ? m : 1);
+    assert(bytes >= batch);
+    return bytes;
 }
 
 // Phi^-1 from S, then the solve, on one stream.  When the stair kernel can report, per problem, that S was exactly

@@ -76,6 +76,9 @@ template <typename T> struct PcgArgs {
     const uint8_t *sel = nullptr;
     uint8_t want = 0;
     uint32_t sel_stride = 1;  // verdict bytes per problem (one per workgroup of the check kernel); the flag is their AND
+    // The verifying resident kernel (launch_pcg_resident_sym_verify) writes its symmetry verdict here, one byte per problem
+    // (1 = symmetric, solved; 0 = left untouched for the general launch).  Read by no other kernel.
+    uint8_t *verdict_out = nullptr;
     // Split path, blocking entry points only: a counter in host-visible memory that a problem bumps when
     // it converges, so that the host can stop enqueueing iteration launches (nullptr: not used).
     uint32_t *host_done = nullptr;
@@ -125,6 +128,12 @@ bool launch_pcg_resident(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t
 template <typename T> bool resident_sym_shape(uint32_t n, uint32_t N);
 template <typename T>
 bool launch_pcg_resident_sym(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err);
+// Its verifying form: every problem, L_{k+1} == R_k^T of S and Pinv tested inside the solve, verdicts into a.verdict_out
+// (stride 1); a problem that fails is left untouched.  resident_sym_verifies: would that form take this solve (n = 14, fp32,
+// N <= 128, S and Pinv 16-byte aligned)?
+template <typename T> bool resident_sym_verifies(const DeviceInfo &dev, uint32_t n, uint32_t N, const T *S, const T *Pinv);
+template <typename T>
+bool launch_pcg_resident_sym_verify(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err);
 
 // ---- pcg_cluster.hip : general-storage matrices register-resident, a problem over a cluster of 2-4 workgroups (CUs)
 // Workgroups per problem the cluster path would use; 0 = shape not handled (n = 14, fp32, 72 < N <= 288 only).

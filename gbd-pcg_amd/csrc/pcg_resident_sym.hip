@@ -316,6 +316,37 @@ __device__ __forceinline__ void symres_touch(const float *M, uint32_t N, uint32_
                  : "=&s"(keep) : "v"(addr), "s"(lds_dump) : "memory");
 }
 
+// Symmetry in storage, verified against the resident tile (verifying kernel only).  Columns 2rp, 2rp+1 of L_{k+1}
+// (column-major: 2n contiguous floats at (k+1) 3n^2 + 2rp n, 16-byte aligned when the matrix is) are the transposes of the
+// lane's rows 2rp, 2rp+1 of R_k.  cmp == false (dead lane, k >= N-1): block 0's first floats are read instead and ignored.
+// Plain loads: non-temporal ones took 21 instead of 8.5 us per round of the tail.  (Touching the next problem's L blocks
+// along with its [D|R] during the iterations, so that this read would find them in the Infinity Cache, cost the iterations
+// as much as it saved here: not done.)
+template <int NCT>
+__device__ __forceinline__ void symres_lcols_issue(const float *__restrict__ M, uint32_t k, uint32_t rp, bool cmp,
+                                                   float4 (&l)[NCT / 2])
+{
+    constexpr uint32_t n = NCT;
+    const float4 *src = reinterpret_cast<const float4 *>(M + (cmp ? (size_t)(k + 1) * 3 * n * n + 2 * rp * n : (size_t)0));
+#pragma unroll
+    for (uint32_t m = 0; m < n / 2; ++m) l[m] = src[m];
+}
+// r[j] = the tile's R piece j: (R[2rp, 2j], R[2rp, 2j+1], R[2rp+1, 2j], R[2rp+1, 2j+1]).  True when some R_k(r, c) and
+// L_{k+1}(c, r) differ bit for bit (the semantics of check_symmetric_pair_kernel: -0.0 != +0.0, NaNs by payload).
+template <int NCT>
+__device__ __forceinline__ bool symres_r_differs(const float4 (&r)[NCT / 2], const float4 (&l)[NCT / 2], bool cmp)
+{
+    constexpr uint32_t n = NCT;
+    auto comp = [](const float4 &v, uint32_t i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; };
+    uint32_t diff = 0;
+#pragma unroll
+    for (uint32_t e = 0; e < 2 * n; ++e) {
+        const uint32_t hi = e / n, c = e % n;   // L_{k+1}(c, 2rp + hi)  vs  R_k(2rp + hi, c)
+        diff |= __builtin_bit_cast(uint32_t, comp(l[e / 4], e % 4)) ^ __builtin_bit_cast(uint32_t, comp(r[c / 2], 2 * hi + (c & 1)));
+    }
+    return cmp && diff != 0;
+}
+
 // One dword LDS-DMA instruction: the active lanes move 4 bytes each from base + off to lds_addr + 4 * lane.  Like the touch
 // above it is invisible to hipcc's counters; the caller waits (s_waitcnt vmcnt(0)) before the barrier that precedes the
 // first read of the destination.
@@ -337,7 +368,11 @@ __device__ __forceinline__ void symres_dma_dword(const float *base, uint32_t off
 #define GBDPCG_RS_STAMP(IDX)
 #endif
 
-template <int NCT, bool STAGED>
+// VERIFY: the launch takes EVERY problem (a.sel is not read) and tests L_{k+1} == R_k^T of both matrices itself, against
+// the resident tiles, after the iterations: a problem that passes is written as by the plain kernel plus verdict byte 1 in
+// a.verdict_out[prob]; one that fails gets verdict byte 0 and nothing else (lambda keeps the caller's warm start for the
+// general launch that follows).  VERIFY = false is the plain kernel.
+template <int NCT, bool STAGED, bool VERIFY = false>
 __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
 {
     using G = SymResGeom<NCT>;
@@ -359,6 +394,8 @@ __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
     float *ls = red1 + WAVES;                                  // lambda
     // LDS byte address of the 256-byte dump area of the prefetch loads (symres_touch), shared by all waves
     const uint32_t dump = (uint32_t)(uintptr_t)(ls + align16<float>(len));
+    // verifying kernel: the workgroup's verdict on the current problem (1 = symmetric), right behind the dump area
+    uint32_t *vword = reinterpret_cast<uint32_t *>(ls + align16<float>(len)) + 64;
 
     const size_t mstride = (size_t)3 * n * n * N;
 
@@ -378,12 +415,19 @@ __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
         ++rs_round;
 #endif
         GBDPCG_RS_STAMP(0)
-        if (pi == 0 || pi - takes_from >= 64) {
-            const uint32_t left = (a.batch - prob + gridDim.x - 1) / gridDim.x;
-            takes = pcg_takes_mask(a, prob, gridDim.x, left < 64 ? left : 64u, lane);
-            takes_from = pi;
+        if constexpr (!VERIFY) {
+            if (pi == 0 || pi - takes_from >= 64) {
+                const uint32_t left = (a.batch - prob + gridDim.x - 1) / gridDim.x;
+                takes = pcg_takes_mask(a, prob, gridDim.x, left < 64 ? left : 64u, lane);
+                takes_from = pi;
+            }
+            if (!((takes >> (pi - takes_from)) & 1ull)) continue;  // this launch is not the one that owns the problem
+        } else {
+            (void)takes;
+            (void)takes_from;
+            // (the previous problem's readers are past its last barrier; several barriers separate this from the tail)
+            if (tid == 0) *vword = 1u;
         }
-        if (!((takes >> (pi - takes_from)) & 1ull)) continue;  // this launch is not the one that owns the problem
         // Everything a lane derives from its number is derived again for every problem, from an opaque copy: hoisted out of
         // the problem loop these dozen values were spilled to scratch (15 VGPRs) and reloaded in the tile-load phase.
         uint32_t lane_o = tid & 63u;
@@ -618,21 +662,58 @@ __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
 #undef GBDPCG_SYMRES_FINISH_Y
 
         GBDPCG_RS_STAMP(5)
+        if constexpr (VERIFY) {
+            // L_{k+1} == R_k^T for both matrices and both of the lane's block-rows against the R halves of the tiles, S then
+            // Pinv (all four sets of pieces in flight at once spill).  The Pinv k1 tile is compared from LDS.
+            const bool cmp0 = live0 && k0 + 1 < N, cmp1 = live1 && k1 + 1 < N;
+            bool bad;
+            {
+                float4 l0[n / 2], l1[n / 2], r0[n / 2], r1[n / 2];
+                symres_lcols_issue<NCT>(S, k0, rp, cmp0, l0);
+                symres_lcols_issue<NCT>(S, k1, rp, cmp1, l1);
+#pragma unroll
+                for (uint32_t j = 0; j < n / 2; ++j) {
+                    r0[j] = s0.q[n / 2 + j];
+                    r1[j] = s1.q[n / 2 + j];
+                }
+                bad = symres_r_differs<NCT>(r0, l0, cmp0);
+                bad |= symres_r_differs<NCT>(r1, l1, cmp1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            {
+                float4 l0[n / 2], l1[n / 2], r0[n / 2], r1[n / 2];
+                symres_lcols_issue<NCT>(P, k0, rp, cmp0, l0);
+                symres_lcols_issue<NCT>(P, k1, rp, cmp1, l1);
+#pragma unroll
+                for (uint32_t j = 0; j < n / 2; ++j) {
+                    r0[j] = p0.q[n / 2 + j];
+                    r1[j] = ltw[(n / 2 + j) * 64];
+                }
+                bad |= symres_r_differs<NCT>(r0, l0, cmp0);
+                bad |= symres_r_differs<NCT>(r1, l1, cmp1);
+            }
+            if (bad) *vword = 0u;   // (every writer writes the same value)
+        }
         while (pf < pf_per_matrix) { GBDPCG_SYMRES_PREFETCH() }  // short solves: the rest of the prefetch
 #undef GBDPCG_SYMRES_PREFETCH
 
         // outputs                                                         (pcg.cuh:212,215)
         __syncthreads();
-        for (uint32_t i = tid; i < len; i += G::THREADS) {
-            a.lambda[voff + i] = ls[i];
-            if (a.r) a.r[voff + i] = xb[n + i];
-            if (a.p) a.p[voff + i] = xa[n + i];
+        // verifying kernel: a problem that failed the test is left to the general launch, untouched
+        const bool keep = VERIFY ? __builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile uint32_t *>(vword)) != 0u : true;
+        if (keep) {
+            for (uint32_t i = tid; i < len; i += G::THREADS) {
+                a.lambda[voff + i] = ls[i];
+                if (a.r) a.r[voff + i] = xb[n + i];
+                if (a.p) a.p[voff + i] = xa[n + i];
+            }
+            if (tid == 0) {
+                a.iters[prob] = iter;
+                if (a.max_iter_exit) a.max_iter_exit[prob] = max_iter_exit ? 1 : 0;
+            }
         }
-        if (tid == 0) {
-            a.iters[prob] = iter;
-            if (a.max_iter_exit) a.max_iter_exit[prob] = max_iter_exit ? 1 : 0;
-        }
-        __syncthreads();  // LDS (tile, vectors) is reused by the next problem
+        if (VERIFY && tid == 0) a.verdict_out[prob] = keep ? 1 : 0;
+        __syncthreads();  // LDS (tile, vectors, verdict word) is reused by the next problem
         GBDPCG_RS_STAMP(6)
     }
     // The prefetch loads are invisible to the compiler's counters; s_endpgm drains the wave's memory counters in
@@ -641,7 +722,7 @@ __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// n = 14, fp32, N <= 128, a preconditioner given, matrices 8-byte aligned.  GBDPCG_NO_RESIDENT_SYM
+// n = 14, fp32, N <= 128, a preconditioner given, matrices 8-byte aligned (16-byte for the verifying kernel).  GBDPCG_NO_RESIDENT_SYM
 // disables the path (tuning runs).
 template <typename T> bool resident_sym_shape(uint32_t n, uint32_t N)
 {
@@ -650,24 +731,40 @@ template <typename T> bool resident_sym_shape(uint32_t n, uint32_t N)
     return N <= SymResGeom<14>::MAX_KNOTS;
 }
 
-static size_t resident_sym_lds(uint32_t n, uint32_t N)
+// (+ 256: the dump area of the prefetch loads; + 16: the verifying kernel's verdict word behind it)
+static size_t resident_sym_lds(uint32_t n, uint32_t N, bool verify = false)
 {
     return ((size_t)SymResGeom<14>::TILE_LDS_FLOATS + 3 * (size_t)align16<float>((N + 3) * n) +
-            2 * SymResGeom<14>::WAVES + align16<float>(N * n)) * sizeof(float) + 256;
+            2 * SymResGeom<14>::WAVES + align16<float>(N * n)) * sizeof(float) + 256 + (verify ? 16 : 0);
+}
+
+static bool resident_sym_staged(const void *S, const void *Pinv)
+{
+    // coalesced 16-byte tile loads need 16-byte aligned matrices (every hipMalloc'ed buffer is)
+    static const bool no_staging = getenv("GBDPCG_RS_DIRECT_LOADS") != nullptr;  // tuning runs only
+    return !no_staging && !((reinterpret_cast<uintptr_t>(S) | reinterpret_cast<uintptr_t>(Pinv)) % 16);
 }
 
 template <typename T>
-bool launch_pcg_resident_sym(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err)
+bool resident_sym_verifies(const DeviceInfo &dev, uint32_t n, uint32_t N, const T *S, const T *Pinv)
+{
+    return sizeof(T) == 4 && S && Pinv && resident_sym_shape<T>(n, N) && resident_sym_staged(S, Pinv) &&
+           resident_sym_lds(n, N, true) <= dev.lds_per_wg_max;
+}
+
+// verify: the verifying kernel (every problem, a.verdict_out written); the caller has checked resident_sym_verifies.
+template <typename T>
+static bool launch_pcg_resident_sym_impl(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err, bool verify)
 {
     if constexpr (sizeof(T) == 4) {
         if (!a.symmetric || !a.Pinv || !resident_sym_shape<T>(a.n, a.N)) return false;
         if ((reinterpret_cast<uintptr_t>(a.S) % 8) || (reinterpret_cast<uintptr_t>(a.Pinv) % 8)) return false;
-        const size_t lds = resident_sym_lds(a.n, a.N);
+        const size_t lds = resident_sym_lds(a.n, a.N, verify);
         if (lds > dev.lds_per_wg_max) return false;
-        // coalesced 16-byte tile loads need 16-byte aligned matrices (every hipMalloc'ed buffer is)
-        static const bool no_staging = getenv("GBDPCG_RS_DIRECT_LOADS") != nullptr;  // tuning runs only
-        const bool staged = !no_staging && !((reinterpret_cast<uintptr_t>(a.S) | reinterpret_cast<uintptr_t>(a.Pinv)) % 16);
-        auto kern = staged ? pcg_resident_sym_kernel<14, true> : pcg_resident_sym_kernel<14, false>;
+        const bool staged = resident_sym_staged(a.S, a.Pinv);
+        if (verify && (!staged || !a.verdict_out)) return false;
+        auto kern = verify ? pcg_resident_sym_kernel<14, true, true>
+                           : staged ? pcg_resident_sym_kernel<14, true, false> : pcg_resident_sym_kernel<14, false, false>;
         // on every launch, like the other launchers: HIP keeps the attribute per device, and a process may hold
         // handles on several devices (one host thread each)
         *err = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -682,9 +779,25 @@ bool launch_pcg_resident_sym(const DeviceInfo &dev, const PcgArgs<T> &a, hipStre
     }
 }
 
+template <typename T>
+bool launch_pcg_resident_sym(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err)
+{
+    return launch_pcg_resident_sym_impl<T>(dev, a, s, err, false);
+}
+
+template <typename T>
+bool launch_pcg_resident_sym_verify(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err)
+{
+    return launch_pcg_resident_sym_impl<T>(dev, a, s, err, true);
+}
+
 template bool resident_sym_shape<float>(uint32_t, uint32_t);
 template bool resident_sym_shape<double>(uint32_t, uint32_t);
 template bool launch_pcg_resident_sym<float>(const DeviceInfo &, const PcgArgs<float> &, hipStream_t, hipError_t *);
 template bool launch_pcg_resident_sym<double>(const DeviceInfo &, const PcgArgs<double> &, hipStream_t, hipError_t *);
+template bool resident_sym_verifies<float>(const DeviceInfo &, uint32_t, uint32_t, const float *, const float *);
+template bool resident_sym_verifies<double>(const DeviceInfo &, uint32_t, uint32_t, const double *, const double *);
+template bool launch_pcg_resident_sym_verify<float>(const DeviceInfo &, const PcgArgs<float> &, hipStream_t, hipError_t *);
+template bool launch_pcg_resident_sym_verify<double>(const DeviceInfo &, const PcgArgs<double> &, hipStream_t, hipError_t *);
 
 }  // namespace gbdpcg

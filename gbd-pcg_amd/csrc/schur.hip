@@ -469,7 +469,7 @@ __device__ __forceinline__ void schur_form_quad_body(uint32_t N, uint32_t run, u
     constexpr uint32_t SW = GBDPCG_SCHUR_ST4 && Q::SROW % 4 == 0 ? 4 : 1;   // (an odd block size: rows of 3 n^2 elements do not split into fours)
     constexpr uint32_t ST_I = SW * sizeof(T) > 16 ? SW * sizeof(T) / 16 : 1;
     constexpr uint32_t OUT_T = (4 * Q::SROW / SW + 63) / 64, GI_T = (4 * Q::SG / SW + 63) / 64;
-    constexpr uint32_t S_STORES = OUT_T * ST_I + 1, GI_STORES = GI_T * ST_I;   // + 1: gamma
+    constexpr uint32_t SG_STORES = OUT_T * ST_I + 1, GI_STORES = GI_T * ST_I;   // + 1: gamma
     static_assert((4 * Q::SROW) % SW == 0 && Q::SROW % SW == 0 && (4 * Q::SG) % SW == 0, "whole groups");
     typedef T OutV __attribute__((ext_vector_type(SW == 4 ? 4 : 2), aligned(sizeof(T))));   // (SW == 1 does not use it)
     uint32_t src[OUT_T][SW];
@@ -563,14 +563,14 @@ __device__ __forceinline__ void schur_form_quad_body(uint32_t N, uint32_t run, u
 #endif
         SCHUR_STAMP(0);
         // The requests for this step were issued at the top of the previous one, before every store that step issued (the
-        // deferred S / gamma stores of the step before it: S_STORES instructions, and its own G^-1 stores: GI_STORES -- a known number per
+        // deferred S / gamma stores of the step before it: SG_STORES instructions, and its own G^-1 stores: GI_STORES -- a known number per
         // instruction per trip, which is why the write-out loops are written trip by trip), and the memory operations of a wave
         // retire in order: waiting until exactly that many are left is waiting for the requests and for nothing else.
         // (One input buffer: the requests were the last thing the previous step issued, so everything is waited for.)
-        static_assert(S_STORES + GI_STORES <= 63, "vmcnt is a 6-bit counter");
+        static_assert(SG_STORES + GI_STORES <= 63, "vmcnt is a 6-bit counter");
         switch ((GBDPCG_SCHUR_SKIP & 4) || SINGLE ? 0u : stores_since_request) {
-        case S_STORES + GI_STORES: asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(S_STORES + GI_STORES) : "memory"); break;
-        case S_STORES: asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(S_STORES) : "memory"); break;
+        case SG_STORES + GI_STORES: asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(SG_STORES + GI_STORES) : "memory"); break;
+        case SG_STORES: asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(SG_STORES) : "memory"); break;
         case GI_STORES: asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(GI_STORES) : "memory"); break;
         default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); break;
         }
@@ -613,7 +613,7 @@ __device__ __forceinline__ void schur_form_quad_body(uint32_t N, uint32_t run, u
         // then queue behind
         constexpr uint32_t PER = (OUT_T + NX - 2) / (NX - 1);
         static_assert(PER * (NX - 1) >= OUT_T, "the last pivot's slot is gamma's");
-        if (pending) stores_since_request += S_STORES;
+        if (pending) stores_since_request += SG_STORES;
         auto drain = [&](uint32_t J) {
 #pragma unroll
             for (uint32_t t = J * PER; t < (J + 1) * PER && t < OUT_T; ++t)
