@@ -120,11 +120,13 @@ class Solver:
         """0 / False: never, 1 / True: assume, 2: test on the device before every solve (the default)."""
         self._check(self.lib.gbdpcg_set_symmetric(self.h, ctypes.c_int(int(mode))), "set_symmetric")
 
-    def check_symmetric(self, n, N, batch, M, stream=None):
+    def check_symmetric(self, n, N, batch, M, stream=None, flags=None):
         """uint8 tensor [batch]: 1 where L_{k+1} == R_k^T bit for bit for every knot."""
         import torch
         suf, _ = _suffix(M)
-        flags = torch.empty(batch, dtype=torch.uint8, device=M.device)
+        if flags is None:
+            flags = torch.empty(batch, dtype=torch.uint8, device=M.device)
+        assert flags.dtype == torch.uint8 and flags.numel() == batch and flags.is_contiguous()
         fn = getattr(self.lib, f"gbdpcg_check_symmetric_{suf}")
         self._check(fn(self.h, ctypes.c_uint32(n), ctypes.c_uint32(N), ctypes.c_uint32(batch), _p(M), _p(flags),
                        self._stream(stream)), "check_symmetric")

@@ -252,6 +252,7 @@ template <typename T> size_t persist_total_bytes(gbdpcg_handle_t, uint32_t n, ui
 // (8 problems of 24 x 128 under max_iter = 100: 370 us of launches for nine iterations).  They are solved by a few persistent
 // launches in a row instead, `persist_slices` problems each, when that row is shorter than the split path's launches alone:
 // 25 us of fixed cost per persistent launch against 1.8 us per launch of the split graph.  0: no slicing.
+// (tests/test_gpu_footprint.py, slices(), restates this rule with these constants to know which launches a case reaches.)
 template <typename T> uint32_t persist_slices(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batch, uint32_t max_iter)
 {
     static const bool off = getenv("GBDPCG_NO_PERSIST_SLICES") != nullptr;   // tuning runs only

@@ -190,3 +190,59 @@ def test_oracle_under_address_and_ub_sanitizers():
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert "oracle selftest ok" in out.stdout and "FAIL" not in out.stdout
     assert "ERROR: AddressSanitizer" not in out.stderr and "runtime error" not in out.stderr
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint8)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("with_pinv", [True, False], ids=["stair", "identity"])
+@pytest.mark.parametrize("N", [1, 2, 3, 128])
+def test_corner_blocks_are_not_part_of_the_system(orc, dtype, with_pinv, N):
+    """L_0 and R_{N-1} of S and of Pinv are never read (pcg.cuh:105-106): NaN there changes no bit of lambda, r, p, the
+    iteration count or the flag -- the reference side of tests/test_gpu_footprint.py, check A."""
+    n, B = 14, 3
+    d = synth.gen_numpy(n, N, seed=300 + N, batch=B, dtype=dtype)
+    lam0 = (0.1 * np.stack([synth.normals(310 + b, 0, n * N) for b in range(B)])).astype(dtype)
+    for tol, max_iter in ((1e-6, 50), (0.0, 1 if N == 1 else 5)):
+        outs = []
+        for poison in (False, True):
+            S, P = d["S"].copy(), d["Pinv"].copy()
+            if poison:
+                for M in (S, P):
+                    M[:, :n * n] = np.nan
+                    M[:, -n * n:] = np.nan
+            outs.append(orc.pcg_batch(n, N, B, S, P if with_pinv else None, d["gamma"], lambda0=lam0, tol=tol, max_iter=max_iter))
+        for key in ("lambda_", "r", "p", "iters", "max_iter_exit"):
+            assert np.array_equal(_bits(outs[0][key]), _bits(outs[1][key])), key
+        assert np.isfinite(outs[1]["lambda_"]).all()
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("flags", [0, 1, 2, 3])
+@pytest.mark.parametrize("kind", ["zero", "nan", "inf"])
+def test_degenerate_problems_run_to_max_iter(orc, dtype, flags, kind):
+    """gamma = 0 (lambda_0 = 0), one NaN, one +Inf in gamma: alpha is 0/0 or NaN, abs(eta_new) < exit_tol is false for NaN
+    (pcg.cuh:169,195), so the loop runs to max_iter, the flag is set and lambda holds no finite entry; with max_iter = 0
+    lambda is lambda_0 and the non-finite entry of r spreads through Pinv to the three block-rows around its knot (NaN x 0 is
+    NaN) -- the reference side of tests/test_gpu_footprint.py, check B, under every summation variant."""
+    n, N, knot = 14, 128, 50
+    d = synth.gen_numpy(n, N, seed=77, batch=1, dtype=dtype)
+    g = d["gamma"][0].copy()
+    if kind == "zero":
+        g[:] = 0
+    else:
+        g[knot * n + 3] = np.nan if kind == "nan" else np.inf
+    for tol, max_iter in ((1e-6, 50), (0.0, 6)):
+        out = orc.pcg(n, N, d["S"][0], d["Pinv"][0], g, tol=tol, max_iter=max_iter, flags=flags)
+        assert out["iters"] == max_iter and out["max_iter_exit"]
+        assert not np.isfinite(out["lambda_"]).any()
+    out = orc.pcg(n, N, d["S"][0], d["Pinv"][0], g, tol=1e-6, max_iter=0, flags=flags)
+    assert out["iters"] == 0 and out["max_iter_exit"] and not out["lambda_"].view(np.uint8).any()
+    bad_r, bad_p = ~np.isfinite(out["r"]), ~np.isfinite(out["p"])
+    if kind == "zero":
+        assert not bad_r.any() and not bad_p.any()
+    else:
+        assert np.flatnonzero(bad_r).tolist() == [knot * n + 3]
+        assert np.flatnonzero(bad_p).tolist() == list(range((knot - 1) * n, (knot + 2) * n))
