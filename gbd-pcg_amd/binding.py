@@ -33,8 +33,21 @@ SYMBOLS = [
     "gbdpcg_graph_create_form_pinv_solve_f32", "gbdpcg_graph_create_form_pinv_solve_f64",
     "gbdpcg_form_schur_f32", "gbdpcg_form_schur_f64", "gbdpcg_recover_primal_f32", "gbdpcg_recover_primal_f64",
     "gbdpcg_kkt_step_f32", "gbdpcg_kkt_step_f64", "gbdpcg_graph_create_kkt_step_f32", "gbdpcg_graph_create_kkt_step_f64",
+    "gbdpcg_form_gamma_f32", "gbdpcg_form_gamma_f64", "gbdpcg_kkt_resolve_f32", "gbdpcg_kkt_resolve_f64",
+    "gbdpcg_graph_create_kkt_resolve_f32", "gbdpcg_graph_create_kkt_resolve_f64",
     "gbdpcg_csr_to_bt_f32", "gbdpcg_csr_to_bt_f64", "gbdpcg_version",
 ]
+
+
+def _resolve_argtypes(lib):
+    """argtypes of the frozen-linearisation entry points (gbdpcg_form_gamma_*, gbdpcg_kkt_resolve_* and its graph form)."""
+    u32, vp = ctypes.c_uint32, ctypes.c_void_p
+    for suf, ft in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
+        head = [vp, u32, u32, u32, u32, vp, vp, vp, vp]            # h, nx, nu, N, batch, Ginv, C, g, c
+        solve = [vp, vp, vp, vp, vp, vp, ft, u32, vp, vp, vp]      # S, Pinv, gamma, lambda, r, p, tol, max_iter, iters, flags, z
+        getattr(lib, f"gbdpcg_form_gamma_{suf}").argtypes = head + [vp, vp]
+        getattr(lib, f"gbdpcg_kkt_resolve_{suf}").argtypes = head + solve + [vp]
+        getattr(lib, f"gbdpcg_graph_create_kkt_resolve_{suf}").argtypes = head + solve + [ctypes.POINTER(vp)]
 
 _lib = None
 
@@ -58,6 +71,7 @@ def load() -> ctypes.CDLL:
         lib.gbdpcg_version.restype = ctypes.c_char_p
         lib.gbdpcg_pcg_shared_mem_size.restype = ctypes.c_size_t
         lib.gbdpcg_workspace_bytes.restype = ctypes.c_size_t
+        _resolve_argtypes(lib)
         _lib = lib
     return _lib
 
@@ -281,6 +295,43 @@ class Solver:
                        _p(C), _p(g), _p(lam), _p(z), self._stream(stream)), "recover_primal")
         return z
 
+    def form_gamma(self, nx, nu, N, batch, Ginv, C, g, c, gamma=None, stream=None):
+        """gbdpcg_form_gamma_*: gamma = -(c + C G^-1 g) from the G^-1 form_schur wrote -- G, C unchanged, new g and c."""
+        import torch
+        suf, _ = _suffix(Ginv)
+        if gamma is None:
+            gamma = torch.empty(batch * nx * N, dtype=Ginv.dtype, device=Ginv.device)
+        fn = getattr(self.lib, f"gbdpcg_form_gamma_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(Ginv), _p(C), _p(g), _p(c), _p(gamma), self._stream(stream)), "form_gamma")
+        return gamma
+
+    def _resolve_args(self, nx, nu, N, batch, Ginv, C, g, c, S, Pinv, gamma, lam, r, p, tol, max_iter, iters, mie, z):
+        suf, _ = _suffix(Ginv)
+        return suf, (self.h, nx, nu, N, batch, _p(Ginv), _p(C), _p(g), _p(c), _p(S), _p(Pinv), _p(gamma), _p(lam), _p(r), _p(p),
+                     tol, max_iter, _p(iters), _p(mie), _p(z))
+
+    def kkt_resolve(self, nx, nu, N, batch, Ginv, C, g, c, S, Pinv, gamma, lam, z, r=None, p=None, tol=1e-6, max_iter=25,
+                    iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_kkt_resolve_*: new g, c on unchanged S, Pinv, G^-1 -> gamma -> PCG (warm start from lam) -> primal step z."""
+        import torch
+        if iters is None:
+            iters = torch.zeros(batch, dtype=torch.int32, device=Ginv.device)
+        if max_iter_exit is None:
+            max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=Ginv.device)
+        suf, args = self._resolve_args(nx, nu, N, batch, Ginv, C, g, c, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                                       max_iter_exit, z)
+        fn = getattr(self.lib, f"gbdpcg_kkt_resolve_{suf}")
+        self._check(fn(*args, self._stream(stream)), "kkt_resolve")
+        return iters, max_iter_exit
+
+    def graph_kkt_resolve(self, nx, nu, N, batch, Ginv, C, g, c, S, Pinv, gamma, lam, r, p, tol, max_iter, iters, max_iter_exit, z):
+        """Capture gamma + solve + recovery into one hipGraph (gbdpcg_graph_create_kkt_resolve_*)."""
+        suf, args = self._resolve_args(nx, nu, N, batch, Ginv, C, g, c, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                                       max_iter_exit, z)
+        gr = ctypes.c_void_p()
+        fn = getattr(self.lib, f"gbdpcg_graph_create_kkt_resolve_{suf}")
+        self._check(fn(*args, ctypes.byref(gr)), "graph_create_kkt_resolve")
+        return Graph(self, gr, keep=(Ginv, C, g, c, S, Pinv, gamma, lam, r, p, iters, max_iter_exit, z))
 
     def _kkt_args(self, nx, nu, N, batch, G, C, g, c, S, gamma, Ginv, Pinv, kind, lam, r, p, tol, max_iter, iters, mie, z):
         suf, ft = _suffix(G)

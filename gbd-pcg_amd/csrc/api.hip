@@ -541,12 +541,16 @@ gbdpcg_status form_schur_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint3
 template <typename T>
 gbdpcg_status recover_primal_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv,
                                   const T *d_C, const T *d_g, const T *d_lambda, T *d_z, void *stream);
+template <typename T>
+gbdpcg_status form_gamma_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv, const T *d_C,
+                              const T *d_g, const T *d_c, T *d_gamma, void *stream);
 
 // The operands of the steps either side of the solve (gbdpcg_kkt_step_*): S and gamma are formed from them before, z after.
 template <typename T> struct KktOperands {
     uint32_t nu;
     const T *G, *C, *g, *c;
     T *Ginv, *z;
+    bool resolve = false;   // gbdpcg_kkt_resolve_*: G is not looked at, Ginv, S and Pinv are read only
 };
 
 // KKT blocks -> S, gamma, G^-1 -> Phi^-1 -> PCG -> primal step, on one stream (capturable: no allocation after the first
@@ -583,6 +587,22 @@ gbdpcg_status kkt_step_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t N, uint32_t
     }
     if (st != GBDPCG_OK) return st;
     return recover_primal_impl<T>(h, nx, k.nu, N, batch, k.Ginv, k.C, k.g, d_lambda, k.z, stream);
+}
+
+// The step for a linearisation that is kept (G, C unchanged since the gbdpcg_kkt_step_* or gbdpcg_form_schur_* that wrote S, Pinv
+// and G^-1): gamma from the new g and c, the ordinary solve on the caller's S and Pinv, the primal step.  The library cannot know
+// that S was left alone, so the solve is told nothing about its symmetry: the handle's mode decides, as in gbdpcg_solve_*.
+template <typename T>
+gbdpcg_status kkt_resolve_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv, const T *d_C,
+                               const T *d_g, const T *d_c, const T *d_S, const T *d_Pinv, T *d_gamma, T *d_lambda, T *d_r, T *d_p,
+                               T tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_exit, T *d_z, hipStream_t stream)
+{
+    if (!h || !d_S || !d_lambda || !d_iters || !d_z) return GBDPCG_ERR_INVALID;
+    gbdpcg_status st = form_gamma_impl<T>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, d_gamma, stream);
+    if (st != GBDPCG_OK) return st;
+    st = solve_impl<T>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, stream);
+    if (st != GBDPCG_OK) return st;
+    return recover_primal_impl<T>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_lambda, d_z, stream);
 }
 
 template <typename T>
@@ -624,7 +644,10 @@ gbdpcg_status graph_create_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint3
     hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
     gbdpcg_status st = GBDPCG_OK;
     if (e == hipSuccess) {
-        if (kkt)
+        if (kkt && kkt->resolve)
+            st = kkt_resolve_impl<T>(h, n, kkt->nu, N, batch, kkt->Ginv, kkt->C, kkt->g, kkt->c, d_S, d_Pinv, const_cast<T *>(d_gamma),
+                                     d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, kkt->z, cs);
+        else if (kkt)
             st = kkt_step_impl<T>(h, n, N, batch, *kkt, const_cast<T *>(d_S), const_cast<T *>(d_gamma), const_cast<T *>(d_Pinv),
                                   (gbdpcg_pinv_kind)form_kind, d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, cs);
         else if (form_kind >= 0)
@@ -701,6 +724,17 @@ gbdpcg_status recover_primal_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, u
     if (!schur_shape_ok<T>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;
     DEVICE_SCOPE(h);
     HIP_TRY(h, launch_recover_primal<T>(h->dev, nx, nu, N, batch, d_Ginv, d_C, d_g, d_lambda, d_z, (hipStream_t)stream));
+    return GBDPCG_OK;
+}
+template <typename T>
+gbdpcg_status form_gamma_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv, const T *d_C,
+                              const T *d_g, const T *d_c, T *d_gamma, void *stream)
+{
+    if (!h || !d_Ginv || !d_g || !d_c || !d_gamma || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))
+        return GBDPCG_ERR_INVALID;
+    if (!schur_shape_ok<T>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_form_gamma<T>(h->dev, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, d_gamma, (hipStream_t)stream));
     return GBDPCG_OK;
 }
 }  // namespace
@@ -1105,6 +1139,41 @@ gbdpcg_status gbdpcg_graph_create_form_pinv_solve_f64(gbdpcg_handle_t h, uint32_
 GBDPCG_KKT_STEP(f32, float)
 GBDPCG_KKT_STEP(f64, double)
 #undef GBDPCG_KKT_STEP
+
+#define GBDPCG_KKT_RESOLVE(SUF, TYPE)                                                                                               \
+    gbdpcg_status gbdpcg_form_gamma_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,                    \
+                                          const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c, TYPE *d_gamma,       \
+                                          void *stream)                                                                             \
+    {                                                                                                                               \
+        return form_gamma_impl<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, d_gamma, stream);                                   \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_kkt_resolve_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,                   \
+                                           const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c, const TYPE *d_S,    \
+                                           const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda, TYPE *d_r, TYPE *d_p, TYPE tol,         \
+                                           uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, TYPE *d_z, void *stream)   \
+    {                                                                                                                               \
+        return kkt_resolve_impl<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol,     \
+                                      max_iter, d_iters, d_max_iter_exit, d_z, (hipStream_t)stream);                                \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_graph_create_kkt_resolve_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,      \
+                                                        const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c,        \
+                                                        const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda,           \
+                                                        TYPE *d_r, TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters,         \
+                                                        uint8_t *d_max_iter_exit, TYPE *d_z, gbdpcg_graph_t *out)                     \
+    {                                                                                                                               \
+        /* what the captured calls would refuse is refused before anything is reserved or captured */                                \
+        if (!h || !out || !d_Ginv || !d_g || !d_c || !d_S || !d_gamma || !d_lambda || !d_iters || !d_z || (!d_C && N > 1) ||        \
+            nu == 0 || !shape_ok(nx, N, batch))                                                                                     \
+            return GBDPCG_ERR_INVALID;                                                                                              \
+        if (!schur_shape_ok<TYPE>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;                                                   \
+        KktOperands<TYPE> k{nu, nullptr, d_C, d_g, d_c, const_cast<TYPE *>(d_Ginv), d_z};                                           \
+        k.resolve = true;                                                                                                           \
+        return graph_create_impl<TYPE>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters,            \
+                                       d_max_iter_exit, out, -1, &k);                                                               \
+    }
+GBDPCG_KKT_RESOLVE(f32, float)
+GBDPCG_KKT_RESOLVE(f64, double)
+#undef GBDPCG_KKT_RESOLVE
 
 gbdpcg_status gbdpcg_csr_to_bt_f32(uint32_t n, uint32_t N, const uint32_t *row_ptr, const uint32_t *col_ind,
                                    const float *val, float *h_M)

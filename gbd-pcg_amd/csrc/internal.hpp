@@ -200,6 +200,10 @@ hipError_t launch_form_schur(const DeviceInfo &dev, uint32_t nx, uint32_t nu, ui
 template <typename T>
 hipError_t launch_recover_primal(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *Ginv,
                                  const T *C, const T *g, const T *lambda, T *z, hipStream_t s);
+// gamma = -(c + C G^-1 g) alone, from the G^-1 launch_form_schur wrote: G and C unchanged, new g and c (S is not touched)
+template <typename T>
+hipError_t launch_form_gamma(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *Ginv, const T *C,
+                             const T *g, const T *c, T *gamma, hipStream_t s);
 template <typename T> bool schur_shape_ok(const DeviceInfo &dev, uint32_t nx, uint32_t nu);
 
 }  // namespace gbdpcg

@@ -2,6 +2,7 @@
 //   form_schur     : KKT blocks (Q_k, R_k, A_k, B_k, q_k, r_k, c_k) of a batch of linearised MPC problems
 //                    -> S = C G^-1 C' in the [L | D | R] layout pcg<T> reads, gamma = -(c + C G^-1 g), and G^-1
 //   recover_primal : lambda -> z = -G^-1 (g + C' lambda)
+//   form_gamma     : G^-1 (as form_schur wrote it), C and NEW g, c -> gamma alone, for a linearisation that is kept
 //
 // The reference tree has no code for either (/root/reference/README.md:2-11 states only the system
 // Pinv S lambda = Pinv gamma that comes out of the first, README.md:66-77 cites the paper that describes them; MPCGPU
@@ -938,6 +939,191 @@ __global__ __launch_bounds__(256) void schur_recover_quad_kernel(uint32_t N, uin
     if (lu) zk[NX + l] = -su;
 }
 
+// ---- gamma alone, for a frozen linearisation (G, C unchanged since the last form_schur: S, Phi^-1 and G^-1 stand, only g and c
+// are new): gamma = -(c + C G^-1 g) from the stored G^-1, nothing inverted, S neither read nor written.
+//     w_k = Q_k^-1 q_k,  v_k = R_k^-1 r_k,  t_k = A_k w_k + B_k v_k,      gamma_0 = -(c_0 + w_0),  gamma_k = -((c_k + w_k) - t_{k-1})
+// Every entry is one fma chain from zero with q ascending (t: the columns of A, then those of B, in one chain), in both kernels
+// below: their results are bit-identical, as those of the recovery pair are.
+__host__ __device__ inline uint32_t gamma_wave_elems(uint32_t nx, uint32_t nu)
+{
+    const uint32_t e = 3 * nx * nx + nu * nu + nx * nu + 4 * nx + 2 * nu;  // Qi_k, Qi_j, A_j, Ri_j, B_j, q_k, q_j, w_j, (spare), r_j, v_j
+    return (e + 3u) & ~3u;
+}
+
+// Any block size: one wavefront per row (problem, k), blocks staged in LDS.
+template <typename T>
+__global__ __launch_bounds__(256) void schur_gamma_kernel(uint32_t nx, uint32_t nu, uint32_t N, uint64_t rows,
+                                                         const T *__restrict__ Ginv, const T *__restrict__ C,
+                                                         const T *__restrict__ g, const T *__restrict__ c, T *__restrict__ gamma)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint64_t row = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+    if (row >= rows) return;  // whole wave
+    const KktDims d(nx, nu, N);
+    const uint64_t prob = row / N;
+    const uint32_t k = (uint32_t)(row - prob * N);
+    const uint32_t nn = nx * nx, uu = nu * nu, xu = nx * nu;
+    const bool has_prev = k > 0;
+
+    T *Qc = reinterpret_cast<T *>(smem_raw) + (size_t)wave * gamma_wave_elems(nx, nu);
+    T *Qp = Qc + nn, *Ap = Qp + nn, *Rp = Ap + nn, *Bp = Rp + uu;
+    T *qc = Bp + xu, *qp = qc + nx, *wp = qp + nx, *rp = wp + 2 * nx, *vp = rp + nu;
+    const T *Gp = Ginv + prob * d.szG, *gp = g + prob * d.szg;
+
+    for (uint32_t i = lane; i < nn; i += 64) Qc[i] = Gp[(size_t)k * d.sg + i];
+    for (uint32_t i = lane; i < nx; i += 64) qc[i] = gp[(size_t)k * d.sv + i];
+    if (has_prev) {
+        const uint32_t j = k - 1;
+        const T *Gj = Gp + (size_t)j * d.sg, *Cj = C + prob * d.szC + (size_t)j * d.sc, *gj = gp + (size_t)j * d.sv;
+        for (uint32_t i = lane; i < nn; i += 64) {
+            Qp[i] = Gj[i];
+            Ap[i] = Cj[i];
+        }
+        for (uint32_t i = lane; i < uu; i += 64) Rp[i] = Gj[nn + i];
+        for (uint32_t i = lane; i < xu; i += 64) Bp[i] = Cj[nn + i];
+        for (uint32_t i = lane; i < nx; i += 64) qp[i] = gj[i];
+        for (uint32_t i = lane; i < nu; i += 64) rp[i] = gj[nx + i];
+    }
+    wave_sync();
+    if (has_prev) {
+        for (uint32_t r = lane; r < nx; r += 64) {
+            T s = T(0);
+            for (uint32_t q = 0; q < nx; ++q) s = fma_t(Qp[q * nx + r], qp[q], s);
+            wp[r] = s;
+        }
+        for (uint32_t r = lane; r < nu; r += 64) {
+            T s = T(0);
+            for (uint32_t q = 0; q < nu; ++q) s = fma_t(Rp[q * nu + r], rp[q], s);
+            vp[r] = s;
+        }
+    }
+    wave_sync();
+    for (uint32_t r = lane; r < nx; r += 64) {
+        T w = T(0);
+        for (uint32_t q = 0; q < nx; ++q) w = fma_t(Qc[q * nx + r], qc[q], w);
+        T v = c[(size_t)row * nx + r] + w;
+        if (has_prev) {
+            T t = T(0);
+            for (uint32_t q = 0; q < nx; ++q) t = fma_t(Ap[q * nx + r], wp[q], t);
+            for (uint32_t q = 0; q < nu; ++q) t = fma_t(Bp[q * nx + r], vp[q], t);
+            v -= t;
+        }
+        gamma[(size_t)row * nx + r] = -v;
+    }
+}
+
+namespace {
+
+// The value the same lane of the 16-lane quarter BEFORE this one holds (quarter 0 gets quarter 3's): a permute between vector
+// registers through the LDS crossbar -- no LDS is allocated or addressed.  Every lane of the wave must be active.
+__device__ __forceinline__ float prev_quarter(float v, uint32_t lane)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((int)(((lane + 48u) & 63u) * 4u), __builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ double prev_quarter(double v, uint32_t lane)
+{
+    const long long b = __builtin_bit_cast(long long, v);
+    const int a = (int)(((lane + 48u) & 63u) * 4u);
+    const int lo = __builtin_amdgcn_ds_bpermute(a, (int)(b & 0xffffffffll));
+    const int hi = __builtin_amdgcn_ds_bpermute(a, (int)(b >> 32));
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
+}
+
+// The operands of one knot in the lanes of one quarter, as schur_recover_quad_kernel holds them: lane l has ROW l of Q^-1, R^-1,
+// A and B (element q of a row comes with the quarter's q-th load: contiguous across the lanes) and entry l of q and r.
+// full: the knot has R^-1, r, A, B (every knot but a problem's last); on == false: nothing is read, everything is zero.
+template <typename T, int NX, int NU>
+__device__ __forceinline__ void gamma_knot_load(T (&qi)[NX], T (&a)[NX], T (&ri)[NU], T (&b)[NU], T &qv, T &rv, const T *__restrict__ Gi,
+                                                const T *__restrict__ Ck, const T *__restrict__ gk, uint32_t cx, uint32_t cu, bool on,
+                                                bool full)
+{
+    if (on) {
+        qv = gk[cx];
+#pragma unroll
+        for (int q = 0; q < NX; ++q) qi[q] = Gi[q * NX + cx];
+    } else {
+        qv = T(0);
+#pragma unroll
+        for (int q = 0; q < NX; ++q) qi[q] = T(0);
+    }
+    if (on && full) {
+        rv = gk[NX + cu];
+#pragma unroll
+        for (int q = 0; q < NX; ++q) a[q] = Ck[q * NX + cx];
+#pragma unroll
+        for (int q = 0; q < NU; ++q) ri[q] = Gi[NX * NX + q * NU + cu];
+#pragma unroll
+        for (int q = 0; q < NU; ++q) b[q] = Ck[NX * NX + q * NX + cx];
+    } else {
+        rv = T(0);
+#pragma unroll
+        for (int q = 0; q < NX; ++q) a[q] = T(0);
+#pragma unroll
+        for (int q = 0; q < NU; ++q) ri[q] = T(0);
+#pragma unroll
+        for (int q = 0; q < NU; ++q) b[q] = T(0);
+    }
+}
+// w = Q^-1 q (entry l in lane l) and t = A w + B R^-1 r
+template <typename T, int NX, int NU>
+__device__ __forceinline__ void gamma_knot_products(const T (&qi)[NX], const T (&a)[NX], const T (&ri)[NU], const T (&b)[NU], T qv, T rv,
+                                                    T &w, T &t)
+{
+    T v = T(0);
+    w = T(0);
+    t = T(0);
+    recover_dot<0, NX>(w, qi, qv);
+    recover_dot<0, NU>(v, ri, rv);
+    recover_dot<0, NX>(t, a, w);
+    recover_dot<0, NU>(t, b, v);
+}
+
+}  // namespace
+
+// ---- compile-time block sizes: FOUR rows per wavefront, one per 16-lane quarter, no LDS (the form of schur_recover_quad_kernel).
+// Every block of G^-1 and C is read ONCE: the quarter of row k forms w_k and t_k = A_k w_k + B_k v_k from the blocks of its own
+// knot, and t_k goes to the quarter of row k+1 as a permute inside the wave.  The first quarter of a wave has no quarter before it:
+// it reads the blocks of knot k-1 as well and forms t_{k-1} itself (the same chains on the same numbers as the wave before it) --
+// 1.25 x the bytes of Q^-1, R^-1, A, B per wave instead of the 2 x of rows that each read both knots.  Every load of a row is
+// requested before the first fma; the products of the second knot run in all quarters on zeros (the kernel waits on memory, and
+// no DPP operand is read under a partial exec mask that way).
+// 1024 x 128 rows at nx 14, nu 7: 87 us in fp32 (307 MB, 3.5 TB/s; 104 registers, four waves per SIMD), 135 us in fp64; 31 us at
+// 12 / 4 (6.5 TB/s) -- profiles/r05_resolve.txt.
+template <typename T, int NX, int NU>
+__global__ __launch_bounds__(256) void schur_gamma_quad_kernel(uint32_t N, uint64_t rows, const T *__restrict__ Ginv,
+                                                              const T *__restrict__ C, const T *__restrict__ g,
+                                                              const T *__restrict__ c, T *__restrict__ gamma)
+{
+    static_assert(NX <= 16 && NU <= NX, "one row per 16-lane quarter");
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t l = lane & 15u, qd = lane >> 4;
+    const uint64_t row = ((uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 4 + qd;
+    const bool live = row < rows;
+    const KktDims d(NX, NU, N);
+    const uint64_t prob = live ? row / N : 0;
+    const uint32_t k = live ? (uint32_t)(row - prob * N) : 0u;
+    const bool has_next = live && k + 1 < N, has_prev = live && k > 0;
+    const bool first = has_prev && qd == 0;                      // no quarter before this one holds t_{k-1}
+    const uint32_t cx = l < NX ? l : 0u, cu = l < NU ? l : 0u;   // clamped: idle lanes read what a live lane reads
+    const uint32_t j = first ? k - 1 : k;
+    const T *Gp = Ginv + prob * d.szG, *Cp = C + prob * d.szC, *gp = g + prob * d.szg;
+
+    T qi[NX], a[NX], ri[NU], b[NU], qv, rv;       // this row's knot
+    T qib[NX], ab[NX], rib[NU], bb[NU], qvb, rvb;  // the knot before it (first quarter only)
+    gamma_knot_load<T, NX, NU>(qi, a, ri, b, qv, rv, Gp + (size_t)k * d.sg, Cp + (size_t)k * d.sc, gp + (size_t)k * d.sv, cx, cu, live, has_next);
+    gamma_knot_load<T, NX, NU>(qib, ab, rib, bb, qvb, rvb, Gp + (size_t)j * d.sg, Cp + (size_t)j * d.sc, gp + (size_t)j * d.sv, cx, cu, first, true);
+    const T ck = live ? c[(prob * N + k) * NX + cx] : T(0);
+
+    T w, t, wb, tb;
+    gamma_knot_products<T, NX, NU>(qi, a, ri, b, qv, rv, w, t);
+    gamma_knot_products<T, NX, NU>(qib, ab, rib, bb, qvb, rvb, wb, tb);
+    const T tp = prev_quarter(t, lane);
+    T v = ck + w;
+    if (has_prev) v -= first ? tb : tp;
+    if (live && l < NX) gamma[(prob * N + k) * NX + l] = -v;
+}
+
 // Waves per workgroup for a per-wave LDS need; 0 = does not fit one CU.
 static uint32_t waves_for(const DeviceInfo &dev, size_t wave_bytes)
 {
@@ -1039,6 +1225,39 @@ hipError_t launch_recover_primal(const DeviceInfo &dev, uint32_t nx, uint32_t nu
     return hipGetLastError();
 }
 
+template <typename T>
+hipError_t launch_form_gamma(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *Ginv, const T *C,
+                             const T *g, const T *c, T *gamma, hipStream_t s)
+{
+    const uint64_t rows = (uint64_t)batch * N;
+    // GBDPCG_SCHUR_GENERAL=1: the any-size kernel also where the four-rows-per-wave form exists (A/B runs, tests)
+    const char *env = getenv("GBDPCG_SCHUR_GENERAL");
+    if (!(env && env[0] == '1')) {
+        const uint64_t grid = (rows + 15) / 16;   // 4 waves x 4 rows per workgroup
+        if (grid > 0x7fffffffull) return hipErrorInvalidValue;
+#define GBDPCG_X(NX, NU)                                                                                                       \
+    if (nx == NX && nu == NU) {                                                                                                \
+        hipLaunchKernelGGL((schur_gamma_quad_kernel<T, NX, NU>), dim3((uint32_t)grid), dim3(256), 0, s, N, rows, Ginv, C, g, c, gamma); \
+        return hipGetLastError();                                                                                              \
+    }
+        GBDPCG_QUAD_SHAPES(GBDPCG_X)
+#undef GBDPCG_X
+    }
+    const size_t wave_bytes = (size_t)gamma_wave_elems(nx, nu) * sizeof(T);
+    const uint32_t waves = waves_for(dev, wave_bytes);
+    if (!waves) return hipErrorInvalidValue;
+    const uint64_t grid = (rows + waves - 1) / waves;
+    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
+    const size_t lds = waves * wave_bytes;
+    auto kern = schur_gamma_kernel<T>;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(64 * waves), lds, s, nx, nu, N, rows, Ginv, C, g, c, gamma);
+    return hipGetLastError();
+}
+
 template <typename T> bool schur_shape_ok(const DeviceInfo &dev, uint32_t nx, uint32_t nu)
 {
     return nx >= 1 && nu >= 1 && waves_for(dev, (size_t)schur_wave_elems(nx, nu) * sizeof(T)) != 0;
@@ -1052,6 +1271,10 @@ template hipError_t launch_recover_primal<float>(const DeviceInfo &, uint32_t, u
                                                  const float *, const float *, const float *, float *, hipStream_t);
 template hipError_t launch_recover_primal<double>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const double *,
                                                   const double *, const double *, const double *, double *, hipStream_t);
+template hipError_t launch_form_gamma<float>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const float *, const float *,
+                                             const float *, const float *, float *, hipStream_t);
+template hipError_t launch_form_gamma<double>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const double *,
+                                              const double *, const double *, const double *, double *, hipStream_t);
 template bool schur_shape_ok<float>(const DeviceInfo &, uint32_t, uint32_t);
 template bool schur_shape_ok<double>(const DeviceInfo &, uint32_t, uint32_t);
 

@@ -350,6 +350,50 @@ gbdpcg_status gbdpcg_graph_create_kkt_step_f64(gbdpcg_handle_t h, uint32_t nx, u
                                                uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z,
                                                gbdpcg_graph_t *out);
 
+/* A linearisation that is kept (linear and linear-time-varying MPC, real-time iterations, several inner steps on one set of
+ * Jacobians): G and C are unchanged since the gbdpcg_form_schur_* or gbdpcg_kkt_step_* that wrote S, G^-1 (and Phi^-1), only the
+ * gradients g and the residuals c are new (the measured state enters through c_0).  S, Phi^-1 and G^-1 stand, and
+ *     gamma = -(c + C G^-1 g):   gamma_0 = -(c_0 + Q_0^-1 q_0),   gamma_k = -(c_k + Q_k^-1 q_k - A_j Q_j^-1 q_j - B_j R_j^-1 r_j)
+ * is all that has to be formed before the solve.  gbdpcg_form_gamma_* does that from d_Ginv as form_schur wrote it (layouts
+ * above): nothing is inverted, S is neither read nor written, d_gamma is the only output.  Asynchronous on `stream`,
+ * capturable, never allocates.  d_C may be NULL when N == 1.  Null handle or required pointer, nx, nu, N or batch == 0:
+ * GBDPCG_ERR_INVALID; a shape gbdpcg_form_schur_* refuses: GBDPCG_ERR_UNSUPPORTED. */
+gbdpcg_status gbdpcg_form_gamma_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                    const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                    float *d_gamma, void *stream);
+gbdpcg_status gbdpcg_form_gamma_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                    const double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                    double *d_gamma, void *stream);
+
+/* The whole step on a kept linearisation as ONE call (or one hipGraph for fixed buffers): gbdpcg_form_gamma_*, then
+ * gbdpcg_solve_* on the caller's UNCHANGED d_S and d_Pinv (NULL: identity) from the d_lambda it finds (warm start), then
+ * gbdpcg_recover_primal_*.  Same results as the three calls, bit for bit.  d_S, d_Pinv, d_Ginv, d_C, d_g, d_c are read only;
+ * d_r, d_p, d_max_iter_exit may be NULL as in gbdpcg_solve_*.  The library cannot know that S was left alone since it was
+ * formed, so the solve takes no shortcut on trust: it runs in the handle's symmetric mode like any gbdpcg_solve_* (the default
+ * tests S and Pinv on the device).  A caller who keeps the S of form_schur untouched knows it to be symmetric in storage:
+ * gbdpcg_set_symmetric(h, 1) is theirs to use.  Replay the graph after rewriting g and c (and lambda, if no warm start is
+ * wanted) in place; like the other graph constructors it reserves what the solve needs. */
+gbdpcg_status gbdpcg_kkt_resolve_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                     const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                     const float *d_S, const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r,
+                                     float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                     float *d_z, void *stream);
+gbdpcg_status gbdpcg_kkt_resolve_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                     const double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                     const double *d_S, const double *d_Pinv, double *d_gamma, double *d_lambda, double *d_r,
+                                     double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                     double *d_z, void *stream);
+gbdpcg_status gbdpcg_graph_create_kkt_resolve_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                  const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                                  const float *d_S, const float *d_Pinv, float *d_gamma, float *d_lambda,
+                                                  float *d_r, float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                                  uint8_t *d_max_iter_exit, float *d_z, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_kkt_resolve_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                  const double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                                  const double *d_S, const double *d_Pinv, double *d_gamma, double *d_lambda,
+                                                  double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                  uint8_t *d_max_iter_exit, double *d_z, gbdpcg_graph_t *out);
+
 /* CSR ingestion (f3): repacks a host CSR matrix (csr_t<T>, include/types.cuh:7-15) whose
  * sparsity lies inside the block-tridiagonal pattern into the [L|D|R] layout (host arrays).
  * Entries outside the pattern give GBDPCG_ERR_INVALID.  Implements what the stub overload

@@ -301,6 +301,40 @@ void kktStep(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoints, uint
     }
 }
 
+// A linearisation that is kept (G, C unchanged since formSchur / kktStep): gamma alone from G^-1 and the new g, c ...
+template <typename T>
+void formGamma(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoints, uint32_t batch, const T *d_Ginv, const T *d_C,
+               const T *d_g, const T *d_c, T *d_gamma, hipStream_t stream = nullptr)
+{
+    static_assert(gbdpcg_detail::is_f32<T> || gbdpcg_detail::is_f64<T>, "formGamma<T>: T is float or double");
+    gbdpcg_handle_t h = gbdpcg_detail::handle();
+    if constexpr (gbdpcg_detail::is_f32<T>) {
+        GBDPCG_CHECK(gbdpcg_form_gamma_f32(h, stateSize, controlSize, knotPoints, batch, d_Ginv, d_C, d_g, d_c, d_gamma, stream), "formGamma");
+    } else {
+        GBDPCG_CHECK(gbdpcg_form_gamma_f64(h, stateSize, controlSize, knotPoints, batch, d_Ginv, d_C, d_g, d_c, d_gamma, stream), "formGamma");
+    }
+}
+
+// ... and the whole step on it: gamma -> PCG on the unchanged d_S, d_Pinv from the d_lambda found in the buffer -> primal step.
+// The solve runs in the handle's symmetric mode (gbdpcg.h: a caller who left the S of formSchur alone may set mode 1).
+template <typename T>
+void kktResolve(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoints, uint32_t batch, const T *d_Ginv, const T *d_C,
+                const T *d_g, const T *d_c, const T *d_S, const T *d_Pinv, T *d_gamma, T *d_lambda, T *d_z, uint32_t *d_iters,
+                uint8_t *d_max_iter_exit, struct pcg_config<T> *config, hipStream_t stream = nullptr)
+{
+    static_assert(gbdpcg_detail::is_f32<T> || gbdpcg_detail::is_f64<T>, "kktResolve<T>: T is float or double");
+    gbdpcg_handle_t h = gbdpcg_detail::handle();
+    if constexpr (gbdpcg_detail::is_f32<T>) {
+        GBDPCG_CHECK(gbdpcg_kkt_resolve_f32(h, stateSize, controlSize, knotPoints, batch, d_Ginv, d_C, d_g, d_c, d_S, d_Pinv, d_gamma,
+                                            d_lambda, nullptr, nullptr, config->pcg_exit_tol, config->pcg_max_iter, d_iters,
+                                            d_max_iter_exit, d_z, stream), "kktResolve");
+    } else {
+        GBDPCG_CHECK(gbdpcg_kkt_resolve_f64(h, stateSize, controlSize, knotPoints, batch, d_Ginv, d_C, d_g, d_c, d_S, d_Pinv, d_gamma,
+                                            d_lambda, nullptr, nullptr, config->pcg_exit_tol, config->pcg_max_iter, d_iters,
+                                            d_max_iter_exit, d_z, stream), "kktResolve");
+    }
+}
+
 // ---- the README's spelling (README.md:42): int pcg_solve<T>(cbtd_t *h_S, ...) ---------------------
 template <typename T>
 int pcg_solve(cbtd_t<T> *h_S, T *h_gamma, T *h_lambda, unsigned stateSize, unsigned knotPoints,
