@@ -35,6 +35,10 @@ SYMBOLS = [
     "gbdpcg_kkt_step_f32", "gbdpcg_kkt_step_f64", "gbdpcg_graph_create_kkt_step_f32", "gbdpcg_graph_create_kkt_step_f64",
     "gbdpcg_form_gamma_f32", "gbdpcg_form_gamma_f64", "gbdpcg_kkt_resolve_f32", "gbdpcg_kkt_resolve_f64",
     "gbdpcg_graph_create_kkt_resolve_f32", "gbdpcg_graph_create_kkt_resolve_f64",
+    "gbdpcg_solve_shared_f32", "gbdpcg_solve_shared_f64", "gbdpcg_graph_create_solve_shared_f32", "gbdpcg_graph_create_solve_shared_f64",
+    "gbdpcg_form_gamma_shared_f32", "gbdpcg_form_gamma_shared_f64", "gbdpcg_recover_primal_shared_f32", "gbdpcg_recover_primal_shared_f64",
+    "gbdpcg_kkt_resolve_shared_f32", "gbdpcg_kkt_resolve_shared_f64",
+    "gbdpcg_graph_create_kkt_resolve_shared_f32", "gbdpcg_graph_create_kkt_resolve_shared_f64",
     "gbdpcg_csr_to_bt_f32", "gbdpcg_csr_to_bt_f64", "gbdpcg_version",
 ]
 
@@ -48,6 +52,14 @@ def _resolve_argtypes(lib):
         getattr(lib, f"gbdpcg_form_gamma_{suf}").argtypes = head + [vp, vp]
         getattr(lib, f"gbdpcg_kkt_resolve_{suf}").argtypes = head + solve + [vp]
         getattr(lib, f"gbdpcg_graph_create_kkt_resolve_{suf}").argtypes = head + solve + [ctypes.POINTER(vp)]
+        # the shared-matrix twins: the same argument lists
+        plain = [vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, ft, u32, vp, vp]   # h, n, N, batch, S, Pinv, gamma, lambda, r, p, tol, max_iter, iters, flags
+        getattr(lib, f"gbdpcg_solve_shared_{suf}").argtypes = plain + [vp]
+        getattr(lib, f"gbdpcg_graph_create_solve_shared_{suf}").argtypes = plain + [ctypes.POINTER(vp)]
+        getattr(lib, f"gbdpcg_form_gamma_shared_{suf}").argtypes = head + [vp, vp]
+        getattr(lib, f"gbdpcg_recover_primal_shared_{suf}").argtypes = head + [vp, vp]      # (lambda in the place of c, z, stream)
+        getattr(lib, f"gbdpcg_kkt_resolve_shared_{suf}").argtypes = head + solve + [vp]
+        getattr(lib, f"gbdpcg_graph_create_kkt_resolve_shared_{suf}").argtypes = head + solve + [ctypes.POINTER(vp)]
 
 _lib = None
 
@@ -331,6 +343,77 @@ class Solver:
         gr = ctypes.c_void_p()
         fn = getattr(self.lib, f"gbdpcg_graph_create_kkt_resolve_{suf}")
         self._check(fn(*args, ctypes.byref(gr)), "graph_create_kkt_resolve")
+        return Graph(self, gr, keep=(Ginv, C, g, c, S, Pinv, gamma, lam, r, p, iters, max_iter_exit, z))
+
+    # ---- shared-matrix batches: ONE S, Pinv, Ginv, C (one problem's worth each) for `batch` sets of vectors (include/gbdpcg.h)
+    def _solve_shared_args(self, n, N, batch, S, Pinv, gamma, lam, r, p, tol, max_iter, iters, mie):
+        for t, cnt in ((S, 3 * n * n * N), (Pinv, 3 * n * n * N), (gamma, batch * n * N), (lam, batch * n * N), (r, batch * n * N),
+                       (p, batch * n * N)):
+            if t is not None:
+                assert t.is_cuda and t.is_contiguous() and t.numel() == cnt and t.dtype == S.dtype
+        suf, _ = _suffix(S)
+        return suf, (self.h, n, N, batch, _p(S), _p(Pinv), _p(gamma), _p(lam), _p(r), _p(p), tol, max_iter, _p(iters), _p(mie))
+
+    def solve_shared(self, n, N, batch, S, Pinv, gamma, lam, r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None,
+                     stream=None):
+        """gbdpcg_solve_shared_*: one S and Pinv (3 n^2 N elements each) for `batch` gamma / lambda.  Returns (iters, flags)."""
+        import torch
+        if iters is None:
+            iters = torch.empty(batch, dtype=torch.int32, device=S.device)
+        if max_iter_exit is None:
+            max_iter_exit = torch.empty(batch, dtype=torch.uint8, device=S.device)
+        suf, args = self._solve_shared_args(n, N, batch, S, Pinv, gamma, lam, r, p, tol, max_iter, iters, max_iter_exit)
+        self._check(getattr(self.lib, f"gbdpcg_solve_shared_{suf}")(*args, self._stream(stream)), "solve_shared")
+        return iters, max_iter_exit
+
+    def graph_solve_shared(self, n, N, batch, S, Pinv, gamma, lam, r, p, tol, max_iter, iters, max_iter_exit):
+        """Capture a shared-matrix solve into a hipGraph (gbdpcg_graph_create_solve_shared_*)."""
+        suf, args = self._solve_shared_args(n, N, batch, S, Pinv, gamma, lam, r, p, tol, max_iter, iters, max_iter_exit)
+        g = ctypes.c_void_p()
+        self._check(getattr(self.lib, f"gbdpcg_graph_create_solve_shared_{suf}")(*args, ctypes.byref(g)), "graph_create_solve_shared")
+        return Graph(self, g, keep=(S, Pinv, gamma, lam, r, p, iters, max_iter_exit))
+
+    def form_gamma_shared(self, nx, nu, N, batch, Ginv, C, g, c, gamma=None, stream=None):
+        """gbdpcg_form_gamma_shared_*: one problem's Ginv and C, `batch` g and c."""
+        import torch
+        suf, _ = _suffix(Ginv)
+        if gamma is None:
+            gamma = torch.empty(batch * nx * N, dtype=Ginv.dtype, device=Ginv.device)
+        fn = getattr(self.lib, f"gbdpcg_form_gamma_shared_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(Ginv), _p(C), _p(g), _p(c), _p(gamma), self._stream(stream)), "form_gamma_shared")
+        return gamma
+
+    def recover_primal_shared(self, nx, nu, N, batch, Ginv, C, g, lam, z=None, stream=None):
+        """gbdpcg_recover_primal_shared_*: one problem's Ginv and C, `batch` g and lambda."""
+        import torch
+        suf, _ = _suffix(Ginv)
+        if z is None:
+            z = torch.empty_like(g)
+        fn = getattr(self.lib, f"gbdpcg_recover_primal_shared_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(Ginv), _p(C), _p(g), _p(lam), _p(z), self._stream(stream)), "recover_primal_shared")
+        return z
+
+    def kkt_resolve_shared(self, nx, nu, N, batch, Ginv, C, g, c, S, Pinv, gamma, lam, z, r=None, p=None, tol=1e-6, max_iter=25,
+                           iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_kkt_resolve_shared_*: gamma -> PCG -> primal step on ONE Ginv, C, S, Pinv for `batch` g, c, lambda."""
+        import torch
+        if iters is None:
+            iters = torch.zeros(batch, dtype=torch.int32, device=Ginv.device)
+        if max_iter_exit is None:
+            max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=Ginv.device)
+        suf, args = self._resolve_args(nx, nu, N, batch, Ginv, C, g, c, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                                       max_iter_exit, z)
+        self._check(getattr(self.lib, f"gbdpcg_kkt_resolve_shared_{suf}")(*args, self._stream(stream)), "kkt_resolve_shared")
+        return iters, max_iter_exit
+
+    def graph_kkt_resolve_shared(self, nx, nu, N, batch, Ginv, C, g, c, S, Pinv, gamma, lam, r, p, tol, max_iter, iters, max_iter_exit,
+                                 z):
+        """Capture the shared-matrix resolve into one hipGraph (gbdpcg_graph_create_kkt_resolve_shared_*)."""
+        suf, args = self._resolve_args(nx, nu, N, batch, Ginv, C, g, c, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                                       max_iter_exit, z)
+        gr = ctypes.c_void_p()
+        self._check(getattr(self.lib, f"gbdpcg_graph_create_kkt_resolve_shared_{suf}")(*args, ctypes.byref(gr)),
+                    "graph_create_kkt_resolve_shared")
         return Graph(self, gr, keep=(Ginv, C, g, c, S, Pinv, gamma, lam, r, p, iters, max_iter_exit, z))
 
     def _kkt_args(self, nx, nu, N, batch, G, C, g, c, S, gamma, Ginv, Pinv, kind, lam, r, p, tol, max_iter, iters, mie, z):

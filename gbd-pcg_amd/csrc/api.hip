@@ -274,15 +274,22 @@ template <typename T>
 gbdpcg_status solve_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batch, const T *d_S, const T *d_Pinv,
                          const T *d_gamma, T *d_lambda, T *d_r, T *d_p, T tol, uint32_t max_iter,
                          uint32_t *d_iters, uint8_t *d_exit, hipStream_t stream, bool blocking = false,
-                         uint32_t given_verdict_stride = 0, bool known_symmetric = false)
+                         uint32_t given_verdict_stride = 0, bool known_symmetric = false,
+                         bool shared = false)   // gbdpcg_solve_shared_*: d_S, d_Pinv are ONE pair of matrices for the whole batch
 {
     if (!h || !d_S || !d_gamma || !d_lambda || !d_iters || !shape_ok(n, N, batch)) return GBDPCG_ERR_INVALID;
     if (!mappable<T>(n)) return GBDPCG_ERR_UNSUPPORTED;
+    // a shared pair is solved by the fused family alone, whatever path the handle is set to: the persistent and split kernels
+    // have no shared form
+    if (shared && !fused_fits<T>(h->dev, n, N)) return GBDPCG_ERR_UNSUPPORTED;
     PcgArgs<T> a{d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, n, N, batch, d_iters, d_exit};
     a.cluster_ws = h->cluster_ws;
     a.rescue_vec = h->cluster_rescue;   // (the persistent path points it at its own buffer below)
+    // problems the symmetry test of mode 2 looks at: the ONE pair of a shared batch is tested once, with the same kernels, and
+    // every problem follows that verdict (the SHARED kernels read the verdict of problem 0 for all of them)
+    const uint32_t vbatch = shared ? 1u : batch;
     DEVICE_SCOPE(h);
-    if (const uint32_t per = persist_slices<T>(h, n, N, batch, max_iter)) {
+    if (const uint32_t per = shared ? 0u : persist_slices<T>(h, n, N, batch, max_iter)) {
         const size_t ms = (size_t)3 * n * n * N, vs = (size_t)n * N;
         for (uint32_t b0 = 0; b0 < batch; b0 += per) {
             const uint32_t nb = batch - b0 < per ? batch - b0 : per;
@@ -293,7 +300,7 @@ gbdpcg_status solve_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t bat
         }
         return GBDPCG_OK;
     }
-    const gbdpcg_path path = pick_path<T>(h, n, N, batch);
+    const gbdpcg_path path = shared ? GBDPCG_PATH_FUSED : pick_path<T>(h, n, N, batch);
     if (path == GBDPCG_PATH_PERSISTENT || path == GBDPCG_PATH_PERSISTENT_1R) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         const bool capturing = hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
@@ -326,7 +333,7 @@ gbdpcg_status solve_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t bat
             // the caller inside this library KNOWS that every problem is symmetric in storage (gbdpcg_kkt_step_*: S written by
             // form_schur, Pinv by the stair kernel from that S): one launch, no test, no verdict bytes, no general launch
             a.symmetric = true;
-            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream));
+            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream, shared));
         } else if (has_sym && h->symmetric == 2 && given_verdict_stride) {
             // the verdict bytes are already in h->sym_flags, put there on this stream by the stair kernel that just
             // formed Pinv from S (gbdpcg_form_pinv_solve_*): no test launch
@@ -334,11 +341,11 @@ gbdpcg_status solve_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t bat
             a.sel = h->sym_flags;
             a.symmetric = true;
             a.want = 1;
-            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream));
+            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream, shared));
             a.symmetric = false;
             a.want = 0;
-            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream));
-        } else if (has_sym && h->symmetric == 2 && resident_sym_verifies<T>(h->dev, n, N, d_S, d_Pinv)) {
+            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream, shared));
+        } else if (has_sym && h->symmetric == 2 && !shared && resident_sym_verifies<T>(h->dev, n, N, d_S, d_Pinv)) {
             // AUTO on the CU-resident symmetric kernel: it takes EVERY problem and tests L_{k+1} == R_k^T itself, against the
             // tiles it holds anyway (no test launch, no second read of R); it writes one verdict byte per problem and leaves
             // the problems that fail untouched for the general launch, which takes exactly those.  One byte per problem:
@@ -360,7 +367,7 @@ gbdpcg_status solve_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t bat
             a.sel_stride = 1;
             a.sel = h->sym_flags;
             a.want = 0;
-            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream));
+            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream, shared));
         } else if (has_sym && h->symmetric == 2) {
             // AUTO: test L_{k+1} == R_k^T on the device (S, then Pinv and-ed in), then launch BOTH kernels:
             // the symmetric one takes the problems that passed, the general one the rest.  No host
@@ -369,7 +376,7 @@ gbdpcg_status solve_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t bat
             // else one flag per problem
             const uint32_t vpp = check_pair_chunks<T>(n, N);
             const bool aligned16 = !((reinterpret_cast<uintptr_t>(d_S) | reinterpret_cast<uintptr_t>(d_Pinv)) % 16);
-            const size_t need_flags = (size_t)batch * (vpp && aligned16 ? vpp : 1);
+            const size_t need_flags = (size_t)vbatch * (vpp && aligned16 ? vpp : 1);
             if (need_flags > h->sym_cap) {
                 hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
                 if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
@@ -379,24 +386,24 @@ gbdpcg_status solve_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t bat
             }
             hipError_t cerr = hipSuccess;
             uint32_t stride = 1;
-            if (vpp && launch_check_symmetric_pair<T>(n, N, batch, d_S, d_Pinv, h->sym_flags, stream, &cerr, &stride)) {
+            if (vpp && launch_check_symmetric_pair<T>(n, N, vbatch, d_S, d_Pinv, h->sym_flags, stream, &cerr, &stride)) {
                 HIP_TRY(h, cerr);
             } else {
                 stride = 1;
-                HIP_TRY(h, launch_check_symmetric<T>(h->dev, n, N, batch, d_S, h->sym_flags, false, stream));
-                HIP_TRY(h, launch_check_symmetric<T>(h->dev, n, N, batch, d_Pinv, h->sym_flags, true, stream));
+                HIP_TRY(h, launch_check_symmetric<T>(h->dev, n, N, vbatch, d_S, h->sym_flags, false, stream));
+                HIP_TRY(h, launch_check_symmetric<T>(h->dev, n, N, vbatch, d_Pinv, h->sym_flags, true, stream));
             }
             a.sel_stride = stride;
             a.sel = h->sym_flags;
             a.symmetric = true;
             a.want = 1;
-            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream));
+            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream, shared));
             a.symmetric = false;
             a.want = 0;
-            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream));
+            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream, shared));
         } else {
             a.symmetric = has_sym && h->symmetric == 1;
-            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream));
+            HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream, shared));
         }
     } else {
         const size_t need = split_workspace_bytes<T>(n, N, batch);
@@ -540,10 +547,11 @@ gbdpcg_status form_schur_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint3
                               const T *d_g, const T *d_c, T *d_S, T *d_gamma, T *d_Ginv, void *stream);
 template <typename T>
 gbdpcg_status recover_primal_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv,
-                                  const T *d_C, const T *d_g, const T *d_lambda, T *d_z, void *stream);
+                                  const T *d_C, const T *d_g, const T *d_lambda, T *d_z, void *stream, bool shared = false);
 template <typename T>
 gbdpcg_status form_gamma_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv, const T *d_C,
-                              const T *d_g, const T *d_c, T *d_gamma, void *stream);
+                              const T *d_g, const T *d_c, T *d_gamma, void *stream, bool shared = false);
+// (shared: d_Ginv and d_C are one problem's blocks, used by every problem of the batch)
 
 // The operands of the steps either side of the solve (gbdpcg_kkt_step_*): S and gamma are formed from them before, z after.
 template <typename T> struct KktOperands {
@@ -551,6 +559,7 @@ template <typename T> struct KktOperands {
     const T *G, *C, *g, *c;
     T *Ginv, *z;
     bool resolve = false;   // gbdpcg_kkt_resolve_*: G is not looked at, Ginv, S and Pinv are read only
+    bool shared = false;    // gbdpcg_kkt_resolve_shared_*: Ginv, C, S and Pinv are ONE problem's, used by every problem of the batch
 };
 
 // KKT blocks -> S, gamma, G^-1 -> Phi^-1 -> PCG -> primal step, on one stream (capturable: no allocation after the first
@@ -595,14 +604,18 @@ gbdpcg_status kkt_step_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t N, uint32_t
 template <typename T>
 gbdpcg_status kkt_resolve_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv, const T *d_C,
                                const T *d_g, const T *d_c, const T *d_S, const T *d_Pinv, T *d_gamma, T *d_lambda, T *d_r, T *d_p,
-                               T tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_exit, T *d_z, hipStream_t stream)
+                               T tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_exit, T *d_z, hipStream_t stream,
+                               bool shared = false)   // the three shared calls: one Ginv, C, S, Pinv for the whole batch
 {
     if (!h || !d_S || !d_lambda || !d_iters || !d_z) return GBDPCG_ERR_INVALID;
-    gbdpcg_status st = form_gamma_impl<T>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, d_gamma, stream);
+    // (a shape the shared solve cannot take is refused before gamma is written)
+    if (shared && shape_ok(nx, N, batch) && mappable<T>(nx) && !fused_fits<T>(h->dev, nx, N)) return GBDPCG_ERR_UNSUPPORTED;
+    gbdpcg_status st = form_gamma_impl<T>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, d_gamma, stream, shared);
     if (st != GBDPCG_OK) return st;
-    st = solve_impl<T>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, stream);
+    st = solve_impl<T>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, stream, false, 0,
+                       false, shared);
     if (st != GBDPCG_OK) return st;
-    return recover_primal_impl<T>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_lambda, d_z, stream);
+    return recover_primal_impl<T>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_lambda, d_z, stream, shared);
 }
 
 template <typename T>
@@ -610,13 +623,21 @@ gbdpcg_status graph_create_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint3
                                 const T *d_Pinv, const T *d_gamma, T *d_lambda, T *d_r, T *d_p, T tol,
                                 uint32_t max_iter, uint32_t *d_iters, uint8_t *d_exit, gbdpcg_graph_t *out,
                                 int form_kind = -1,  // >= 0: the graph also forms Pinv (written through d_Pinv) from S
-                                const KktOperands<T> *kkt = nullptr)  // the graph also forms S, gamma (written through d_S, d_gamma) and recovers z
+                                const KktOperands<T> *kkt = nullptr,  // the graph also forms S, gamma (written through d_S, d_gamma) and recovers z
+                                bool shared = false)  // gbdpcg_graph_create_solve_shared_* (the kkt form carries its own flag)
 {
     if (!h || !out) return GBDPCG_ERR_INVALID;
     *out = nullptr;
     if (!shape_ok(n, N, batch)) return GBDPCG_ERR_INVALID;
+    shared = shared || (kkt && kkt->shared);
     DEVICE_SCOPE(h);
-    if (const uint32_t per = persist_slices<T>(h, n, N, batch, max_iter)) {   // the hand-off words of the slices (solve_impl)
+    if (shared) {   // the fused family whatever the handle's path: verdict bytes are all it may need
+        if (mappable<T>(n) && !fused_fits<T>(h->dev, n, N)) return GBDPCG_ERR_UNSUPPORTED;
+        if (h->symmetric == 2) {
+            gbdpcg_status st = ensure_sym_flags(h, verdict_bytes<T>(n, N, batch));
+            if (st != GBDPCG_OK) return st;
+        }
+    } else if (const uint32_t per = persist_slices<T>(h, n, N, batch, max_iter)) {   // the hand-off words of the slices (solve_impl)
         void *pws = nullptr;
         gbdpcg_status st = get_pws(h, sizeof(T), n, N, per, persist_total_bytes<T>(h, n, N, per), true, &pws);
         if (st == GBDPCG_OK && batch % per) st = get_pws(h, sizeof(T), n, N, batch % per, persist_total_bytes<T>(h, n, N, batch % per), true, &pws);
@@ -646,7 +667,7 @@ gbdpcg_status graph_create_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint3
     if (e == hipSuccess) {
         if (kkt && kkt->resolve)
             st = kkt_resolve_impl<T>(h, n, kkt->nu, N, batch, kkt->Ginv, kkt->C, kkt->g, kkt->c, d_S, d_Pinv, const_cast<T *>(d_gamma),
-                                     d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, kkt->z, cs);
+                                     d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, kkt->z, cs, kkt->shared);
         else if (kkt)
             st = kkt_step_impl<T>(h, n, N, batch, *kkt, const_cast<T *>(d_S), const_cast<T *>(d_gamma), const_cast<T *>(d_Pinv),
                                   (gbdpcg_pinv_kind)form_kind, d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, cs);
@@ -655,7 +676,7 @@ gbdpcg_status graph_create_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint3
                                          d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, cs);
         else
             st = solve_impl<T>(h, n, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit,
-                               cs);
+                               cs, false, 0, false, shared);
         hipError_t e2 = hipStreamEndCapture(cs, &g->graph);
         if (st == GBDPCG_OK && e2 != hipSuccess) st = fail(h, e2);
     } else {
@@ -717,24 +738,24 @@ gbdpcg_status form_schur_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint3
 }
 template <typename T>
 gbdpcg_status recover_primal_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv,
-                                  const T *d_C, const T *d_g, const T *d_lambda, T *d_z, void *stream)
+                                  const T *d_C, const T *d_g, const T *d_lambda, T *d_z, void *stream, bool shared)
 {
     if (!h || !d_Ginv || !d_g || !d_lambda || !d_z || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))
         return GBDPCG_ERR_INVALID;
     if (!schur_shape_ok<T>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;
     DEVICE_SCOPE(h);
-    HIP_TRY(h, launch_recover_primal<T>(h->dev, nx, nu, N, batch, d_Ginv, d_C, d_g, d_lambda, d_z, (hipStream_t)stream));
+    HIP_TRY(h, launch_recover_primal<T>(h->dev, nx, nu, N, batch, d_Ginv, d_C, d_g, d_lambda, d_z, (hipStream_t)stream, shared));
     return GBDPCG_OK;
 }
 template <typename T>
 gbdpcg_status form_gamma_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv, const T *d_C,
-                              const T *d_g, const T *d_c, T *d_gamma, void *stream)
+                              const T *d_g, const T *d_c, T *d_gamma, void *stream, bool shared)
 {
     if (!h || !d_Ginv || !d_g || !d_c || !d_gamma || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))
         return GBDPCG_ERR_INVALID;
     if (!schur_shape_ok<T>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;
     DEVICE_SCOPE(h);
-    HIP_TRY(h, launch_form_gamma<T>(h->dev, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, d_gamma, (hipStream_t)stream));
+    HIP_TRY(h, launch_form_gamma<T>(h->dev, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, d_gamma, (hipStream_t)stream, shared));
     return GBDPCG_OK;
 }
 }  // namespace
@@ -1174,6 +1195,68 @@ GBDPCG_KKT_STEP(f64, double)
 GBDPCG_KKT_RESOLVE(f32, float)
 GBDPCG_KKT_RESOLVE(f64, double)
 #undef GBDPCG_KKT_RESOLVE
+
+// ---- shared-matrix batches: one S, Phi^-1 (and one G^-1, C) for `batch` right-hand sides.  Twins of the entry points above, same
+// argument lists; the single matrices are one problem's worth (made by the batch-1 forms of gbdpcg_form_schur_*, gbdpcg_form_pinv_*
+// or gbdpcg_kkt_step_*).
+#define GBDPCG_SHARED(SUF, TYPE)                                                                                                    \
+    gbdpcg_status gbdpcg_solve_shared_##SUF(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batch, const TYPE *d_S,              \
+                                            const TYPE *d_Pinv, const TYPE *d_gamma, TYPE *d_lambda, TYPE *d_r, TYPE *d_p, TYPE tol, \
+                                            uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, void *stream)           \
+    {                                                                                                                               \
+        return solve_impl<TYPE>(h, n, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters, d_max_iter_exit,   \
+                                (hipStream_t)stream, false, 0, false, true);                                                        \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_graph_create_solve_shared_##SUF(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batch, const TYPE *d_S, \
+                                                         const TYPE *d_Pinv, const TYPE *d_gamma, TYPE *d_lambda, TYPE *d_r,        \
+                                                         TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters,                 \
+                                                         uint8_t *d_max_iter_exit, gbdpcg_graph_t *out)                             \
+    {                                                                                                                               \
+        return graph_create_impl<TYPE>(h, n, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters,             \
+                                       d_max_iter_exit, out, -1, nullptr, true);                                                    \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_form_gamma_shared_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,             \
+                                                 const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c,             \
+                                                 TYPE *d_gamma, void *stream)                                                       \
+    {                                                                                                                               \
+        return form_gamma_impl<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, d_gamma, stream, true);                             \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_recover_primal_shared_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,         \
+                                                     const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g, const TYPE *d_lambda,    \
+                                                     TYPE *d_z, void *stream)                                                       \
+    {                                                                                                                               \
+        return recover_primal_impl<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_lambda, d_z, stream, true);                        \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_kkt_resolve_shared_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,            \
+                                                  const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c,            \
+                                                  const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda, TYPE *d_r,    \
+                                                  TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters,                        \
+                                                  uint8_t *d_max_iter_exit, TYPE *d_z, void *stream)                                \
+    {                                                                                                                               \
+        return kkt_resolve_impl<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol,     \
+                                      max_iter, d_iters, d_max_iter_exit, d_z, (hipStream_t)stream, true);                          \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_graph_create_kkt_resolve_shared_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N,              \
+                                                               uint32_t batch, const TYPE *d_Ginv, const TYPE *d_C,                \
+                                                               const TYPE *d_g, const TYPE *d_c, const TYPE *d_S,                  \
+                                                               const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda, TYPE *d_r,       \
+                                                               TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters,          \
+                                                               uint8_t *d_max_iter_exit, TYPE *d_z, gbdpcg_graph_t *out)           \
+    {                                                                                                                               \
+        /* what the captured calls would refuse is refused before anything is reserved or captured */                                \
+        if (!h || !out || !d_Ginv || !d_g || !d_c || !d_S || !d_gamma || !d_lambda || !d_iters || !d_z || (!d_C && N > 1) ||        \
+            nu == 0 || !shape_ok(nx, N, batch))                                                                                     \
+            return GBDPCG_ERR_INVALID;                                                                                              \
+        if (!schur_shape_ok<TYPE>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;                                                   \
+        KktOperands<TYPE> k{nu, nullptr, d_C, d_g, d_c, const_cast<TYPE *>(d_Ginv), d_z};                                           \
+        k.resolve = true;                                                                                                           \
+        k.shared = true;                                                                                                            \
+        return graph_create_impl<TYPE>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters,            \
+                                       d_max_iter_exit, out, -1, &k);                                                               \
+    }
+GBDPCG_SHARED(f32, float)
+GBDPCG_SHARED(f64, double)
+#undef GBDPCG_SHARED
 
 gbdpcg_status gbdpcg_csr_to_bt_f32(uint32_t n, uint32_t N, const uint32_t *row_ptr, const uint32_t *col_ind,
                                    const float *val, float *h_M)

@@ -22,9 +22,13 @@ struct DeviceInfo {
 constexpr uint32_t kItersGaveUp = 0xffffffffu;
 
 // Does this launch own problem `prob`?  (see PcgArgs::sel)
-template <typename A> __device__ __forceinline__ bool pcg_takes(const A &a, uint32_t prob)
+// SHARED (here and below): the instantiations of gbdpcg_solve_shared_* -- a.S and a.Pinv are ONE problem's matrices, used by every
+// problem of the batch (the vectors stay per problem), and a.sel, where set, holds ONE verdict that every problem follows.  A
+// compile-time switch throughout: the per-problem instantiations are what they were before the shared form existed.
+template <bool SHARED = false, typename A> __device__ __forceinline__ bool pcg_takes(const A &a, uint32_t prob)
 {
     if (!a.sel) return true;
+    if constexpr (SHARED) prob = 0;
     bool sym = true;
     for (uint32_t c = 0; c < a.sel_stride; ++c) sym &= a.sel[(size_t)prob * a.sel_stride + c] == 1;
     return sym == (a.want == 1);
@@ -34,13 +38,13 @@ template <typename A> __device__ __forceinline__ bool pcg_takes(const A &a, uint
 // (j < count <= 64).  Every lane of the calling wave fetches the verdict bytes of one problem, so a workgroup that walks
 // over many problems pays one memory round trip for all of them instead of one per problem; every wave of a workgroup
 // that calls it gets the same mask.  All 64 lanes must be active.
-template <typename A>
+template <bool SHARED = false, typename A>
 __device__ __forceinline__ unsigned long long pcg_takes_mask(const A &a, uint32_t first, uint32_t step, uint32_t count, uint32_t lane)
 {
     if (!a.sel) return count >= 64 ? ~0ull : ((1ull << count) - 1ull);
     bool mine = false;
     if (lane < count) {
-        const size_t prob = (size_t)first + (size_t)lane * step;
+        const size_t prob = SHARED ? (size_t)0 : (size_t)first + (size_t)lane * step;
         bool sym = true;
         for (uint32_t c = 0; c < a.sel_stride; ++c) sym &= a.sel[prob * a.sel_stride + c] == 1;
         mine = sym == (a.want == 1);
@@ -116,18 +120,19 @@ template <typename T> hipError_t launch_spmv(const DeviceInfo &dev, const SpmvAr
 // ---- pcg_fused.hip : one workgroup per problem
 template <typename T> size_t fused_lds_bytes(uint32_t n, uint32_t N, uint32_t waves);
 template <typename T> bool fused_fits(const DeviceInfo &dev, uint32_t n, uint32_t N);
-template <typename T> hipError_t launch_pcg_fused(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s);
+// (shared, here and in the launchers below: the SHARED instantiations -- one pair of matrices for the whole batch)
+template <typename T> hipError_t launch_pcg_fused(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, bool shared = false);
 
 // ---- pcg_resident.hip : both matrices register-resident, one 8-wave workgroup per problem.
 // Returns false when the shape is not eligible (then nothing was launched).
 template <typename T> bool resident_shape(uint32_t n, uint32_t N);  // shape handled by the resident kernel
 template <typename T> void resident_prepare(uint32_t n, uint32_t N);  // runtime queries of that kernel, outside any capture
 template <typename T>
-bool launch_pcg_resident(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err);
+bool launch_pcg_resident(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err, bool shared = false);
 // Symmetric matrices resident on one CU (pcg_resident_sym.hip): n = 14, fp32, N <= 128, a.symmetric set.
 template <typename T> bool resident_sym_shape(uint32_t n, uint32_t N);
 template <typename T>
-bool launch_pcg_resident_sym(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err);
+bool launch_pcg_resident_sym(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err, bool shared = false);
 // Its verifying form: every problem, L_{k+1} == R_k^T of S and Pinv tested inside the solve, verdicts into a.verdict_out
 // (stride 1); a problem that fails is left untouched.  resident_sym_verifies: would that form take this solve (n = 14, fp32,
 // N <= 128, S and Pinv 16-byte aligned)?
@@ -142,7 +147,7 @@ size_t cluster_workspace_bytes(const DeviceInfo &dev);
 size_t cluster_rescue_bytes(const DeviceInfo &dev);   // PcgArgs::rescue_vec of a cluster launch
 // Returns false when the launch is not eligible (then nothing was launched).
 template <typename T>
-bool launch_pcg_cluster(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err);
+bool launch_pcg_cluster(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err, bool shared = false);
 
 // ---- pcg_split.hip : many workgroups per problem, two launches per iteration
 template <typename T> size_t split_workspace_bytes(uint32_t n, uint32_t N, uint32_t batch);
@@ -199,11 +204,12 @@ hipError_t launch_form_schur(const DeviceInfo &dev, uint32_t nx, uint32_t nu, ui
                              const T *g, const T *c, T *S, T *gamma, T *Ginv, hipStream_t s);
 template <typename T>
 hipError_t launch_recover_primal(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *Ginv,
-                                 const T *C, const T *g, const T *lambda, T *z, hipStream_t s);
+                                 const T *C, const T *g, const T *lambda, T *z, hipStream_t s, bool shared = false);
 // gamma = -(c + C G^-1 g) alone, from the G^-1 launch_form_schur wrote: G and C unchanged, new g and c (S is not touched)
 template <typename T>
 hipError_t launch_form_gamma(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *Ginv, const T *C,
-                             const T *g, const T *c, T *gamma, hipStream_t s);
+                             const T *g, const T *c, T *gamma, hipStream_t s, bool shared = false);
+// (shared, both launchers: Ginv and C are one problem's blocks, used by every problem of the batch)
 template <typename T> bool schur_shape_ok(const DeviceInfo &dev, uint32_t nx, uint32_t nu);
 
 }  // namespace gbdpcg

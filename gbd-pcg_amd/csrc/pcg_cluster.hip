@@ -129,7 +129,9 @@ template <typename T, int NCT> struct ClusterLight {
 // ONE: a cluster of one workgroup (launch_pcg_cluster: only where the shape has such launches) -- nobody to hand anything to, the wave
 // partials meet in LDS, in the same words and the same sum as in memory.  A compile-time switch: as a run-time test inside the
 // hand-off it cost the clusters of two to four members 4 %.
-template <typename T, int NCT, int V, bool STAGED, bool ONE = false>
+// SHARED (gbdpcg_solve_shared_*): a.S and a.Pinv are one pair of matrices for the whole batch -- every cluster loads its tiles from
+// it (zero problem stride; after the first round they come from L2 / Infinity Cache).
+template <typename T, int NCT, int V, bool STAGED, bool ONE = false, bool SHARED = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(ClusterLight<T, NCT>::value ? 4 : 2)))
 void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
                                                           uint32_t clusters, uint32_t spin_limit, uint32_t drop_block, bool no_plain)
@@ -196,7 +198,11 @@ void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
     };
     const uint32_t wl = (cnt - 1) / Dg::BPW, lb = (cnt - 1) - wl * Dg::BPW;   // the last knot: wave wl, lanes [7 lb, 7 lb + 7)
     const uint32_t POLL = wl == 7 ? 6u : 7u;                          // the polling wave: never wave 0, never wave wl
-    const size_t mstride = (size_t)3 * n * n * N;
+    size_t mstride = (size_t)3 * n * n * N;
+    if constexpr (SHARED) {   // zero, but not a constant the compiler may build on: the code, and with it the registers, of the per-problem kernel
+        mstride = 0;
+        asm volatile("" : "+s"(mstride));
+    }
 
     unsigned char *slots = ws + kClCtrlBytes;
     const __amdgpu_buffer_rsrc_t region =
@@ -345,7 +351,7 @@ void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
     bool any = a.sel == nullptr;
     for (uint32_t first = c; !any && first < a.batch; first += 64 * clusters) {
         const uint32_t left = (a.batch - first + clusters - 1) / clusters;
-        any = pcg_takes_mask(a, first, clusters, left < 64 ? left : 64u, lane) != 0ull;
+        any = pcg_takes_mask<SHARED>(a, first, clusters, left < 64 ? left : 64u, lane) != 0ull;
     }
     if (any) {
         // this workgroup's slot, both parities, cleared by the lanes that will publish into the same words (a wave's stores
@@ -367,7 +373,7 @@ void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
         }
     }
     if (any) for (uint32_t prob = c; prob < a.batch; prob += clusters) {
-        if (!pcg_takes(a, prob)) continue;   // this launch is not the one that owns the problem (same verdict in every member)
+        if (!pcg_takes<SHARED>(a, prob)) continue;   // this launch is not the one that owns the problem (same verdict in every member)
         if (dead) {
             if (a.rescue_off && h == 0 && tid == 0) {   // (hooks build only: show the mark)
                 a.iters[prob] = kItersGaveUp;
@@ -688,7 +694,7 @@ void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
         if (from != 0xffffffffu) {
             T *vec = reinterpret_cast<T *>(a.rescue_vec) + (size_t)c * rescue_vec_elems<T>(n, N);
             for (uint32_t prob = from; prob < a.batch; prob += clusters)
-                if (pcg_takes(a, prob)) stream_rescue<T, Dg::WAVES>(a, prob, vec, rescue_red);
+                if (pcg_takes<SHARED>(a, prob)) stream_rescue<T, Dg::WAVES, SHARED>(a, prob, vec, rescue_red);
         }
     }
     // ---- the workgroup that finishes last gives the next launch its number ------------------------------------------------
@@ -764,7 +770,7 @@ size_t cluster_rescue_bytes(const DeviceInfo &dev)
 }
 
 template <typename T>
-bool launch_pcg_cluster(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err)
+bool launch_pcg_cluster(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err, bool shared)
 {
     const uint32_t H = cluster_members<T>(a.n, a.N);
     if (H == 0 || !a.cluster_ws || a.symmetric) return false;
@@ -812,10 +818,10 @@ bool launch_pcg_cluster(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t 
             const size_t tail = (size_t)ClusterTail<TT, NN>::COLS * 512 * 8;                                \
             size_t lds = tail;                                                                                           \
             void (*kern)(PcgArgs<T>, unsigned char *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, bool) =          \
-                pcg_cluster_kernel<T, NN, VV, false>;                                                                    \
+                shared ? pcg_cluster_kernel<T, NN, VV, false, false, true> : pcg_cluster_kernel<T, NN, VV, false>;       \
             if constexpr (can_stage) {                                                                                   \
                 if (staged) {                                                                                            \
-                    kern = pcg_cluster_kernel<T, NN, VV, true>;                                                          \
+                    kern = shared ? pcg_cluster_kernel<T, NN, VV, true, false, true> : pcg_cluster_kernel<T, NN, VV, true>; \
                     if (dense_stage_lds_bytes<TT, NN, VV>() > lds) lds = dense_stage_lds_bytes<TT, NN, VV>();            \
                 }                                                                                                        \
             }                                                                                                            \
@@ -823,9 +829,9 @@ bool launch_pcg_cluster(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t 
                (no single-workgroup kernel in pcg_resident.hip: fp32 16 and 18, fp64 14, 15, 16) */                      \
             if constexpr (!ClusterLight<TT, NN>::value && ((sizeof(TT) == 4 && NN >= 16) || (sizeof(TT) == 8 && NN >= 14))) { \
                 if (H == 1) {                                                                                            \
-                    kern = pcg_cluster_kernel<T, NN, VV, false, true>;                                                   \
+                    kern = shared ? pcg_cluster_kernel<T, NN, VV, false, true, true> : pcg_cluster_kernel<T, NN, VV, false, true>; \
                     if constexpr (can_stage) {                                                                           \
-                        if (staged) kern = pcg_cluster_kernel<T, NN, VV, true, true>;                                    \
+                        if (staged) kern = shared ? pcg_cluster_kernel<T, NN, VV, true, true, true> : pcg_cluster_kernel<T, NN, VV, true, true>; \
                     }                                                                                                    \
                 }                                                                                                        \
             }                                                                                                            \
@@ -848,7 +854,7 @@ bool launch_pcg_cluster(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t 
 
 template uint32_t cluster_members<float>(uint32_t, uint32_t);
 template uint32_t cluster_members<double>(uint32_t, uint32_t);
-template bool launch_pcg_cluster<float>(const DeviceInfo &, const PcgArgs<float> &, hipStream_t, hipError_t *);
-template bool launch_pcg_cluster<double>(const DeviceInfo &, const PcgArgs<double> &, hipStream_t, hipError_t *);
+template bool launch_pcg_cluster<float>(const DeviceInfo &, const PcgArgs<float> &, hipStream_t, hipError_t *, bool);
+template bool launch_pcg_cluster<double>(const DeviceInfo &, const PcgArgs<double> &, hipStream_t, hipError_t *, bool);
 
 }  // namespace gbdpcg

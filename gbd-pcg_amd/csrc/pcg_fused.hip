@@ -21,7 +21,7 @@ namespace gbdpcg {
 
 // SYM: both matrices are symmetric block-tridiagonal (L_{k+1} == R_k^T) and are streamed through
 // SymStream (bt_sym.hpp): [D_k | R_k] only, 2/3 of the bytes.  The per-problem solve is StreamSolver::solve (pcg_stream.hpp).
-template <typename T, int NCT, int V, int WAVES, bool SYM>
+template <typename T, int NCT, int V, int WAVES, bool SYM, bool SHARED = false>
 __global__ __launch_bounds__(WAVES * 64) void pcg_fused_kernel(PcgArgs<T> a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -30,8 +30,8 @@ __global__ __launch_bounds__(WAVES * 64) void pcg_fused_kernel(PcgArgs<T> a)
     const FusedCarve<T> cv(n, a.N, WAVES, SYM);
     StreamSolver<T, NCT, V, WAVES, SYM> sv(n, threadIdx.x);
     for (uint32_t prob = blockIdx.x; prob < a.batch; prob += gridDim.x) {
-        if (!pcg_takes(a, prob)) continue;  // this launch is not the one that owns the problem
-        sv.solve(a, prob, smem + cv.xa, smem + cv.xb, smem + cv.yc, smem + cv.lam, smem + cv.red, smem + cv.zc);
+        if (!pcg_takes<SHARED>(a, prob)) continue;  // this launch is not the one that owns the problem
+        sv.template solve<SHARED>(a, prob, smem + cv.xa, smem + cv.xb, smem + cv.yc, smem + cv.lam, smem + cv.red, smem + cv.zc);
     }
 }
 
@@ -59,11 +59,11 @@ template <typename T> bool fused_fits(const DeviceInfo &dev, uint32_t n, uint32_
 }
 
 template <typename T, int NCT, int V, int WAVES, bool SYM = false>
-static hipError_t launch_fused_w(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s)
+static hipError_t launch_fused_w(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, bool shared)
 {
     const size_t lds = (size_t)FusedCarve<T>(a.n, a.N, WAVES, SYM).total * sizeof(T);
     if (lds > dev.lds_per_wg_max) return hipErrorInvalidValue;
-    auto kern = pcg_fused_kernel<T, NCT, V, WAVES, SYM>;
+    auto kern = shared ? pcg_fused_kernel<T, NCT, V, WAVES, SYM, true> : pcg_fused_kernel<T, NCT, V, WAVES, SYM>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -86,7 +86,7 @@ static hipError_t launch_fused_w(const DeviceInfo &dev, const PcgArgs<T> &a, hip
 }
 
 template <typename T, int NCT, int V>
-static hipError_t launch_fused_v(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s)
+static hipError_t launch_fused_v(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, bool shared)
 {
     // Few problems: give each the widest workgroup.  Many problems: 8-wave workgroups, two resident per
     // CU -- one streams while the other sits in its reduction / vector-update barriers, and only
@@ -107,48 +107,48 @@ static hipError_t launch_fused_v(const DeviceInfo &dev, const PcgArgs<T> &a, hip
                              (!a.Pinv || reinterpret_cast<uintptr_t>(a.Pinv) % al == 0);
         if (a.symmetric && aligned && waves != 4) {
             if (waves == 16 && FusedCarve<T>(a.n, a.N, 16, true).total * sizeof(T) <= dev.lds_per_wg_max)
-                return launch_fused_w<T, NCT, V, 16, true>(dev, a, s);
+                return launch_fused_w<T, NCT, V, 16, true>(dev, a, s, shared);
             if (FusedCarve<T>(a.n, a.N, 8, true).total * sizeof(T) <= dev.lds_per_wg_max)
-                return launch_fused_w<T, NCT, V, 8, true>(dev, a, s);
+                return launch_fused_w<T, NCT, V, 8, true>(dev, a, s, shared);
         }
     }
     switch (waves) {
-    case 16: return launch_fused_w<T, NCT, V, 16>(dev, a, s);
-    case 8: return launch_fused_w<T, NCT, V, 8>(dev, a, s);
-    default: return launch_fused_w<T, NCT, V, 4>(dev, a, s);
+    case 16: return launch_fused_w<T, NCT, V, 16>(dev, a, s, shared);
+    case 8: return launch_fused_w<T, NCT, V, 8>(dev, a, s, shared);
+    default: return launch_fused_w<T, NCT, V, 4>(dev, a, s, shared);
     }
 }
 
 template <typename T, int NCT>
-static hipError_t launch_fused_n(const DeviceInfo &dev, const PcgArgs<T> &a, int V, hipStream_t s)
+static hipError_t launch_fused_n(const DeviceInfo &dev, const PcgArgs<T> &a, int V, hipStream_t s, bool shared)
 {
-    if (V == 1) return launch_fused_v<T, NCT, 1>(dev, a, s);
+    if (V == 1) return launch_fused_v<T, NCT, 1>(dev, a, s, shared);
     if constexpr (NCT == 0 || NCT % 2 == 0) {
-        if (V == 2) return launch_fused_v<T, NCT, 2>(dev, a, s);
+        if (V == 2) return launch_fused_v<T, NCT, 2>(dev, a, s, shared);
     }
     if constexpr (sizeof(T) == 4 && (NCT == 0 || NCT % 4 == 0)) {
-        if (V == 4) return launch_fused_v<T, NCT, 4>(dev, a, s);
+        if (V == 4) return launch_fused_v<T, NCT, 4>(dev, a, s, shared);
     }
     return hipErrorInvalidValue;
 }
 
-template <typename T> hipError_t launch_pcg_fused(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s)
+template <typename T> hipError_t launch_pcg_fused(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, bool shared)
 {
     hipError_t rerr = hipSuccess;
-    if (launch_pcg_resident<T>(dev, a, s, &rerr)) return rerr;  // small problems: pcg_resident.hip
-    if (a.symmetric && launch_pcg_resident_sym<T>(dev, a, s, &rerr)) return rerr;  // pcg_resident_sym.hip
-    if (!a.symmetric && launch_pcg_cluster<T>(dev, a, s, &rerr)) return rerr;      // general storage over 2-4 CUs: pcg_cluster.hip
+    if (launch_pcg_resident<T>(dev, a, s, &rerr, shared)) return rerr;  // small problems: pcg_resident.hip
+    if (a.symmetric && launch_pcg_resident_sym<T>(dev, a, s, &rerr, shared)) return rerr;  // pcg_resident_sym.hip
+    if (!a.symmetric && launch_pcg_cluster<T>(dev, a, s, &rerr, shared)) return rerr;      // general storage over 2-4 CUs: pcg_cluster.hip
     const void *ptrs[] = {a.S, a.Pinv};
     const int V = choose_vec<T>(a.n, ptrs, 2);
     if (V == 0) return hipErrorInvalidValue;
     static const bool generic_only = getenv("GBDPCG_FORCE_GENERIC") != nullptr;  // tuning runs only
     if (!generic_only) {
 #define GBDPCG_CASE(NN) \
-    if (a.n == NN && V == best_v<T, NN>()) return launch_fused_v<T, NN, best_v<T, NN>()>(dev, a, s);
+    if (a.n == NN && V == best_v<T, NN>()) return launch_fused_v<T, NN, best_v<T, NN>()>(dev, a, s, shared);
         GBDPCG_SPECIALIZED_N(GBDPCG_CASE)
 #undef GBDPCG_CASE
     }
-    return launch_fused_n<T, 0>(dev, a, V, s);
+    return launch_fused_n<T, 0>(dev, a, V, s, shared);
 }
 
 template bool fused_has_symmetric<float>(const DeviceInfo &, uint32_t, uint32_t, uint32_t);
@@ -157,7 +157,7 @@ template size_t fused_lds_bytes<float>(uint32_t, uint32_t, uint32_t);
 template size_t fused_lds_bytes<double>(uint32_t, uint32_t, uint32_t);
 template bool fused_fits<float>(const DeviceInfo &, uint32_t, uint32_t);
 template bool fused_fits<double>(const DeviceInfo &, uint32_t, uint32_t);
-template hipError_t launch_pcg_fused<float>(const DeviceInfo &, const PcgArgs<float> &, hipStream_t);
-template hipError_t launch_pcg_fused<double>(const DeviceInfo &, const PcgArgs<double> &, hipStream_t);
+template hipError_t launch_pcg_fused<float>(const DeviceInfo &, const PcgArgs<float> &, hipStream_t, bool);
+template hipError_t launch_pcg_fused<double>(const DeviceInfo &, const PcgArgs<double> &, hipStream_t, bool);
 
 }  // namespace gbdpcg

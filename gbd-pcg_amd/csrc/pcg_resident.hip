@@ -15,7 +15,8 @@
 #define GBDPCG_RES_OCC 1   // 0: no register cap on the small-block instantiations of the resident kernel (A/B runs)
 #endif
 #if GBDPCG_RES_OCC
-#define GBDPCG_RES_OCC_ATTR __attribute__((amdgpu_waves_per_eu(NCT * sizeof(T) <= 32 || (NCT <= 6) || (V == 1 && sizeof(T) == 4 && NCT <= 11) ? 4 : 2)))   // n <= 8 in fp32, n <= 6 in fp64, odd n <= 11 in fp32 (one row per lane: 6n matrix registers)
+// (not the shared form at n = 8 in fp32: with its tiles live across the problem loop the cap put reloads from scratch inside the iterations)
+#define GBDPCG_RES_OCC_ATTR __attribute__((amdgpu_waves_per_eu((NCT * sizeof(T) <= 32 || (NCT <= 6) || (V == 1 && sizeof(T) == 4 && NCT <= 11)) && !(SHARED && sizeof(T) == 4 && NCT == 8) ? 4 : 2)))   // n <= 8 in fp32, n <= 6 in fp64, odd n <= 11 in fp32 (one row per lane: 6n matrix registers)
 #else
 #define GBDPCG_RES_OCC_ATTR
 #endif
@@ -39,7 +40,9 @@ __device__ __forceinline__ T wg_sum_r(T part, T *red, uint32_t lane, uint32_t wa
 // 16-byte pieces instead of 8 bytes per lane at a 56-byte stride (bt_dense.hpp, dense_staged_load).
 // (Blocks of 8 or fewer -- 6 in fp64, where n = 8 would spill 40 registers -- are held to 128 registers, so that two workgroups
 // share a compute unit: 1024 converged solves of n = 8, N = 128 take 105 instead of 119 us, n = 6, N = 80 in fp64 92 instead of 120.)
-template <typename T, int NCT, int V, bool STAGED = false>
+// SHARED (gbdpcg_solve_shared_*): a.S and a.Pinv are ONE pair of matrices for the whole batch; both enter the
+// registers once per workgroup, before its problem loop, and a problem costs its vectors and its iterations only.
+template <typename T, int NCT, int V, bool STAGED = false, bool SHARED = false>
 __global__ __launch_bounds__(512) GBDPCG_RES_OCC_ATTR void pcg_resident_kernel(PcgArgs<T> a)
 {
     using Dg = DenseGeom<T, NCT, V>;
@@ -61,20 +64,31 @@ __global__ __launch_bounds__(512) GBDPCG_RES_OCC_ATTR void pcg_resident_kernel(P
     const uint32_t row0 = (dc.live ? dc.kl : 0u) * n + dc.rp * V;  // first of this lane's rows
     const size_t mstride = (size_t)3 * n * n * N;
 
-    for (uint32_t prob = blockIdx.x; prob < a.batch; prob += gridDim.x) {
-        const T *S = a.S + prob * mstride;
-        const T *P = a.Pinv ? a.Pinv + prob * mstride : nullptr;
-        const size_t voff = (size_t)prob * len;
+    DenseTile<T, NCT, V> tS, tP;
+    // the tiles of the matrices S and P (P may be null: identity preconditioner) into tS, tP
+#define GBDPCG_RESIDENT_LOAD_TILES()                                                                                              \
+        if constexpr (STAGED) {                                                                                                   \
+            /* the staging buffers sit behind the mirrors and the reduction words in dynamic LDS (16-byte aligned) */             \
+            float *stage = reinterpret_cast<float *>(smem_raw) + stage_offset_floats;                                            \
+            dense_staged_load<T, NCT, V>(S, P, N, dc, wave, lane, 0u, N, reinterpret_cast<unsigned char *>(stage), tS, tP, [] {}); \
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                    \
+        } else {                                                                                                                  \
+            dense_load<T, NCT, V>(S, N, dc, tS);                                                                                  \
+            if (P) dense_load<T, NCT, V>(P, N, dc, tP);                                                                           \
+        }
+    if constexpr (SHARED) {
+        const T *S = a.S, *P = a.Pinv;
+        GBDPCG_RESIDENT_LOAD_TILES()
+    }
 
-        DenseTile<T, NCT, V> tS, tP;
-        if constexpr (STAGED) {
-            // the staging buffers sit behind the mirrors and the reduction words in dynamic LDS (16-byte aligned)
-            float *stage = reinterpret_cast<float *>(smem_raw) + stage_offset_floats;
-            dense_staged_load<T, NCT, V>(S, P, N, dc, wave, lane, 0u, N, reinterpret_cast<unsigned char *>(stage), tS, tP, [] {});
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        } else {
-            dense_load<T, NCT, V>(S, N, dc, tS);
-            if (P) dense_load<T, NCT, V>(P, N, dc, tP);
+    for (uint32_t prob = blockIdx.x; prob < a.batch; prob += gridDim.x) {
+        const T *S = a.S + (SHARED ? (size_t)0 : prob * mstride);
+        const T *P = a.Pinv ? a.Pinv + (SHARED ? (size_t)0 : prob * mstride) : nullptr;
+        const size_t voff = (size_t)prob * len;
+        (void)S;
+
+        if constexpr (!SHARED) {
+            GBDPCG_RESIDENT_LOAD_TILES()
         }
 
         T lamv[V], rv[V], pv[V], yv[V];
@@ -175,6 +189,7 @@ __global__ __launch_bounds__(512) GBDPCG_RES_OCC_ATTR void pcg_resident_kernel(P
         }
         __syncthreads();  // LDS mirrors are reused by the next problem
     }
+#undef GBDPCG_RESIDENT_LOAD_TILES
 }
 
 // Taken whenever the shape fits: the matrices are then read once per solve instead of once per iteration.  Built for the even
@@ -219,14 +234,14 @@ template <typename K> static uint32_t resident_wgs_per_cu(K kern, uint32_t threa
 // Workgroups per compute unit of pcg_resident_kernel<T, NN, RV> at this LDS size: one count per LDS size class of 8 KB (the
 // kernel's registers do not depend on the horizon), asked of the runtime once -- never while a graph is being captured
 // (query = false: an unknown class then counts as 1; gbdpcg_graph_create_* asks before it starts the capture).
-template <typename T, int NN> static uint32_t resident_per_cu(size_t lds, bool query)
+template <typename T, int NN, bool SHARED = false> static uint32_t resident_per_cu(size_t lds, bool query)
 {
     constexpr int RV = resident_rows<T, NN>();
     static uint32_t per_cu[32] = {};
     const uint32_t cls = (uint32_t)(lds >> 13) < 31u ? (uint32_t)(lds >> 13) : 31u;
     uint32_t w = __atomic_load_n(&per_cu[cls], __ATOMIC_RELAXED);
     if (!w && query) {
-        w = resident_wgs_per_cu(pcg_resident_kernel<T, NN, RV>, DenseGeom<T, NN, RV>::WAVES * 64, ((size_t)cls + 1) << 13);
+        w = resident_wgs_per_cu(pcg_resident_kernel<T, NN, RV, false, SHARED>, DenseGeom<T, NN, RV>::WAVES * 64, ((size_t)cls + 1) << 13);
         __atomic_store_n(&per_cu[cls], w, __ATOMIC_RELAXED);
     }
     return w ? w : 1u;
@@ -238,14 +253,14 @@ template <typename T> void resident_prepare(uint32_t n, uint32_t N)
     const size_t lds = ((size_t)2 * align16<T>((N + 2) * n) + 2 * align16<T>(8)) * sizeof(T);
 #define GBDPCG_X(NN)                                     \
     if constexpr (resident_built<T, NN>()) {             \
-        if (n == NN) (void)resident_per_cu<T, NN>(lds, true); \
+        if (n == NN) (void)resident_per_cu<T, NN>(lds, true), (void)resident_per_cu<T, NN, true>(lds, true); \
     }
     GBDPCG_RESIDENT_N(GBDPCG_X)
 #undef GBDPCG_X
 }
 
 template <typename T, int NN>
-static bool launch_pcg_resident_n(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err)
+static bool launch_pcg_resident_n(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err, bool shared)
 {
     constexpr int RV = resident_rows<T, NN>();
     using Dg = DenseGeom<T, NN, RV>;
@@ -260,7 +275,7 @@ static bool launch_pcg_resident_n(const DeviceInfo &dev, const PcgArgs<T> &a, hi
             uint32_t grid = (uint32_t)dev.num_cus;  // one resident workgroup owns a CU's register file
             if (grid > a.batch) grid = a.batch;
             lds = (lds + 15) / 16 * 16 + dense_stage_lds_bytes<T, 14, RV>();
-            auto kern = pcg_resident_kernel<T, 14, RV, true>;
+            auto kern = shared ? pcg_resident_kernel<T, 14, RV, true, true> : pcg_resident_kernel<T, 14, RV, true>;
             *err = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (*err != hipSuccess) return true;
             hipLaunchKernelGGL(kern, dim3(grid), dim3(Dg::WAVES * 64), lds, s, a);
@@ -268,11 +283,11 @@ static bool launch_pcg_resident_n(const DeviceInfo &dev, const PcgArgs<T> &a, hi
             return true;
         }
     }
-    auto kern = pcg_resident_kernel<T, NN, RV>;
+    auto kern = shared ? pcg_resident_kernel<T, NN, RV, false, true> : pcg_resident_kernel<T, NN, RV>;
     // the smaller blocks need few registers: several workgroups share a compute unit and fill each other's barrier waits
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const bool capturing = s && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-    const uint32_t w = resident_per_cu<T, NN>(lds, !capturing);
+    const uint32_t w = shared ? resident_per_cu<T, NN, true>(lds, !capturing) : resident_per_cu<T, NN>(lds, !capturing);
     uint64_t grid = (uint64_t)dev.num_cus * w;
     if (grid > a.batch) grid = a.batch;
     if (lds > 48 * 1024) {
@@ -285,12 +300,12 @@ static bool launch_pcg_resident_n(const DeviceInfo &dev, const PcgArgs<T> &a, hi
 }
 
 template <typename T>
-bool launch_pcg_resident(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err)
+bool launch_pcg_resident(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err, bool shared)
 {
     if (!resident_shape<T>(a.n, a.N)) return false;
 #define GBDPCG_X(NN)                                                        \
     if constexpr (resident_built<T, NN>()) {                                \
-        if (a.n == NN) return launch_pcg_resident_n<T, NN>(dev, a, s, err); \
+        if (a.n == NN) return launch_pcg_resident_n<T, NN>(dev, a, s, err, shared); \
     }
     GBDPCG_RESIDENT_N(GBDPCG_X)
 #undef GBDPCG_X
@@ -301,7 +316,7 @@ template void resident_prepare<float>(uint32_t, uint32_t);
 template void resident_prepare<double>(uint32_t, uint32_t);
 template bool resident_shape<float>(uint32_t, uint32_t);
 template bool resident_shape<double>(uint32_t, uint32_t);
-template bool launch_pcg_resident<float>(const DeviceInfo &, const PcgArgs<float> &, hipStream_t, hipError_t *);
-template bool launch_pcg_resident<double>(const DeviceInfo &, const PcgArgs<double> &, hipStream_t, hipError_t *);
+template bool launch_pcg_resident<float>(const DeviceInfo &, const PcgArgs<float> &, hipStream_t, hipError_t *, bool);
+template bool launch_pcg_resident<double>(const DeviceInfo &, const PcgArgs<double> &, hipStream_t, hipError_t *, bool);
 
 }  // namespace gbdpcg

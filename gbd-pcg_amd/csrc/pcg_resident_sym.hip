@@ -372,10 +372,15 @@ __device__ __forceinline__ void symres_dma_dword(const float *base, uint32_t off
 // the resident tiles, after the iterations: a problem that passes is written as by the plain kernel plus verdict byte 1 in
 // a.verdict_out[prob]; one that fails gets verdict byte 0 and nothing else (lambda keeps the caller's warm start for the
 // general launch that follows).  VERIFY = false is the plain kernel.
-template <int NCT, bool STAGED, bool VERIFY = false>
+// SHARED (gbdpcg_solve_shared_*): a.S and a.Pinv are ONE pair of matrices for the whole batch.  The workgroup
+// loads its four quarter-tiles once, before its problem loop, and keeps them in registers and LDS for all of its problems: a
+// problem then costs its vectors, the prologue, the iterations and the write-back -- no tile ingest, nothing to prefetch.  The
+// products are the same instructions on the same numbers: problem b gets the bits the plain kernel gives it on replicated matrices.
+template <int NCT, bool STAGED, bool VERIFY = false, bool SHARED = false>
 __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
 {
     using G = SymResGeom<NCT>;
+    static_assert(!(VERIFY && SHARED), "a shared pair is tested once, before the launch (api.hip)");
     static_assert(G::THREADS == 512, "launch bounds above assume 8 waves");
     static_assert(NCT == 14, "the reduce-scatter is written for 7 live lanes x 2 rows");
     constexpr uint32_t n = NCT, WAVES = G::WAVES;
@@ -410,6 +415,89 @@ __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
 #ifdef GBDPCG_RS_STAMPS
     uint32_t rs_round = 0xffffffffu;
 #endif
+    // The block-rows of a lane, from its number LANE_O (declares rp, grp, k0, k1, live0, live1).
+    // Which pair of block-rows a group owns is free; it is chosen so that the four groups that share an LDS pass
+    // (lanes 0-31 / 32-63 of a wave) own pairs j, j+4, j+8, j+12: their rows of a vector then start 48 banks apart
+    // (a pair is 2n = 28 floats) and the 8-byte accesses of 4 x 7 lanes tile the 64 banks instead of colliding two by
+    // two, as consecutive pairs do (bases 0, 28, 56, 20 mod 64: 13 % of an iteration's LDS-array cycles were conflicts).
+#if GBDPCG_RS_LINEAR_PAIRS
+#define GBDPCG_SYMRES_K0(GRP) (2 * (wave * G::GROUPS + (GRP)))
+#else
+#define GBDPCG_SYMRES_K0(GRP) (2 * (16 * (wave >> 1) + 4 * ((GRP) & 3u) + 2 * (wave & 1u) + ((GRP) >> 2)))
+#endif
+#define GBDPCG_SYMRES_LANE_ROWS(LANE_O)                                                                       \
+        const uint32_t rp = (LANE_O) & 7u;                                                                    \
+        const uint32_t grp = (LANE_O) >> 3;                                                                   \
+        const uint32_t k0 = GBDPCG_SYMRES_K0(grp), k1 = k0 + 1;                                               \
+        const bool live0 = rp < n / 2 && k0 < N, live1 = rp < n / 2 && k1 < N;
+
+    // Resident for the whole solve (SHARED: for the whole launch): three tiles in registers, the fourth in LDS.
+    SymResTile<NCT> s0, s1, p0;
+    // The tiles of the matrices S and P into s0, s1, p0, the wave's block of regions (ltw) and lt0.  Wave-local: no barrier.
+#define GBDPCG_SYMRES_LOAD_TILES()                                                                            \
+        if constexpr (STAGED) {                                                                               \
+            const uint32_t l8 = rp;                                                                           \
+            const bool g0 = k0 < N, g1 = k1 < N;  /* whole group alive */                                     \
+            /* all four tiles are requested at once (4 x 52 VGPRs, nothing else is live yet): one memory      \
+               round trip per problem instead of one per tile */                                              \
+            SymResStage<NCT> sa, sb, sc, sd;                                                                  \
+            symres_stage_issue<NCT>(S, k0, g0, l8, sa);                                                       \
+            symres_stage_issue<NCT>(S, k1, g1, l8, sb);                                                       \
+            symres_stage_issue<NCT>(P, k0, g0, l8, sc);                                                       \
+            symres_stage_issue<NCT>(P, k1, g1, l8, sd);                                                       \
+            __builtin_amdgcn_sched_barrier(0);                                                                \
+            GBDPCG_RS_STAMP(1)                                                                                \
+            symres_stage_park<NCT>(sa, region, l8, g0, g0 && k0 != N - 1);                                    \
+            symres_stage_pick<NCT>(region, rp, live0, s0);                                                    \
+            __builtin_amdgcn_sched_barrier(0);                                                                \
+            symres_stage_park<NCT>(sb, region, l8, g1, g1 && k1 != N - 1);                                    \
+            symres_stage_pick<NCT>(region, rp, live1, s1);                                                    \
+            __builtin_amdgcn_sched_barrier(0);                                                                \
+            symres_stage_park<NCT>(sc, region, l8, g0, g0 && k0 != N - 1);                                    \
+            symres_stage_pick<NCT>(region, rp, live0, p0);                                                    \
+            __builtin_amdgcn_sched_barrier(0);                                                                \
+            symres_stage_park<NCT>(sd, region, l8, g1, g1 && k1 != N - 1);                                    \
+            {   /* the LDS-resident tile: picked up like the others, then put back one float4 per lane and    \
+                   piece (conflict-free 16-byte reads in the products) over the wave's own staging block */   \
+                SymResTile<NCT> p1;                                                                           \
+                symres_stage_pick<NCT>(region, rp, live1, p1);                                                \
+                asm volatile("" ::: "memory");                                                                \
+                _Pragma("unroll")                                                                             \
+                for (uint32_t i = 0; i < n; ++i) ltw[i * 64] = p1.q[i];                                       \
+            }                                                                                                 \
+        } else {                                                                                              \
+            {                                                                                                 \
+                SymResTile<NCT> p1;                                                                           \
+                symres_issue<NCT>(P, k1, rp, live1, p1);                                                      \
+                symres_issue<NCT>(S, k0, rp, live0, s0);                                                      \
+                symres_issue<NCT>(S, k1, rp, live1, s1);                                                      \
+                __builtin_amdgcn_sched_barrier(0);                                                            \
+                symres_mask<NCT>(N, k1, live1, p1);                                                           \
+                _Pragma("unroll")                                                                             \
+                for (uint32_t i = 0; i < n; ++i) ltw[i * 64] = p1.q[i];                                       \
+            }                                                                                                 \
+            symres_issue<NCT>(P, k0, rp, live0, p0);  /* takes the registers the LDS-resident tile came through */ \
+            __builtin_amdgcn_sched_barrier(0);                                                                \
+            symres_mask<NCT>(N, k0, live0, s0);                                                               \
+            symres_mask<NCT>(N, k1, live1, s1);                                                               \
+            symres_mask<NCT>(N, k0, live0, p0);                                                               \
+        }                                                                                                     \
+        _Pragma("unroll")                                                                                     \
+        for (uint32_t i = 0; i < G::P0_LDS_QUADS; ++i) lt0[i * G::THREADS] = p0.q[i];
+
+    if constexpr (SHARED) {
+        // the one pair, once per workgroup: every problem below finds its tiles where a plain solve leaves them after its load
+        // (edge blocks zeroed, the Pinv k1 tile over the wave's staging block, which nothing touches again)
+#ifdef GBDPCG_RS_STAMPS
+        const uint32_t rs_round = 0;
+#endif
+        GBDPCG_SYMRES_LANE_ROWS(lane)
+        (void)grp;
+        float4_alias *ltw = reinterpret_cast<float4_alias *>(smem + wave * G::GROUPS * G::REGION) + lane;
+        const float *S = a.S, *P = a.Pinv;
+        GBDPCG_SYMRES_LOAD_TILES()
+    }
+
     for (uint32_t prob = blockIdx.x, pi = 0; prob < a.batch; prob += gridDim.x, ++pi) {
 #ifdef GBDPCG_RS_STAMPS
         ++rs_round;
@@ -418,7 +506,7 @@ __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
         if constexpr (!VERIFY) {
             if (pi == 0 || pi - takes_from >= 64) {
                 const uint32_t left = (a.batch - prob + gridDim.x - 1) / gridDim.x;
-                takes = pcg_takes_mask(a, prob, gridDim.x, left < 64 ? left : 64u, lane);
+                takes = pcg_takes_mask<SHARED>(a, prob, gridDim.x, left < 64 ? left : 64u, lane);
                 takes_from = pi;
             }
             if (!((takes >> (pi - takes_from)) & 1ull)) continue;  // this launch is not the one that owns the problem
@@ -432,18 +520,7 @@ __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
         // the problem loop these dozen values were spilled to scratch (15 VGPRs) and reloaded in the tile-load phase.
         uint32_t lane_o = tid & 63u;
         asm volatile("" : "+v"(lane_o));
-        const uint32_t rp = lane_o & 7u;
-        // Which pair of block-rows a group owns is free; it is chosen so that the four groups that share an LDS pass
-        // (lanes 0-31 / 32-63 of a wave) own pairs j, j+4, j+8, j+12: their rows of a vector then start 48 banks apart
-        // (a pair is 2n = 28 floats) and the 8-byte accesses of 4 x 7 lanes tile the 64 banks instead of colliding two by
-        // two, as consecutive pairs do (bases 0, 28, 56, 20 mod 64: 13 % of an iteration's LDS-array cycles were conflicts).
-        const uint32_t grp = lane_o >> 3;
-    #if GBDPCG_RS_LINEAR_PAIRS
-        const uint32_t k0 = 2 * (wave * G::GROUPS + grp), k1 = k0 + 1;
-    #else
-        const uint32_t k0 = 2 * (16 * (wave >> 1) + 4 * (grp & 3u) + 2 * (wave & 1u) + (grp >> 2)), k1 = k0 + 1;
-    #endif
-        const bool live0 = rp < n / 2 && k0 < N, live1 = rp < n / 2 && k1 < N;
+        GBDPCG_SYMRES_LANE_ROWS(lane_o)
         const uint32_t row0 = (live0 ? k0 * n + rp * 2 : 0u), row1 = (live1 ? k1 * n + rp * 2 : 0u);
         // x operand windows inside a padded mirror (n zeros before x_0 and after x_{N-1}); dead lanes read row 0
         const uint32_t xo0 = n + (live0 ? k0 : 0u) * n;
@@ -454,8 +531,10 @@ __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
         // the lane's own operand entries inside a mirror; dead lanes read the zero padding in front of x_0 instead, so
         // nothing downstream needs a select (v_cndmask with an SGPR mask turned out to be the costliest VALU op here)
         const uint32_t own0 = live0 ? n + row0 : 0u, own1 = live1 ? n + row1 : 0u;
-        const float *S = a.S + prob * mstride;
-        const float *P = a.Pinv + prob * mstride;
+        const float *S = a.S + (SHARED ? (size_t)0 : prob * mstride);   // (SHARED: not looked at again, the tiles are in)
+        const float *P = a.Pinv + (SHARED ? (size_t)0 : prob * mstride);
+        (void)S;
+        (void)P;
         const size_t voff = (size_t)prob * len;
         // lambda (into its own array and into the operand mirror) and gamma (into the mirror of r, where r = gamma - S lambda
         // will replace it) are requested FIRST, by LDS-DMA -- no register, no instruction of the tile phase waits for them --
@@ -470,58 +549,10 @@ __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
             }
         }
 
-        // Resident for the whole solve: three tiles in registers, the fourth in LDS.  Everything else
-        // (lambda, r, p) lives in LDS between the phases; only y crosses a barrier in registers.
-        SymResTile<NCT> s0, s1, p0;
-        if constexpr (STAGED) {
-            const uint32_t l8 = rp;
-            const bool g0 = k0 < N, g1 = k1 < N;  // whole group alive
-            // all four tiles are requested at once (4 x 52 VGPRs, nothing else is live yet): one memory
-            // round trip per problem instead of one per tile
-            SymResStage<NCT> sa, sb, sc, sd;
-            symres_stage_issue<NCT>(S, k0, g0, l8, sa);
-            symres_stage_issue<NCT>(S, k1, g1, l8, sb);
-            symres_stage_issue<NCT>(P, k0, g0, l8, sc);
-            symres_stage_issue<NCT>(P, k1, g1, l8, sd);
-            __builtin_amdgcn_sched_barrier(0);
-            GBDPCG_RS_STAMP(1)
-            symres_stage_park<NCT>(sa, region, l8, g0, g0 && k0 != N - 1);
-            symres_stage_pick<NCT>(region, rp, live0, s0);
-            __builtin_amdgcn_sched_barrier(0);
-            symres_stage_park<NCT>(sb, region, l8, g1, g1 && k1 != N - 1);
-            symres_stage_pick<NCT>(region, rp, live1, s1);
-            __builtin_amdgcn_sched_barrier(0);
-            symres_stage_park<NCT>(sc, region, l8, g0, g0 && k0 != N - 1);
-            symres_stage_pick<NCT>(region, rp, live0, p0);
-            __builtin_amdgcn_sched_barrier(0);
-            symres_stage_park<NCT>(sd, region, l8, g1, g1 && k1 != N - 1);
-            {   // the LDS-resident tile: picked up like the others, then put back one float4 per lane and
-                // piece (conflict-free 16-byte reads in the products) over the wave's own staging block
-                SymResTile<NCT> p1;
-                symres_stage_pick<NCT>(region, rp, live1, p1);
-                asm volatile("" ::: "memory");
-#pragma unroll
-                for (uint32_t i = 0; i < n; ++i) ltw[i * 64] = p1.q[i];
-            }
-        } else {
-            {
-                SymResTile<NCT> p1;
-                symres_issue<NCT>(P, k1, rp, live1, p1);
-                symres_issue<NCT>(S, k0, rp, live0, s0);
-                symres_issue<NCT>(S, k1, rp, live1, s1);
-                __builtin_amdgcn_sched_barrier(0);
-                symres_mask<NCT>(N, k1, live1, p1);
-#pragma unroll
-                for (uint32_t i = 0; i < n; ++i) ltw[i * 64] = p1.q[i];
-            }
-            symres_issue<NCT>(P, k0, rp, live0, p0);  // takes the registers the LDS-resident tile came through
-            __builtin_amdgcn_sched_barrier(0);
-            symres_mask<NCT>(N, k0, live0, s0);
-            symres_mask<NCT>(N, k1, live1, s1);
-            symres_mask<NCT>(N, k0, live0, p0);
+        // Everything but the tiles (lambda, r, p) lives in LDS between the phases; only y crosses a barrier in registers.
+        if constexpr (!SHARED) {
+            GBDPCG_SYMRES_LOAD_TILES()
         }
-#pragma unroll
-        for (uint32_t i = 0; i < G::P0_LDS_QUADS; ++i) lt0[i * G::THREADS] = p0.q[i];
         GBDPCG_RS_STAMP(2)
 
         for (uint32_t i = tid; i < n; i += G::THREADS) {
@@ -609,7 +640,8 @@ __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
         // prefetch schedule for the next problem of this workgroup: two lines per thread and iteration
         const uint32_t nprob = prob + gridDim.x;
         constexpr uint32_t pf_steps = (2 * n * n * 4 + 63) / 64 + 1;  // 64-byte steps per [D|R] row (symres_touch)
-        const uint32_t pf_per_matrix = GBDPCG_RS_PREFETCH && nprob < a.batch ? (N * pf_steps + G::THREADS - 1) / G::THREADS : 0u;
+        // (SHARED: the next problem's matrices are the ones already here)
+        const uint32_t pf_per_matrix = !SHARED && GBDPCG_RS_PREFETCH && nprob < a.batch ? (N * pf_steps + G::THREADS - 1) / G::THREADS : 0u;
         uint32_t pf = 0;
 #define GBDPCG_SYMRES_PREFETCH()                                                                              \
         if (pf < pf_per_matrix) {                                                                             \
@@ -716,6 +748,9 @@ __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
         __syncthreads();  // LDS (tile, vectors, verdict word) is reused by the next problem
         GBDPCG_RS_STAMP(6)
     }
+#undef GBDPCG_SYMRES_LOAD_TILES
+#undef GBDPCG_SYMRES_LANE_ROWS
+#undef GBDPCG_SYMRES_K0
     // The prefetch loads are invisible to the compiler's counters; s_endpgm drains the wave's memory counters in
     // hardware, and this makes it explicit: none of them can still be in flight (towards this workgroup's LDS dump
     // area) when the workgroup's LDS is handed to another one.
@@ -754,7 +789,8 @@ bool resident_sym_verifies(const DeviceInfo &dev, uint32_t n, uint32_t N, const 
 
 // verify: the verifying kernel (every problem, a.verdict_out written); the caller has checked resident_sym_verifies.
 template <typename T>
-static bool launch_pcg_resident_sym_impl(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err, bool verify)
+static bool launch_pcg_resident_sym_impl(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err, bool verify,
+                                         bool shared = false)
 {
     if constexpr (sizeof(T) == 4) {
         if (!a.symmetric || !a.Pinv || !resident_sym_shape<T>(a.n, a.N)) return false;
@@ -763,8 +799,10 @@ static bool launch_pcg_resident_sym_impl(const DeviceInfo &dev, const PcgArgs<T>
         if (lds > dev.lds_per_wg_max) return false;
         const bool staged = resident_sym_staged(a.S, a.Pinv);
         if (verify && (!staged || !a.verdict_out)) return false;
+        if (verify && shared) return false;   // a shared pair has ONE verdict, found before the launch
         auto kern = verify ? pcg_resident_sym_kernel<14, true, true>
                            : staged ? pcg_resident_sym_kernel<14, true, false> : pcg_resident_sym_kernel<14, false, false>;
+        if (shared) kern = staged ? pcg_resident_sym_kernel<14, true, false, true> : pcg_resident_sym_kernel<14, false, false, true>;
         // on every launch, like the other launchers: HIP keeps the attribute per device, and a process may hold
         // handles on several devices (one host thread each)
         *err = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -780,9 +818,9 @@ static bool launch_pcg_resident_sym_impl(const DeviceInfo &dev, const PcgArgs<T>
 }
 
 template <typename T>
-bool launch_pcg_resident_sym(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err)
+bool launch_pcg_resident_sym(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err, bool shared)
 {
-    return launch_pcg_resident_sym_impl<T>(dev, a, s, err, false);
+    return launch_pcg_resident_sym_impl<T>(dev, a, s, err, false, shared);
 }
 
 template <typename T>
@@ -793,8 +831,8 @@ bool launch_pcg_resident_sym_verify(const DeviceInfo &dev, const PcgArgs<T> &a, 
 
 template bool resident_sym_shape<float>(uint32_t, uint32_t);
 template bool resident_sym_shape<double>(uint32_t, uint32_t);
-template bool launch_pcg_resident_sym<float>(const DeviceInfo &, const PcgArgs<float> &, hipStream_t, hipError_t *);
-template bool launch_pcg_resident_sym<double>(const DeviceInfo &, const PcgArgs<double> &, hipStream_t, hipError_t *);
+template bool launch_pcg_resident_sym<float>(const DeviceInfo &, const PcgArgs<float> &, hipStream_t, hipError_t *, bool);
+template bool launch_pcg_resident_sym<double>(const DeviceInfo &, const PcgArgs<double> &, hipStream_t, hipError_t *, bool);
 template bool resident_sym_verifies<float>(const DeviceInfo &, uint32_t, uint32_t, const float *, const float *);
 template bool resident_sym_verifies<double>(const DeviceInfo &, uint32_t, uint32_t, const double *, const double *);
 template bool launch_pcg_resident_sym_verify<float>(const DeviceInfo &, const PcgArgs<float> &, hipStream_t, hipError_t *);

@@ -96,11 +96,17 @@ template <typename T, int NCT, int V, int WAVES, bool SYM> struct StreamSolver {
     // Solve problem `prob` of `a`.  xa, xb, yc, lam (and zc when SYM): this workgroup's vectors per FusedCarve -- LDS, or
     // device memory touched by this workgroup only (__syncthreads() orders a workgroup's global accesses on its CU);
     // red0: 2 * WAVES partials in LDS.  All threads of the workgroup call it together; it ends on a barrier.
+    // SHARED: one pair of matrices for every problem (zero problem stride: it stays in L2 / Infinity Cache for the whole launch).
+    template <bool SHARED = false>
     __device__ __forceinline__ void solve(const PcgArgs<T> &a, uint32_t prob, T *xa, T *xb, T *yc, T *lam, T *red0, T *zc)
     {
         const uint32_t N = a.N, len = n * N;
         T *red1 = red0 + WAVES;
-        const size_t mstride = (size_t)3 * n * n * N;
+        size_t mstride = (size_t)3 * n * n * N;
+        if constexpr (SHARED) {   // zero, but not a constant the compiler may build on: the code, and with it the registers, of the per-problem kernel
+            mstride = 0;
+            asm volatile("" : "+s"(mstride));
+        }
         const T *S = a.S + prob * mstride;
         const T *P = a.Pinv ? a.Pinv + prob * mstride : nullptr;
         const T *gamma = a.gamma + (size_t)prob * len;
@@ -235,12 +241,12 @@ template <typename T> __host__ __device__ inline size_t rescue_vec_elems(uint32_
 // block size, one element per lane and load (any alignment), vectors in `vec` (rescue_vec_elems elements of device memory
 // that nobody else touches), partials in `red` (2 * WAVES elements of LDS).  Slow -- one CU's share of the fabric -- and
 // only ever reached when a launch could not get its workgroups onto the device together.
-template <typename T, int WAVES>
+template <typename T, int WAVES, bool SHARED = false>
 __device__ __forceinline__ void stream_rescue(const PcgArgs<T> &a, uint32_t prob, T *vec, T *red)
 {
     const FusedCarve<T> cv(a.n, a.N, 1);
     StreamSolver<T, 0, 1, WAVES, false> sv(a.n, threadIdx.x);
-    sv.solve(a, prob, vec + cv.xa, vec + cv.xb, vec + cv.yc, vec + cv.lam, red, nullptr);
+    sv.template solve<SHARED>(a, prob, vec + cv.xa, vec + cv.xb, vec + cv.yc, vec + cv.lam, red, nullptr);
 }
 
 }  // namespace gbdpcg

@@ -807,7 +807,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sc
 }
 
 // z = -G^-1 (g + C' lambda): x_k = -Q_k^-1 (q_k + lambda_k - A_k' lambda_{k+1}),  u_k = -R_k^-1 (r_k - B_k' lambda_{k+1}).
-template <typename T>
+// SHARED (here and in the three kernels below; gbdpcg_recover_primal_shared_*, gbdpcg_form_gamma_shared_*): Ginv and C are ONE
+// problem's blocks, read with a zero problem stride by every problem of the batch -- the same fma chains, the same bits.
+template <typename T, bool SHARED = false>
 __global__ __launch_bounds__(256) void schur_recover_kernel(uint32_t nx, uint32_t nu, uint32_t N, uint64_t rows,
                                                            const T *__restrict__ Ginv, const T *__restrict__ C,
                                                            const T *__restrict__ g, const T *__restrict__ lambda, T *__restrict__ z)
@@ -824,7 +826,8 @@ __global__ __launch_bounds__(256) void schur_recover_kernel(uint32_t nx, uint32_
 
     T *Qi = reinterpret_cast<T *>(smem_raw) + (size_t)wave * recover_wave_elems(nx, nu);
     T *A = Qi + nn, *Ri = A + nn, *B = Ri + uu, *ln = B + xu, *tx = ln + nx, *tu = tx + 2 * nx;
-    const T *Gi = Ginv + prob * d.szG + (size_t)k * d.sg, *Ck = C + prob * d.szC + (size_t)k * d.sc;
+    const uint64_t mprob = SHARED ? 0 : prob;   // the problem whose matrices this row reads
+    const T *Gi = Ginv + mprob * d.szG + (size_t)k * d.sg, *Ck = C + mprob * d.szC + (size_t)k * d.sc;
     const T *gk = g + prob * d.szg + (size_t)k * d.sv;
     T *zk = z + prob * d.szg + (size_t)k * d.sv;
 
@@ -876,7 +879,7 @@ __global__ __launch_bounds__(256) void schur_recover_kernel(uint32_t nx, uint32_
 //   * every load of a row is requested before the first fma (53 registers of operands per lane), five or six waves per SIMD keep
 //     ~200 KB per compute unit in flight.
 // Same sums in the same order as the kernel above (q ascending, one fma chain per output entry): bit-identical results.
-template <typename T, int NX, int NU>
+template <typename T, int NX, int NU, bool SHARED = false>
 __global__ __launch_bounds__(256) void schur_recover_quad_kernel(uint32_t N, uint64_t rows, const T *__restrict__ Ginv,
                                                                 const T *__restrict__ C, const T *__restrict__ g,
                                                                 const T *__restrict__ lambda, T *__restrict__ z)
@@ -892,7 +895,8 @@ __global__ __launch_bounds__(256) void schur_recover_quad_kernel(uint32_t N, uin
     const bool has_next = live && k + 1 < N;
     const bool lx = live && l < NX, lu = has_next && l < NU;
     const uint32_t cx = l < NX ? l : 0u, cu = l < NU ? l : 0u;   // clamped: idle lanes read what a live lane reads
-    const T *Gi = Ginv + prob * d.szG + (size_t)k * d.sg, *Ck = C + prob * d.szC + (size_t)k * d.sc;
+    const uint64_t mprob = SHARED ? 0 : prob;
+    const T *Gi = Ginv + mprob * d.szG + (size_t)k * d.sg, *Ck = C + mprob * d.szC + (size_t)k * d.sc;
     const T *gk = g + prob * d.szg + (size_t)k * d.sv;
     const T *lk = lambda + (prob * N + k) * NX;
 
@@ -951,7 +955,7 @@ __host__ __device__ inline uint32_t gamma_wave_elems(uint32_t nx, uint32_t nu)
 }
 
 // Any block size: one wavefront per row (problem, k), blocks staged in LDS.
-template <typename T>
+template <typename T, bool SHARED = false>
 __global__ __launch_bounds__(256) void schur_gamma_kernel(uint32_t nx, uint32_t nu, uint32_t N, uint64_t rows,
                                                          const T *__restrict__ Ginv, const T *__restrict__ C,
                                                          const T *__restrict__ g, const T *__restrict__ c, T *__restrict__ gamma)
@@ -969,13 +973,14 @@ __global__ __launch_bounds__(256) void schur_gamma_kernel(uint32_t nx, uint32_t 
     T *Qc = reinterpret_cast<T *>(smem_raw) + (size_t)wave * gamma_wave_elems(nx, nu);
     T *Qp = Qc + nn, *Ap = Qp + nn, *Rp = Ap + nn, *Bp = Rp + uu;
     T *qc = Bp + xu, *qp = qc + nx, *wp = qp + nx, *rp = wp + 2 * nx, *vp = rp + nu;
-    const T *Gp = Ginv + prob * d.szG, *gp = g + prob * d.szg;
+    const uint64_t mprob = SHARED ? 0 : prob;
+    const T *Gp = Ginv + mprob * d.szG, *gp = g + prob * d.szg;
 
     for (uint32_t i = lane; i < nn; i += 64) Qc[i] = Gp[(size_t)k * d.sg + i];
     for (uint32_t i = lane; i < nx; i += 64) qc[i] = gp[(size_t)k * d.sv + i];
     if (has_prev) {
         const uint32_t j = k - 1;
-        const T *Gj = Gp + (size_t)j * d.sg, *Cj = C + prob * d.szC + (size_t)j * d.sc, *gj = gp + (size_t)j * d.sv;
+        const T *Gj = Gp + (size_t)j * d.sg, *Cj = C + mprob * d.szC + (size_t)j * d.sc, *gj = gp + (size_t)j * d.sv;
         for (uint32_t i = lane; i < nn; i += 64) {
             Qp[i] = Gj[i];
             Ap[i] = Cj[i];
@@ -1090,7 +1095,7 @@ __device__ __forceinline__ void gamma_knot_products(const T (&qi)[NX], const T (
 // no DPP operand is read under a partial exec mask that way).
 // 1024 x 128 rows at nx 14, nu 7: 87 us in fp32 (307 MB, 3.5 TB/s; 104 registers, four waves per SIMD), 135 us in fp64; 31 us at
 // 12 / 4 (6.5 TB/s) -- profiles/r05_resolve.txt.
-template <typename T, int NX, int NU>
+template <typename T, int NX, int NU, bool SHARED = false>
 __global__ __launch_bounds__(256) void schur_gamma_quad_kernel(uint32_t N, uint64_t rows, const T *__restrict__ Ginv,
                                                               const T *__restrict__ C, const T *__restrict__ g,
                                                               const T *__restrict__ c, T *__restrict__ gamma)
@@ -1107,7 +1112,8 @@ __global__ __launch_bounds__(256) void schur_gamma_quad_kernel(uint32_t N, uint6
     const bool first = has_prev && qd == 0;                      // no quarter before this one holds t_{k-1}
     const uint32_t cx = l < NX ? l : 0u, cu = l < NU ? l : 0u;   // clamped: idle lanes read what a live lane reads
     const uint32_t j = first ? k - 1 : k;
-    const T *Gp = Ginv + prob * d.szG, *Cp = C + prob * d.szC, *gp = g + prob * d.szg;
+    const uint64_t mprob = SHARED ? 0 : prob;
+    const T *Gp = Ginv + mprob * d.szG, *Cp = C + mprob * d.szC, *gp = g + prob * d.szg;
 
     T qi[NX], a[NX], ri[NU], b[NU], qv, rv;       // this row's knot
     T qib[NX], ab[NX], rib[NU], bb[NU], qvb, rvb;  // the knot before it (first quarter only)
@@ -1194,7 +1200,7 @@ hipError_t launch_form_schur(const DeviceInfo &dev, uint32_t nx, uint32_t nu, ui
 
 template <typename T>
 hipError_t launch_recover_primal(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *Ginv,
-                                 const T *C, const T *g, const T *lambda, T *z, hipStream_t s)
+                                 const T *C, const T *g, const T *lambda, T *z, hipStream_t s, bool shared)
 {
     const uint64_t rows = (uint64_t)batch * N;
     // GBDPCG_SCHUR_GENERAL=1: the any-size kernel also where the four-rows-per-wave form exists (A/B runs, tests)
@@ -1204,7 +1210,10 @@ hipError_t launch_recover_primal(const DeviceInfo &dev, uint32_t nx, uint32_t nu
         if (grid > 0x7fffffffull) return hipErrorInvalidValue;
 #define GBDPCG_X(NX, NU)                                                                                                              \
     if (nx == NX && nu == NU) {                                                                                                       \
-        hipLaunchKernelGGL((schur_recover_quad_kernel<T, NX, NU>), dim3((uint32_t)grid), dim3(256), 0, s, N, rows, Ginv, C, g, lambda, z); \
+        if (shared)                                                                                                                   \
+            hipLaunchKernelGGL((schur_recover_quad_kernel<T, NX, NU, true>), dim3((uint32_t)grid), dim3(256), 0, s, N, rows, Ginv, C, g, lambda, z); \
+        else                                                                                                                          \
+            hipLaunchKernelGGL((schur_recover_quad_kernel<T, NX, NU>), dim3((uint32_t)grid), dim3(256), 0, s, N, rows, Ginv, C, g, lambda, z); \
         return hipGetLastError();                                                                                                     \
     }
         GBDPCG_QUAD_SHAPES(GBDPCG_X)
@@ -1216,7 +1225,7 @@ hipError_t launch_recover_primal(const DeviceInfo &dev, uint32_t nx, uint32_t nu
     const uint64_t grid = (rows + waves - 1) / waves;
     if (grid > 0x7fffffffull) return hipErrorInvalidValue;
     const size_t lds = waves * wave_bytes;
-    auto kern = schur_recover_kernel<T>;
+    auto kern = shared ? schur_recover_kernel<T, true> : schur_recover_kernel<T>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -1227,7 +1236,7 @@ hipError_t launch_recover_primal(const DeviceInfo &dev, uint32_t nx, uint32_t nu
 
 template <typename T>
 hipError_t launch_form_gamma(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *Ginv, const T *C,
-                             const T *g, const T *c, T *gamma, hipStream_t s)
+                             const T *g, const T *c, T *gamma, hipStream_t s, bool shared)
 {
     const uint64_t rows = (uint64_t)batch * N;
     // GBDPCG_SCHUR_GENERAL=1: the any-size kernel also where the four-rows-per-wave form exists (A/B runs, tests)
@@ -1237,7 +1246,10 @@ hipError_t launch_form_gamma(const DeviceInfo &dev, uint32_t nx, uint32_t nu, ui
         if (grid > 0x7fffffffull) return hipErrorInvalidValue;
 #define GBDPCG_X(NX, NU)                                                                                                       \
     if (nx == NX && nu == NU) {                                                                                                \
-        hipLaunchKernelGGL((schur_gamma_quad_kernel<T, NX, NU>), dim3((uint32_t)grid), dim3(256), 0, s, N, rows, Ginv, C, g, c, gamma); \
+        if (shared)                                                                                                            \
+            hipLaunchKernelGGL((schur_gamma_quad_kernel<T, NX, NU, true>), dim3((uint32_t)grid), dim3(256), 0, s, N, rows, Ginv, C, g, c, gamma); \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((schur_gamma_quad_kernel<T, NX, NU>), dim3((uint32_t)grid), dim3(256), 0, s, N, rows, Ginv, C, g, c, gamma); \
         return hipGetLastError();                                                                                              \
     }
         GBDPCG_QUAD_SHAPES(GBDPCG_X)
@@ -1249,7 +1261,7 @@ hipError_t launch_form_gamma(const DeviceInfo &dev, uint32_t nx, uint32_t nu, ui
     const uint64_t grid = (rows + waves - 1) / waves;
     if (grid > 0x7fffffffull) return hipErrorInvalidValue;
     const size_t lds = waves * wave_bytes;
-    auto kern = schur_gamma_kernel<T>;
+    auto kern = shared ? schur_gamma_kernel<T, true> : schur_gamma_kernel<T>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -1268,13 +1280,13 @@ template hipError_t launch_form_schur<float>(const DeviceInfo &, uint32_t, uint3
 template hipError_t launch_form_schur<double>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const double *, const double *,
                                               const double *, const double *, double *, double *, double *, hipStream_t);
 template hipError_t launch_recover_primal<float>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const float *,
-                                                 const float *, const float *, const float *, float *, hipStream_t);
+                                                 const float *, const float *, const float *, float *, hipStream_t, bool);
 template hipError_t launch_recover_primal<double>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const double *,
-                                                  const double *, const double *, const double *, double *, hipStream_t);
+                                                  const double *, const double *, const double *, double *, hipStream_t, bool);
 template hipError_t launch_form_gamma<float>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const float *, const float *,
-                                             const float *, const float *, float *, hipStream_t);
+                                             const float *, const float *, float *, hipStream_t, bool);
 template hipError_t launch_form_gamma<double>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const double *,
-                                              const double *, const double *, const double *, double *, hipStream_t);
+                                              const double *, const double *, const double *, double *, hipStream_t, bool);
 template bool schur_shape_ok<float>(const DeviceInfo &, uint32_t, uint32_t);
 template bool schur_shape_ok<double>(const DeviceInfo &, uint32_t, uint32_t);
 

@@ -394,6 +394,79 @@ gbdpcg_status gbdpcg_graph_create_kkt_resolve_f64(gbdpcg_handle_t h, uint32_t nx
                                                   double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
                                                   uint8_t *d_max_iter_exit, double *d_z, gbdpcg_graph_t *out);
 
+/* Shared-matrix batches: ONE S and Phi^-1 (and ONE G^-1 and C) for `batch` right-hand sides -- one plant model against many
+ * measured states or references: Monte-Carlo validation of a linear MPC, scenario MPC around one trajectory, a fleet of
+ * identical robots.  Each entry point is the twin of the one named in it and takes the same arguments in the same order; the
+ * difference is what the matrix pointers hold:
+ *     gbdpcg_solve_shared_*, gbdpcg_graph_create_solve_shared_*              d_S, d_Pinv: 3 n^2 N elements each (d_Pinv NULL: identity)
+ *     gbdpcg_form_gamma_shared_*, gbdpcg_recover_primal_shared_*             d_Ginv, d_C: one problem's blocks
+ *     gbdpcg_kkt_resolve_shared_*, gbdpcg_graph_create_kkt_resolve_shared_*  d_Ginv, d_C, d_S, d_Pinv: one problem's each
+ * Every vector (g, c, gamma, lambda, r, p, z) and d_iters / d_max_iter_exit stay per problem, problem-major, as in the twins.
+ * No formation entry point is needed: the single matrices are what gbdpcg_form_schur_*, gbdpcg_form_pinv_* or
+ * gbdpcg_kkt_step_* write with batch = 1.
+ *  - Problem b gets exactly the bits its twin writes for problem b of a batch whose matrices are `batch` copies of the single
+ *    ones, on the same handle in the same symmetric mode with the path set to GBDPCG_PATH_FUSED; batch = 1 is the twin.
+ *  - A shared solve always runs on the fused family (one workgroup or one cluster of workgroups per problem), by the rules the
+ *    twin applies to that n, N, batch and mode, whatever gbdpcg_set_path says.  A shape that does not fit one workgroup (36 x 256
+ *    in fp64, say) gives GBDPCG_ERR_UNSUPPORTED and nothing is written: the persistent and split forms have no shared
+ *    counterpart.  Where a kernel keeps a problem's matrices on chip (stateSize 14 in fp32, and the small blocks) a workgroup
+ *    loads the one pair once and keeps it for all of its problems; elsewhere the pair is re-read from the caches.
+ *  - Symmetric mode 2 tests the ONE pair once per call, on the device, and every problem follows that verdict; modes 1 and 0
+ *    are as in gbdpcg_set_symmetric.
+ *  - Exactly one problem's worth is read behind each single pointer: nothing past element 3 n^2 N of d_S / d_Pinv, nothing
+ *    past one problem's extent of d_Ginv / d_C.
+ *  - Everything else is as for the twins: asynchronous on `stream`, capturable, no allocation under capture (what
+ *    gbdpcg_reserve sizes for (n, N, batch) suffices; the graph constructors reserve for themselves), warm start from
+ *    d_lambda, d_r / d_p / d_max_iter_exit may be NULL, and the same error codes. */
+gbdpcg_status gbdpcg_solve_shared_f32(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batch, const float *d_S,
+                                      const float *d_Pinv, const float *d_gamma, float *d_lambda, float *d_r, float *d_p,
+                                      float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, void *stream);
+gbdpcg_status gbdpcg_solve_shared_f64(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batch, const double *d_S,
+                                      const double *d_Pinv, const double *d_gamma, double *d_lambda, double *d_r, double *d_p,
+                                      double tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, void *stream);
+gbdpcg_status gbdpcg_graph_create_solve_shared_f32(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batch,
+                                                   const float *d_S, const float *d_Pinv, const float *d_gamma, float *d_lambda,
+                                                   float *d_r, float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                                   uint8_t *d_max_iter_exit, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_solve_shared_f64(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batch,
+                                                   const double *d_S, const double *d_Pinv, const double *d_gamma, double *d_lambda,
+                                                   double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                   uint8_t *d_max_iter_exit, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_form_gamma_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                           const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                           float *d_gamma, void *stream);
+gbdpcg_status gbdpcg_form_gamma_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                           const double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                           double *d_gamma, void *stream);
+gbdpcg_status gbdpcg_recover_primal_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                               const float *d_Ginv, const float *d_C, const float *d_g, const float *d_lambda,
+                                               float *d_z, void *stream);
+gbdpcg_status gbdpcg_recover_primal_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                               const double *d_Ginv, const double *d_C, const double *d_g, const double *d_lambda,
+                                               double *d_z, void *stream);
+gbdpcg_status gbdpcg_kkt_resolve_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                            const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                            const float *d_S, const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r,
+                                            float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                            uint8_t *d_max_iter_exit, float *d_z, void *stream);
+gbdpcg_status gbdpcg_kkt_resolve_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                            const double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                            const double *d_S, const double *d_Pinv, double *d_gamma, double *d_lambda, double *d_r,
+                                            double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                            uint8_t *d_max_iter_exit, double *d_z, void *stream);
+gbdpcg_status gbdpcg_graph_create_kkt_resolve_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N,
+                                                         uint32_t batch, const float *d_Ginv, const float *d_C, const float *d_g,
+                                                         const float *d_c, const float *d_S, const float *d_Pinv, float *d_gamma,
+                                                         float *d_lambda, float *d_r, float *d_p, float tol, uint32_t max_iter,
+                                                         uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_z,
+                                                         gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_kkt_resolve_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N,
+                                                         uint32_t batch, const double *d_Ginv, const double *d_C, const double *d_g,
+                                                         const double *d_c, const double *d_S, const double *d_Pinv, double *d_gamma,
+                                                         double *d_lambda, double *d_r, double *d_p, double tol, uint32_t max_iter,
+                                                         uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z,
+                                                         gbdpcg_graph_t *out);
+
 /* CSR ingestion (f3): repacks a host CSR matrix (csr_t<T>, include/types.cuh:7-15) whose
  * sparsity lies inside the block-tridiagonal pattern into the [L|D|R] layout (host arrays).
  * Entries outside the pattern give GBDPCG_ERR_INVALID.  Implements what the stub overload

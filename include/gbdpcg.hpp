@@ -335,6 +335,67 @@ void kktResolve(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoints, u
     }
 }
 
+// ---- shared-matrix batches (gbdpcg.h): ONE S, Phi^-1, G^-1 and C -- one problem's worth behind each matrix pointer, as the
+// batch-1 forms of formSchur / kktStep write them -- for `batch` sets of vectors.  Same arguments as the per-problem calls.
+template <typename T>
+void solveShared(uint32_t stateSize, uint32_t knotPoints, uint32_t batch, const T *d_S, const T *d_Pinv, const T *d_gamma, T *d_lambda,
+                 uint32_t *d_iters, uint8_t *d_max_iter_exit, struct pcg_config<T> *config, hipStream_t stream = nullptr)
+{
+    static_assert(gbdpcg_detail::is_f32<T> || gbdpcg_detail::is_f64<T>, "solveShared<T>: T is float or double");
+    gbdpcg_handle_t h = gbdpcg_detail::handle();
+    if constexpr (gbdpcg_detail::is_f32<T>) {
+        GBDPCG_CHECK(gbdpcg_solve_shared_f32(h, stateSize, knotPoints, batch, d_S, d_Pinv, d_gamma, d_lambda, nullptr, nullptr,
+                                             config->pcg_exit_tol, config->pcg_max_iter, d_iters, d_max_iter_exit, stream), "solveShared");
+    } else {
+        GBDPCG_CHECK(gbdpcg_solve_shared_f64(h, stateSize, knotPoints, batch, d_S, d_Pinv, d_gamma, d_lambda, nullptr, nullptr,
+                                             config->pcg_exit_tol, config->pcg_max_iter, d_iters, d_max_iter_exit, stream), "solveShared");
+    }
+}
+
+template <typename T>
+void formGammaShared(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoints, uint32_t batch, const T *d_Ginv, const T *d_C,
+                     const T *d_g, const T *d_c, T *d_gamma, hipStream_t stream = nullptr)
+{
+    static_assert(gbdpcg_detail::is_f32<T> || gbdpcg_detail::is_f64<T>, "formGammaShared<T>: T is float or double");
+    gbdpcg_handle_t h = gbdpcg_detail::handle();
+    if constexpr (gbdpcg_detail::is_f32<T>) {
+        GBDPCG_CHECK(gbdpcg_form_gamma_shared_f32(h, stateSize, controlSize, knotPoints, batch, d_Ginv, d_C, d_g, d_c, d_gamma, stream), "formGammaShared");
+    } else {
+        GBDPCG_CHECK(gbdpcg_form_gamma_shared_f64(h, stateSize, controlSize, knotPoints, batch, d_Ginv, d_C, d_g, d_c, d_gamma, stream), "formGammaShared");
+    }
+}
+
+template <typename T>
+void recoverPrimalShared(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoints, uint32_t batch, const T *d_Ginv, const T *d_C,
+                         const T *d_g, const T *d_lambda, T *d_z, hipStream_t stream = nullptr)
+{
+    static_assert(gbdpcg_detail::is_f32<T> || gbdpcg_detail::is_f64<T>, "recoverPrimalShared<T>: T is float or double");
+    gbdpcg_handle_t h = gbdpcg_detail::handle();
+    if constexpr (gbdpcg_detail::is_f32<T>) {
+        GBDPCG_CHECK(gbdpcg_recover_primal_shared_f32(h, stateSize, controlSize, knotPoints, batch, d_Ginv, d_C, d_g, d_lambda, d_z, stream), "recoverPrimalShared");
+    } else {
+        GBDPCG_CHECK(gbdpcg_recover_primal_shared_f64(h, stateSize, controlSize, knotPoints, batch, d_Ginv, d_C, d_g, d_lambda, d_z, stream), "recoverPrimalShared");
+    }
+}
+
+template <typename T>
+void kktResolveShared(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoints, uint32_t batch, const T *d_Ginv, const T *d_C,
+                      const T *d_g, const T *d_c, const T *d_S, const T *d_Pinv, T *d_gamma, T *d_lambda, T *d_z, uint32_t *d_iters,
+                      uint8_t *d_max_iter_exit, struct pcg_config<T> *config, hipStream_t stream = nullptr)
+{
+    static_assert(gbdpcg_detail::is_f32<T> || gbdpcg_detail::is_f64<T>, "kktResolveShared<T>: T is float or double");
+    gbdpcg_handle_t h = gbdpcg_detail::handle();
+    if constexpr (gbdpcg_detail::is_f32<T>) {
+        GBDPCG_CHECK(gbdpcg_kkt_resolve_shared_f32(h, stateSize, controlSize, knotPoints, batch, d_Ginv, d_C, d_g, d_c, d_S, d_Pinv, d_gamma,
+                                                   d_lambda, nullptr, nullptr, config->pcg_exit_tol, config->pcg_max_iter, d_iters,
+                                                   d_max_iter_exit, d_z, stream), "kktResolveShared");
+    } else {
+        GBDPCG_CHECK(gbdpcg_kkt_resolve_shared_f64(h, stateSize, controlSize, knotPoints, batch, d_Ginv, d_C, d_g, d_c, d_S, d_Pinv, d_gamma,
+                                                   d_lambda, nullptr, nullptr, config->pcg_exit_tol, config->pcg_max_iter, d_iters,
+                                                   d_max_iter_exit, d_z, stream), "kktResolveShared");
+    }
+}
+
 // ---- the README's spelling (README.md:42): int pcg_solve<T>(cbtd_t *h_S, ...) ---------------------
 template <typename T>
 int pcg_solve(cbtd_t<T> *h_S, T *h_gamma, T *h_lambda, unsigned stateSize, unsigned knotPoints,
