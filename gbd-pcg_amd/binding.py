@@ -39,6 +39,7 @@ SYMBOLS = [
     "gbdpcg_form_gamma_shared_f32", "gbdpcg_form_gamma_shared_f64", "gbdpcg_recover_primal_shared_f32", "gbdpcg_recover_primal_shared_f64",
     "gbdpcg_kkt_resolve_shared_f32", "gbdpcg_kkt_resolve_shared_f64",
     "gbdpcg_graph_create_kkt_resolve_shared_f32", "gbdpcg_graph_create_kkt_resolve_shared_f64",
+    "gbdpcg_kkt_residual_f32", "gbdpcg_kkt_residual_f64", "gbdpcg_kkt_residual_shared_f32", "gbdpcg_kkt_residual_shared_f64",
     "gbdpcg_csr_to_bt_f32", "gbdpcg_csr_to_bt_f64", "gbdpcg_version",
 ]
 
@@ -60,6 +61,9 @@ def _resolve_argtypes(lib):
         getattr(lib, f"gbdpcg_recover_primal_shared_{suf}").argtypes = head + [vp, vp]      # (lambda in the place of c, z, stream)
         getattr(lib, f"gbdpcg_kkt_resolve_shared_{suf}").argtypes = head + solve + [vp]
         getattr(lib, f"gbdpcg_graph_create_kkt_resolve_shared_{suf}").argtypes = head + solve + [ctypes.POINTER(vp)]
+        # the residual norms: h, nx, nu, N, batch, G, C, g, c | z, lambda, res, stream
+        getattr(lib, f"gbdpcg_kkt_residual_{suf}").argtypes = head + [vp, vp, vp, vp]
+        getattr(lib, f"gbdpcg_kkt_residual_shared_{suf}").argtypes = head + [vp, vp, vp, vp]
 
 _lib = None
 
@@ -415,6 +419,25 @@ class Solver:
         self._check(getattr(self.lib, f"gbdpcg_graph_create_kkt_resolve_shared_{suf}")(*args, ctypes.byref(gr)),
                     "graph_create_kkt_resolve_shared")
         return Graph(self, gr, keep=(Ginv, C, g, c, S, Pinv, gamma, lam, r, p, iters, max_iter_exit, z))
+
+    def _kkt_residual(self, name, nx, nu, N, batch, G, C, g, c, z, lam, res, stream):
+        import torch
+        suf, _ = _suffix(G)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=G.dtype, device=G.device)
+        assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == G.dtype
+        fn = getattr(self.lib, f"gbdpcg_{name}_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(G), _p(C), _p(g), _p(c), _p(z), _p(lam), _p(res), self._stream(stream)), name)
+        return res.view(batch, 2)
+
+    def kkt_residual(self, nx, nu, N, batch, G, C, g, c, z, lam, res=None, stream=None):
+        """gbdpcg_kkt_residual_*: [batch, 2] tensor of (||G z + g + C' lambda||_inf, ||C z - c||_inf) per problem.  G holds the
+        Hessians (not G^-1); z has the layout of g."""
+        return self._kkt_residual("kkt_residual", nx, nu, N, batch, G, C, g, c, z, lam, res, stream)
+
+    def kkt_residual_shared(self, nx, nu, N, batch, G, C, g, c, z, lam, res=None, stream=None):
+        """gbdpcg_kkt_residual_shared_*: one problem's G and C, `batch` g, c, z and lambda."""
+        return self._kkt_residual("kkt_residual_shared", nx, nu, N, batch, G, C, g, c, z, lam, res, stream)
 
     def _kkt_args(self, nx, nu, N, batch, G, C, g, c, S, gamma, Ginv, Pinv, kind, lam, r, p, tol, max_iter, iters, mie, z):
         suf, ft = _suffix(G)

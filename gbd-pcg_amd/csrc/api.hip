@@ -758,6 +758,17 @@ gbdpcg_status form_gamma_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint3
     HIP_TRY(h, launch_form_gamma<T>(h->dev, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, d_gamma, (hipStream_t)stream, shared));
     return GBDPCG_OK;
 }
+template <typename T>
+gbdpcg_status kkt_residual_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_G, const T *d_C,
+                                const T *d_g, const T *d_c, const T *d_z, const T *d_lambda, T *d_res, void *stream, bool shared)
+{
+    if (!h || !d_G || !d_g || !d_c || !d_z || !d_lambda || !d_res || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))
+        return GBDPCG_ERR_INVALID;
+    if (!schur_shape_ok<T>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_kkt_residual<T>(h->dev, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, (hipStream_t)stream, shared));
+    return GBDPCG_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1257,6 +1268,24 @@ GBDPCG_KKT_RESOLVE(f64, double)
 GBDPCG_SHARED(f32, float)
 GBDPCG_SHARED(f64, double)
 #undef GBDPCG_SHARED
+
+// ---- KKT residual norms of (z, lambda): one launch, no handle state; the shared twin reads one problem's G and C
+#define GBDPCG_KKT_RESIDUAL(SUF, TYPE)                                                                                              \
+    gbdpcg_status gbdpcg_kkt_residual_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,                  \
+                                            const TYPE *d_G, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c, const TYPE *d_z,      \
+                                            const TYPE *d_lambda, TYPE *d_res, void *stream)                                        \
+    {                                                                                                                               \
+        return kkt_residual_impl<TYPE>(h, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, stream, false);                \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_kkt_residual_shared_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,           \
+                                                   const TYPE *d_G, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c,              \
+                                                   const TYPE *d_z, const TYPE *d_lambda, TYPE *d_res, void *stream)                \
+    {                                                                                                                               \
+        return kkt_residual_impl<TYPE>(h, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, stream, true);                 \
+    }
+GBDPCG_KKT_RESIDUAL(f32, float)
+GBDPCG_KKT_RESIDUAL(f64, double)
+#undef GBDPCG_KKT_RESIDUAL
 
 gbdpcg_status gbdpcg_csr_to_bt_f32(uint32_t n, uint32_t N, const uint32_t *row_ptr, const uint32_t *col_ind,
                                    const float *val, float *h_M)

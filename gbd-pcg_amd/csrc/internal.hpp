@@ -209,7 +209,11 @@ hipError_t launch_recover_primal(const DeviceInfo &dev, uint32_t nx, uint32_t nu
 template <typename T>
 hipError_t launch_form_gamma(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *Ginv, const T *C,
                              const T *g, const T *c, T *gamma, hipStream_t s, bool shared = false);
-// (shared, both launchers: Ginv and C are one problem's blocks, used by every problem of the batch)
+// res[2b] = ||G z + g + C' lambda||_inf, res[2b+1] = ||C z - c||_inf of problem b (G: the Hessians, not their inverses)
+template <typename T>
+hipError_t launch_kkt_residual(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *G, const T *C,
+                               const T *g, const T *c, const T *z, const T *lambda, T *res, hipStream_t s, bool shared = false);
+// (shared, the three launchers: Ginv / G and C are one problem's blocks, used by every problem of the batch)
 template <typename T> bool schur_shape_ok(const DeviceInfo &dev, uint32_t nx, uint32_t nu);
 
 }  // namespace gbdpcg

@@ -467,6 +467,40 @@ gbdpcg_status gbdpcg_graph_create_kkt_resolve_shared_f64(gbdpcg_handle_t h, uint
                                                          uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z,
                                                          gbdpcg_graph_t *out);
 
+/* Does a point (z, lambda) solve the KKT system?  The two conditions an outer loop terminates on, per problem, on the device --
+ * for the step gbdpcg_kkt_step_*, gbdpcg_kkt_resolve_* or gbdpcg_kkt_resolve_shared_* has just written, or for any other point:
+ *     d_res[2b]   = || G z + g + C' lambda ||_inf     stationarity of problem b
+ *     d_res[2b+1] = || C z - c ||_inf                 feasibility of problem b
+ * in the call's precision, row by row of the convention above (d_G holds the HESSIANS, not d_Ginv; d_z has the layout of d_g;
+ * d_lambda that of d_gamma; d_res has 2 batch elements):
+ *     stationarity, x-part of knot k:   Q_k x_k + q_k + lambda_k - A_k' lambda_{k+1}
+ *     stationarity, u-part of knot k:   R_k u_k + r_k - B_k' lambda_{k+1}          (the last knot has neither product and no u)
+ *     feasibility of knot 0:            x_0 - c_0
+ *     feasibility of knot k+1:          x_{k+1} - A_k x_k - B_k u_k - c_{k+1}
+ * Every entry is one fma chain in a fixed order, so the result is bit-identical from call to call.  Both outputs are
+ * overwritten whatever d_res held before and do not depend on it.  A NaN anywhere in a problem's residual makes that norm
+ * NaN (the maximum is taken over bit patterns, it does not drop NaN as fmax does); Inf stays Inf; the other problems of the
+ * batch are unaffected.
+ * One launch, no handle state: asynchronous on `stream`, capturable (callers capture it on their stream behind the step; there
+ * is no graph constructor of its own), never allocates, frees or synchronises, needs nothing from gbdpcg_reserve.  d_C may be
+ * NULL when N == 1.  Null handle or required pointer, nx, nu, N or batch == 0: GBDPCG_ERR_INVALID; a shape gbdpcg_form_schur_*
+ * refuses: GBDPCG_ERR_UNSUPPORTED (nothing is written).
+ * gbdpcg_kkt_residual_shared_*: the shared-matrix twin -- d_G and d_C are ONE problem's blocks, every vector and d_res stay
+ * per problem; problem b gets exactly the bits the per-problem call gives it on `batch` copies, batch = 1 is the twin, and
+ * exactly one problem's extent is read behind d_G and d_C. */
+gbdpcg_status gbdpcg_kkt_residual_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                      const float *d_G, const float *d_C, const float *d_g, const float *d_c,
+                                      const float *d_z, const float *d_lambda, float *d_res, void *stream);
+gbdpcg_status gbdpcg_kkt_residual_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                      const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                      const double *d_z, const double *d_lambda, double *d_res, void *stream);
+gbdpcg_status gbdpcg_kkt_residual_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                             const float *d_G, const float *d_C, const float *d_g, const float *d_c,
+                                             const float *d_z, const float *d_lambda, float *d_res, void *stream);
+gbdpcg_status gbdpcg_kkt_residual_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                             const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                             const double *d_z, const double *d_lambda, double *d_res, void *stream);
+
 /* CSR ingestion (f3): repacks a host CSR matrix (csr_t<T>, include/types.cuh:7-15) whose
  * sparsity lies inside the block-tridiagonal pattern into the [L|D|R] layout (host arrays).
  * Entries outside the pattern give GBDPCG_ERR_INVALID.  Implements what the stub overload

@@ -396,6 +396,35 @@ void kktResolveShared(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoi
     }
 }
 
+// ---- KKT residual norms of a point (z, lambda) on the device (gbdpcg.h): d_res[2b] = ||G z + g + C' lambda||_inf,
+// d_res[2b+1] = ||C z - c||_inf of problem b.  d_G holds the Hessians (not G^-1).  One launch on `stream`, capturable behind a step.
+template <typename T>
+void kktResidual(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoints, uint32_t batch, const T *d_G, const T *d_C,
+                 const T *d_g, const T *d_c, const T *d_z, const T *d_lambda, T *d_res, hipStream_t stream = nullptr)
+{
+    static_assert(gbdpcg_detail::is_f32<T> || gbdpcg_detail::is_f64<T>, "kktResidual<T>: T is float or double");
+    gbdpcg_handle_t h = gbdpcg_detail::handle();
+    if constexpr (gbdpcg_detail::is_f32<T>) {
+        GBDPCG_CHECK(gbdpcg_kkt_residual_f32(h, stateSize, controlSize, knotPoints, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, stream), "kktResidual");
+    } else {
+        GBDPCG_CHECK(gbdpcg_kkt_residual_f64(h, stateSize, controlSize, knotPoints, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, stream), "kktResidual");
+    }
+}
+
+// ... and its shared-matrix twin: d_G and d_C are one problem's blocks, every vector and d_res stay per problem.
+template <typename T>
+void kktResidualShared(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoints, uint32_t batch, const T *d_G, const T *d_C,
+                       const T *d_g, const T *d_c, const T *d_z, const T *d_lambda, T *d_res, hipStream_t stream = nullptr)
+{
+    static_assert(gbdpcg_detail::is_f32<T> || gbdpcg_detail::is_f64<T>, "kktResidualShared<T>: T is float or double");
+    gbdpcg_handle_t h = gbdpcg_detail::handle();
+    if constexpr (gbdpcg_detail::is_f32<T>) {
+        GBDPCG_CHECK(gbdpcg_kkt_residual_shared_f32(h, stateSize, controlSize, knotPoints, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, stream), "kktResidualShared");
+    } else {
+        GBDPCG_CHECK(gbdpcg_kkt_residual_shared_f64(h, stateSize, controlSize, knotPoints, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, stream), "kktResidualShared");
+    }
+}
+
 // ---- the README's spelling (README.md:42): int pcg_solve<T>(cbtd_t *h_S, ...) ---------------------
 template <typename T>
 int pcg_solve(cbtd_t<T> *h_S, T *h_gamma, T *h_lambda, unsigned stateSize, unsigned knotPoints,
