@@ -625,17 +625,21 @@ __global__ __launch_bounds__((K * PersistGeom<T, NCT>::TPK)) void pcg_persist_ke
 // ---- single-reduction variant (opt-in: GBDPCG_PATH_PERSISTENT_1R) ------------------------------------------------------
 // The same solve in the Chronopoulos-Gear form of preconditioned CG, arranged so that an iteration crosses the chip
 // ONCE (the north star's "single cross-CU reduction per iteration"):
-//     u = Pinv r ; w = S u ; gamma = r.u ; delta = u.w                      (both inner products in ONE all-gather)
-//     beta = gamma / gamma_old ; alpha = gamma / (delta - beta gamma / alpha_old)      (beta = 0, alpha = gamma / delta first)
+//     u = Pinv r ; w = S u ; gamma = r.u ; delta = u.w ; chi = u.s + p.w    (all inner products in ONE all-gather)
+//     beta = gamma / gamma_old ; q = delta + beta chi + beta^2 q_old ; alpha = gamma / q       (beta = 0, q = delta first)
 //     p = u + beta p ; s = w + beta s ; lambda += alpha p ; r -= alpha s
+// q is p.Sp of the NEW direction written out, (u + beta p).(w + beta s) with the old p and s = S p: it holds for ANY S and
+// Pinv in the [L|D|R] storage.  (Chronopoulos and Gear replace chi by -2 gamma / alpha_old, which is what it equals when S
+// and Pinv are symmetric matrices -- and only then: on operators that are not, that form computes other iterates, lambda off
+// by its own size after four iterations, tests/test_gpu_layout.py.  chi costs two fma per row and a third value per slot.)
 // w = S u needs u on the two knots next to the workgroup's own.  Instead of a second hand-off they are recomputed here:
 // the workgroup also keeps the Pinv block-rows of those two knots in registers (the threads of its first / last own
 // knot hold one more row run each: +28 VGPRs in fp64) and carries r, s and w on a TWO-knot halo; what travels with the
-// all-gather is {gamma, delta} and the two outer own knots of w on each side.  Redundant values are bit-identical: every
+// all-gather is {gamma, delta, chi} and the two outer own knots of w on each side.  Redundant values are bit-identical: every
 // copy is the same sequence of fma's on the same bits.
 // In exact arithmetic p, lambda, r and the tested quantity gamma_i = r_i . Pinv r_i are those of pcg.cuh:154-206 (the exit
-// test |gamma| < tol is the same test, seen one product pair later); the ROUNDING sequence differs (alpha is not
-// eta / (p . S p), and s = S p is carried by recurrence), so this is not the reference's recurrence and AUTO does not
+// test |gamma| < tol is the same test, seen one product pair later); the ROUNDING sequence differs (p . S p is
+// assembled from four products, and s = S p is carried by recurrence), so this is not the reference's recurrence and AUTO does not
 // pick it.  Against the oracle: equal iteration counts and fp64 lambda within 1e-10 on every shape of
 // tests/test_gpu_persist.py (a = 0.5 and a = 0.9 generators).  Two or three knots per workgroup only.
 template <typename T, int NCT, int K, bool HAS_PINV>
@@ -657,8 +661,8 @@ __global__ __launch_bounds__((K * PersistGeom<T, NCT>::TPK)) void pcg_persist1r_
 
     __shared__ __attribute__((aligned(16))) T rwin[WINP], swin[WINP], uwin[WINP], wwin[WINP], lwin[WINP];
     __shared__ __attribute__((aligned(16))) T lam[OWN], pown[OWN];
-    __shared__ T dots_g[NWAVES], dots_d[NWAVES];
-    __shared__ T bc[4];          // [0] alpha, [1] beta, [2] gamma_old, [3] alpha_old
+    __shared__ T dots_g[NWAVES], dots_d[NWAVES], dots_c[NWAVES];
+    __shared__ T bc[4];          // [0] alpha, [1] beta, [2] gamma_old, [3] q_old = p . S p of the direction in use
     __shared__ uint32_t bci[4];  // [0] stop (1 converged, 2 hand-off timed out, 3 ran out), [1] iterations, [3] persist_leave's flag
     __shared__ T rescue_red[2 * NWAVES];
 
@@ -685,9 +689,9 @@ __global__ __launch_bounds__((K * PersistGeom<T, NCT>::TPK)) void pcg_persist1r_
     T *lambda = a.lambda + (size_t)prob * len;
 
     u64 *ws = ws_all + (size_t)prob * persist_words<T>(n, N);
-    constexpr uint32_t PSW = kPartStrideWords > 2 * PER ? kPartStrideWords : 2 * PER;
-    static_assert(PSW == kPartStrideWords, "two values per partial slot fit the slot stride");
-    u64 *part = ws + kPersistCtrl;                       // [2][N] slots of {gamma, delta}
+    constexpr uint32_t PSW = kPartStrideWords > 3 * PER ? kPartStrideWords : 3 * PER;
+    static_assert(PSW == kPartStrideWords, "three values per partial slot fit the slot stride");
+    u64 *part = ws + kPersistCtrl;                       // [2][N] slots of {gamma, delta, chi}
     const __amdgpu_buffer_rsrc_t region = __builtin_amdgcn_make_buffer_rsrc(
         part, 0, (int)((persist_words<T>(n, N) - kPersistCtrl) * 8), 0x00020000);
     const uint32_t h_base = (uint32_t)(persist_part_words<T>(N) * 8);
@@ -799,37 +803,45 @@ __global__ __launch_bounds__((K * PersistGeom<T, NCT>::TPK)) void pcg_persist1r_
         }
         __syncthreads();
         GBDPCG_STAMP(3, stamp_here)
-        // w = S u on the own knots ; share of delta = u . w
+        // w = S u on the own knots ; shares of delta = u . w and of chi = u . s + p . w (s, p: still the old direction's)
         {
             T y = group_sum8(persist_row_dot<T, COLS, (THREADS > 768), Gm::ALIGNED>(sreg, uwin + (slot + 1) * n + cbase,
                                                                                    uwin + (slot + 1) * n + cbase, T(0)));
-            T d = T(0);
+            T d = T(0), c = T(0);
             if (g == 0 && row_live) {
+                const T uo = uwin[(slot + 2) * n + row];
                 wwin[(slot + 2) * n + row] = y;
-                d = uwin[(slot + 2) * n + row] * y;
+                d = uo * y;
+                c = fma_t(uo, swin[(slot + 2) * n + row], pown[slot * n + row] * y);
             }
             d = wave_sum(d);
-            if (lane == 0) dots_d[wave] = d;
+            c = wave_sum(c);
+            if (lane == 0) {
+                dots_d[wave] = d;
+                dots_c[wave] = c;
+            }
         }
         __syncthreads();
         GBDPCG_STAMP(4, stamp_here)
-        // {gamma, delta, the two outer own knots of w per side} in ONE all-gather
+        // {gamma, delta, chi, the two outer own knots of w per side} in ONE all-gather
         if (wave == PUB) {   // the partials first: every workgroup waits for them
-            T pg = dots_g[0], pd = dots_d[0];
+            T pg = dots_g[0], pd = dots_d[0], pc = dots_c[0];
 #pragma unroll
             for (uint32_t q = 1; q < NWAVES; ++q) {
                 pg += dots_g[q];
                 pd += dots_d[q];
+                pc += dots_c[q];
             }
             if (lane == 0) {
                 slot_store(region, (par * N + w) * PSW * 8u, base + ew, pg);
                 slot_store(region, (par * N + w) * PSW * 8u + PER * 8u, base + ew, pd);
+                slot_store(region, (par * N + w) * PSW * 8u + 2 * PER * 8u, base + ew, pc);
             }
         }
         GBDPCG_1R_PUBLISH_HALO(wwin, par, base + ew)
         if (wave == 0) {
-            T tot[2];
-            const bool ok = persist_sweep_n<T, NCT, 2, HN>(region, par * N * PSW * 8u, nbr_l(par), nbr_r(par), W, base + ew, lane,
+            T tot[3];
+            const bool ok = persist_sweep_n<T, NCT, 3, HN>(region, par * N * PSW * 8u, nbr_l(par), nbr_r(par), W, base + ew, lane,
                                                           spin_limit, tot, wwin, wwin + (K + 2) * n);
             GBDPCG_STAMP(5, stamp_here)
             if (lane == 0) {
@@ -845,11 +857,11 @@ __global__ __launch_bounds__((K * PersistGeom<T, NCT>::TPK)) void pcg_persist1r_
                     bc[1] = iter > 0 ? gam / bc[2] : T(0);        // the beta of the direction update the reference still runs
                 } else {
                     const T beta = iter > 0 ? gam / bc[2] : T(0);
-                    const T alpha = iter > 0 ? gam / (del - beta * gam / bc[3]) : gam / del;
-                    bc[0] = alpha;
+                    const T q = iter > 0 ? fma_t(beta, fma_t(beta, bc[3], tot[2]), del) : del;   // (u + beta p).(w + beta s)
+                    bc[0] = gam / q;
                     bc[1] = beta;
                     bc[2] = gam;
-                    bc[3] = alpha;
+                    bc[3] = q;
                 }
             }
         }

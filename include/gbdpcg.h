@@ -66,11 +66,14 @@ typedef enum gbdpcg_path {
                                   (streaming kernel: slow, correct).  The caller always gets a solved problem; on a
                                   device shared with long-running kernels GBDPCG_PATH_SPLIT avoids the wait. */
     GBDPCG_PATH_PERSISTENT_1R = 4 /* OPT-IN, never chosen by AUTO: the persistent launch with the single-reduction
-                                  (Chronopoulos-Gear) recurrence -- u = Pinv r, w = S u, gamma = r.u and delta = u.w in ONE
-                                  all-gather per iteration (the halo knots of u are recomputed, not exchanged),
-                                  alpha = gamma / (delta - beta gamma / alpha_old), s = S p by recurrence.  Same iterates and the same exit test as pcg.cuh:154-206 in exact arithmetic,
-                                  a different rounding sequence: equal iteration counts and fp64 lambda within 1e-13 of the
-                                  default path on the test shapes, but not the reference's recurrence. */
+                                  (Chronopoulos-Gear style) recurrence -- u = Pinv r, w = S u, gamma = r.u, delta = u.w and
+                                  chi = u.s + p.w in ONE all-gather per iteration (the halo knots of u are recomputed, not
+                                  exchanged), p.Sp = delta + beta chi + beta^2 (p.Sp)_old, s = S p by recurrence.  Same
+                                  iterates and the same exit test as pcg.cuh:154-206 in exact arithmetic, for ANY S and Pinv
+                                  the storage holds, symmetric as matrices or not (chi is carried for that: the textbook form
+                                  replaces it by an identity of symmetric operators); a different rounding sequence: equal
+                                  iteration counts and fp64 lambda within 1e-10 of the oracle on the test shapes, but not
+                                  the reference's recurrence. */
 } gbdpcg_path;
 
 /* Preconditioners gbdpcg_form_pinv can build from S. */
@@ -251,7 +254,11 @@ gbdpcg_status gbdpcg_graph_destroy(gbdpcg_graph_t g);
 
 /* Builds Pinv from S on the device (f1): the step the reference's host overload lacks
  * (interface.cuh:33-34,45-46) and MPCGPU does with the block helpers of
- * include/utils.cuh:96-161.  d_Pinv gets the same [L|D|R] layout as d_S. */
+ * include/utils.cuh:96-161.  d_Pinv gets the same [L|D|R] layout as d_S.
+ * The D_k of S are taken to be symmetric: the kernels invert D_k and write the UPPER triangle of D_k^-1 into both
+ * halves of the block (so that the stair comes out symmetric bit for bit whenever S is), which is D_k^-1 only for a
+ * symmetric D_k.  L_{k+1} and R_k are independent: the left slot -D_{k+1}^-1 L_{k+1} D_k^-1 is evaluated from L_{k+1} itself
+ * whenever it is not the mirror image of R_k, in every symmetric mode (tests/test_gpu_layout.py). */
 gbdpcg_status gbdpcg_form_pinv_f32(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batch,
                                    const float *d_S, float *d_Pinv, gbdpcg_pinv_kind kind,
                                    void *stream);
