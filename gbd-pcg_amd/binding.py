@@ -40,6 +40,9 @@ SYMBOLS = [
     "gbdpcg_kkt_resolve_shared_f32", "gbdpcg_kkt_resolve_shared_f64",
     "gbdpcg_graph_create_kkt_resolve_shared_f32", "gbdpcg_graph_create_kkt_resolve_shared_f64",
     "gbdpcg_kkt_residual_f32", "gbdpcg_kkt_residual_f64", "gbdpcg_kkt_residual_shared_f32", "gbdpcg_kkt_residual_shared_f64",
+    "gbdpcg_form_schur_reg_f32", "gbdpcg_form_schur_reg_f64", "gbdpcg_kkt_step_reg_f32", "gbdpcg_kkt_step_reg_f64",
+    "gbdpcg_graph_create_kkt_step_reg_f32", "gbdpcg_graph_create_kkt_step_reg_f64",
+    "gbdpcg_kkt_residual_reg_f32", "gbdpcg_kkt_residual_reg_f64",
     "gbdpcg_csr_to_bt_f32", "gbdpcg_csr_to_bt_f64", "gbdpcg_version",
 ]
 
@@ -64,6 +67,12 @@ def _resolve_argtypes(lib):
         # the residual norms: h, nx, nu, N, batch, G, C, g, c | z, lambda, res, stream
         getattr(lib, f"gbdpcg_kkt_residual_{suf}").argtypes = head + [vp, vp, vp, vp]
         getattr(lib, f"gbdpcg_kkt_residual_shared_{suf}").argtypes = head + [vp, vp, vp, vp]
+        # per-problem regularisation: d_rho directly behind c
+        step = [vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, ft, u32, vp, vp, vp]   # S, gamma, Ginv, Pinv, kind, lambda, r, p, tol, max_iter, iters, flags, z
+        getattr(lib, f"gbdpcg_form_schur_reg_{suf}").argtypes = head + [vp] + [vp, vp, vp, vp]     # rho | S, gamma, Ginv, stream
+        getattr(lib, f"gbdpcg_kkt_step_reg_{suf}").argtypes = head + [vp] + step + [vp]
+        getattr(lib, f"gbdpcg_graph_create_kkt_step_reg_{suf}").argtypes = head + [vp] + step + [ctypes.POINTER(vp)]
+        getattr(lib, f"gbdpcg_kkt_residual_reg_{suf}").argtypes = head + [vp] + [vp, vp, vp, vp]   # rho | z, lambda, res, stream
 
 _lib = None
 
@@ -468,6 +477,67 @@ class Solver:
         fn = getattr(self.lib, f"gbdpcg_graph_create_kkt_step_{suf}")
         self._check(fn(*args, ctypes.byref(gr)), "graph_create_kkt_step")
         return Graph(self, gr, keep=(G, C, g, c, S, gamma, Ginv, Pinv, lam, r, p, iters, max_iter_exit, z))
+
+    # ---- per-problem regularisation: problem b on G_b + rho_b I, rho a device tensor [batch] of G's dtype (include/gbdpcg.h)
+    @staticmethod
+    def _rho(rho, batch, G):
+        assert rho is not None and rho.is_cuda and rho.is_contiguous() and rho.numel() == batch and rho.dtype == G.dtype
+        return rho
+
+    def form_schur_reg(self, nx, nu, N, batch, G, C, g, c, rho, S=None, gamma=None, Ginv=None, want_ginv=True, stream=None):
+        """gbdpcg_form_schur_reg_*: S, gamma and (optionally) the inverse blocks of G + rho I, the add fused into the formation."""
+        import torch
+        suf, _ = _suffix(G)
+        if S is None:
+            S = torch.empty(batch * 3 * nx * nx * N, dtype=G.dtype, device=G.device)
+        if gamma is None:
+            gamma = torch.empty(batch * nx * N, dtype=G.dtype, device=G.device)
+        if Ginv is None and want_ginv:
+            Ginv = torch.empty_like(G)
+        fn = getattr(self.lib, f"gbdpcg_form_schur_reg_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(G), _p(C), _p(g), _p(c), _p(self._rho(rho, batch, G)), _p(S), _p(gamma), _p(Ginv),
+                       self._stream(stream)), "form_schur_reg")
+        return S, gamma, Ginv
+
+    def _kkt_reg_args(self, nx, nu, N, batch, G, C, g, c, rho, S, gamma, Ginv, Pinv, kind, lam, r, p, tol, max_iter, iters, mie, z):
+        suf, _ = _suffix(G)
+        return suf, (self.h, nx, nu, N, batch, _p(G), _p(C), _p(g), _p(c), _p(self._rho(rho, batch, G)), _p(S), _p(gamma), _p(Ginv),
+                     _p(Pinv), kind, _p(lam), _p(r), _p(p), tol, max_iter, _p(iters), _p(mie), _p(z))
+
+    def kkt_step_reg(self, nx, nu, N, batch, G, C, g, c, rho, S, gamma, Ginv, Pinv, lam, z, kind=PINV_STAIR, r=None, p=None, tol=1e-6,
+                     max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_kkt_step_reg_*: the whole step of kkt_step on G + rho I, one call."""
+        import torch
+        if iters is None:
+            iters = torch.zeros(batch, dtype=torch.int32, device=G.device)
+        if max_iter_exit is None:
+            max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=G.device)
+        suf, args = self._kkt_reg_args(nx, nu, N, batch, G, C, g, c, rho, S, gamma, Ginv, Pinv, kind, lam, r, p, tol, max_iter, iters,
+                                       max_iter_exit, z)
+        self._check(getattr(self.lib, f"gbdpcg_kkt_step_reg_{suf}")(*args, self._stream(stream)), "kkt_step_reg")
+        return iters, max_iter_exit
+
+    def graph_kkt_step_reg(self, nx, nu, N, batch, G, C, g, c, rho, S, gamma, Ginv, Pinv, lam, r, p, tol, max_iter, iters,
+                           max_iter_exit, z, kind=PINV_STAIR):
+        """Capture the regularised step into one hipGraph (gbdpcg_graph_create_kkt_step_reg_*): the graph keeps rho's pointer,
+        rewrite the tensor in place between replays."""
+        suf, args = self._kkt_reg_args(nx, nu, N, batch, G, C, g, c, rho, S, gamma, Ginv, Pinv, kind, lam, r, p, tol, max_iter, iters,
+                                       max_iter_exit, z)
+        gr = ctypes.c_void_p()
+        self._check(getattr(self.lib, f"gbdpcg_graph_create_kkt_step_reg_{suf}")(*args, ctypes.byref(gr)), "graph_create_kkt_step_reg")
+        return Graph(self, gr, keep=(G, C, g, c, rho, S, gamma, Ginv, Pinv, lam, r, p, iters, max_iter_exit, z))
+
+    def kkt_residual_reg(self, nx, nu, N, batch, G, C, g, c, rho, z, lam, res=None, stream=None):
+        """gbdpcg_kkt_residual_reg_*: [batch, 2] tensor of (||(G + rho I) z + g + C' lambda||_inf, ||C z - c||_inf) per problem."""
+        import torch
+        suf, _ = _suffix(G)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=G.dtype, device=G.device)
+        assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == G.dtype
+        fn = getattr(self.lib, f"gbdpcg_kkt_residual_reg_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(G), _p(C), _p(g), _p(c), _p(self._rho(rho, batch, G)), _p(z), _p(lam), _p(res),
+                       self._stream(stream)), "kkt_residual_reg")
+        return res.view(batch, 2)
 
 
 class Graph:

@@ -542,9 +542,11 @@ gbdpcg_status solve_host_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, const T
     return st;
 }
 
+// (reg: gbdpcg_form_schur_reg_* -- problem b is formed from G_b + rho_b I, d_rho [batch] on the device, required)
 template <typename T>
 gbdpcg_status form_schur_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_G, const T *d_C,
-                              const T *d_g, const T *d_c, T *d_S, T *d_gamma, T *d_Ginv, void *stream);
+                              const T *d_g, const T *d_c, T *d_S, T *d_gamma, T *d_Ginv, void *stream, const T *d_rho = nullptr,
+                              bool reg = false);
 template <typename T>
 gbdpcg_status recover_primal_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv,
                                   const T *d_C, const T *d_g, const T *d_lambda, T *d_z, void *stream, bool shared = false);
@@ -560,6 +562,8 @@ template <typename T> struct KktOperands {
     T *Ginv, *z;
     bool resolve = false;   // gbdpcg_kkt_resolve_*: G is not looked at, Ginv, S and Pinv are read only
     bool shared = false;    // gbdpcg_kkt_resolve_shared_*: Ginv, C, S and Pinv are ONE problem's, used by every problem of the batch
+    const T *rho = nullptr; // gbdpcg_kkt_step_reg_*: [batch] on the device, read by the formation kernel when it runs
+    bool reg = false;       // ... and the step is that of G_b + rho_b I (rho is then required)
 };
 
 // KKT blocks -> S, gamma, G^-1 -> Phi^-1 -> PCG -> primal step, on one stream (capturable: no allocation after the first
@@ -570,8 +574,9 @@ gbdpcg_status kkt_step_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t N, uint32_t
                             uint32_t *d_iters, uint8_t *d_exit, hipStream_t stream)
 {
     if (!k.Ginv || !k.z) return GBDPCG_ERR_INVALID;
-    gbdpcg_status st = form_schur_impl<T>(h, nx, k.nu, N, batch, k.G, k.C, k.g, k.c, d_S, d_gamma, k.Ginv, stream);
+    gbdpcg_status st = form_schur_impl<T>(h, nx, k.nu, N, batch, k.G, k.C, k.g, k.c, d_S, d_gamma, k.Ginv, stream, k.rho, k.reg);
     if (st != GBDPCG_OK) return st;
+    // (the regularised formation adds rho_b to a block before BOTH of its uses, so what follows holds for it unchanged)
     // form_schur writes S exactly symmetric in storage (R_k and L_{k+1} are copies of the same registers), and where the
     // one-launch stair kernel forms Pinv from such an S it writes every pair as mirror images: in the default symmetric mode
     // the verdicts of gbdpcg_form_pinv_solve_* would all read "symmetric", so they are neither written nor read here and the
@@ -727,13 +732,14 @@ gbdpcg_status csr_to_bt_impl(uint32_t n, uint32_t N, const uint32_t *row_ptr, co
 namespace {
 template <typename T>
 gbdpcg_status form_schur_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_G, const T *d_C,
-                              const T *d_g, const T *d_c, T *d_S, T *d_gamma, T *d_Ginv, void *stream)
+                              const T *d_g, const T *d_c, T *d_S, T *d_gamma, T *d_Ginv, void *stream, const T *d_rho, bool reg)
 {
-    if (!h || !d_G || !d_g || !d_c || !d_S || !d_gamma || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))
+    if (!h || !d_G || !d_g || !d_c || !d_S || !d_gamma || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch) || (reg && !d_rho))
         return GBDPCG_ERR_INVALID;
     if (!schur_shape_ok<T>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;
     DEVICE_SCOPE(h);
-    HIP_TRY(h, launch_form_schur<T>(h->dev, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_S, d_gamma, d_Ginv, (hipStream_t)stream));
+    HIP_TRY(h, launch_form_schur<T>(h->dev, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_S, d_gamma, d_Ginv, (hipStream_t)stream,
+                                    reg ? d_rho : nullptr));
     return GBDPCG_OK;
 }
 template <typename T>
@@ -760,13 +766,16 @@ gbdpcg_status form_gamma_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint3
 }
 template <typename T>
 gbdpcg_status kkt_residual_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_G, const T *d_C,
-                                const T *d_g, const T *d_c, const T *d_z, const T *d_lambda, T *d_res, void *stream, bool shared)
+                                const T *d_g, const T *d_c, const T *d_z, const T *d_lambda, T *d_res, void *stream, bool shared,
+                                const T *d_rho = nullptr, bool reg = false)   // reg: the stationarity of G_b + rho_b I
 {
-    if (!h || !d_G || !d_g || !d_c || !d_z || !d_lambda || !d_res || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))
+    if (!h || !d_G || !d_g || !d_c || !d_z || !d_lambda || !d_res || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch) ||
+        (reg && !d_rho))
         return GBDPCG_ERR_INVALID;
     if (!schur_shape_ok<T>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;
     DEVICE_SCOPE(h);
-    HIP_TRY(h, launch_kkt_residual<T>(h->dev, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, (hipStream_t)stream, shared));
+    HIP_TRY(h, launch_kkt_residual<T>(h->dev, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, (hipStream_t)stream, shared,
+                                      reg ? d_rho : nullptr));
     return GBDPCG_OK;
 }
 }  // namespace
@@ -1286,6 +1295,52 @@ GBDPCG_SHARED(f64, double)
 GBDPCG_KKT_RESIDUAL(f32, float)
 GBDPCG_KKT_RESIDUAL(f64, double)
 #undef GBDPCG_KKT_RESIDUAL
+
+// ---- per-problem regularisation: the entry points above on G_b + rho_b I (d_rho: [batch] on the device, directly after d_c,
+// read when the kernels run).  The same code paths with the REG instantiations of the formation / residual kernels; the solve and
+// the recovery work on the S, gamma and G^-1 the formation wrote and need no switch.
+#define GBDPCG_REG(SUF, TYPE)                                                                                                       \
+    gbdpcg_status gbdpcg_form_schur_reg_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,                \
+                                              const TYPE *d_G, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c, const TYPE *d_rho,  \
+                                              TYPE *d_S, TYPE *d_gamma, TYPE *d_Ginv, void *stream)                                  \
+    {                                                                                                                               \
+        return form_schur_impl<TYPE>(h, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_S, d_gamma, d_Ginv, stream, d_rho, true);            \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_kkt_step_reg_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const TYPE *d_G, \
+                                            const TYPE *d_C, const TYPE *d_g, const TYPE *d_c, const TYPE *d_rho, TYPE *d_S,          \
+                                            TYPE *d_gamma, TYPE *d_Ginv, TYPE *d_Pinv, gbdpcg_pinv_kind kind, TYPE *d_lambda,         \
+                                            TYPE *d_r, TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters,                    \
+                                            uint8_t *d_max_iter_exit, TYPE *d_z, void *stream)                                       \
+    {                                                                                                                               \
+        KktOperands<TYPE> k{nu, d_G, d_C, d_g, d_c, d_Ginv, d_z};                                                                   \
+        k.rho = d_rho;                                                                                                              \
+        k.reg = true;                                                                                                               \
+        return kkt_step_impl<TYPE>(h, nx, N, batch, k, d_S, d_gamma, d_Pinv, kind, d_lambda, d_r, d_p, tol, max_iter, d_iters,       \
+                                   d_max_iter_exit, (hipStream_t)stream);                                                           \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_graph_create_kkt_step_reg_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,     \
+                                                         const TYPE *d_G, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c,          \
+                                                         const TYPE *d_rho, TYPE *d_S, TYPE *d_gamma, TYPE *d_Ginv, TYPE *d_Pinv,     \
+                                                         gbdpcg_pinv_kind kind, TYPE *d_lambda, TYPE *d_r, TYPE *d_p, TYPE tol,       \
+                                                         uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, TYPE *d_z,   \
+                                                         gbdpcg_graph_t *out)                                                        \
+    {                                                                                                                               \
+        if (!d_rho || !d_S || !d_gamma || !d_Pinv || !d_Ginv || !d_z || (int)kind < 0 || (int)kind > 2) return GBDPCG_ERR_INVALID;  \
+        KktOperands<TYPE> k{nu, d_G, d_C, d_g, d_c, d_Ginv, d_z};                                                                   \
+        k.rho = d_rho;                                                                                                              \
+        k.reg = true;                                                                                                               \
+        return graph_create_impl<TYPE>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters,            \
+                                       d_max_iter_exit, out, (int)kind, &k);                                                        \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_kkt_residual_reg_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,              \
+                                                const TYPE *d_G, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c,                 \
+                                                const TYPE *d_rho, const TYPE *d_z, const TYPE *d_lambda, TYPE *d_res, void *stream) \
+    {                                                                                                                               \
+        return kkt_residual_impl<TYPE>(h, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, stream, false, d_rho, true);   \
+    }
+GBDPCG_REG(f32, float)
+GBDPCG_REG(f64, double)
+#undef GBDPCG_REG
 
 gbdpcg_status gbdpcg_csr_to_bt_f32(uint32_t n, uint32_t N, const uint32_t *row_ptr, const uint32_t *col_ind,
                                    const float *val, float *h_M)

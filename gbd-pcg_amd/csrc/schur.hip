@@ -4,6 +4,11 @@
 //   recover_primal : lambda -> z = -G^-1 (g + C' lambda)
 //   form_gamma     : G^-1 (as form_schur wrote it), C and NEW g, c -> gamma alone, for a linearisation that is kept
 //   kkt_residual   : G, C, g, c and a point (z, lambda) -> ||G z + g + C' lambda||_inf and ||C z - c||_inf per problem
+// REG (gbdpcg_form_schur_reg_*, gbdpcg_kkt_step_reg_*, gbdpcg_kkt_residual_reg_*): problem b works on G_b + rho_b I.  A compile-time
+// switch of the formation and residual kernels: where a kernel picks up Q_k or R_k, every diagonal entry d becomes fl(d + rho_b) --
+// one rounding, rho_b one scalar load per wave or run (a wave serves one problem at a time) and an SGPR operand of the add, never
+// staged in LDS -- and everything
+// downstream is the arithmetic it was.  The instantiations without REG are what they were before the switch existed.
 //
 // The reference tree has no code for either (/root/reference/README.md:2-11 states only the system
 // Pinv S lambda = Pinv gamma that comes out of the first, README.md:66-77 cites the paper that describes them; MPCGPU
@@ -85,13 +90,16 @@ __host__ __device__ inline uint32_t recover_wave_elems(uint32_t nx, uint32_t nu)
 
 // Inverse of the m x m block at `src` (global, column-major) into `out` (LDS, column-major, mirrored across the diagonal).
 // Same arithmetic, element for element, as pinv_diag_kernel (pinv.hip): pr = row_j * (1/pivot), a_rc = fma(-a_rj, pr_c, a_rc).
-template <typename T>
-__device__ __forceinline__ void wave_invert(const T *__restrict__ src, uint32_t m, T *tab, T *prow, T *pcol, T *out, uint32_t lane)
+// REG: the block inverted is src + rho I (the diagonal entries rounded once on their way into the tableau).
+template <typename T, bool REG = false>
+__device__ __forceinline__ void wave_invert(const T *__restrict__ src, uint32_t m, T *tab, T *prow, T *pcol, T *out, uint32_t lane,
+                                            T rho = T(0))
 {
     const uint32_t w = 2 * m;
     for (uint32_t i = lane; i < m * m; i += 64) {
         const uint32_t c = i / m, r = i - c * m;
-        tab[r * w + c] = src[i];
+        if constexpr (REG) tab[r * w + c] = (r == c) ? src[i] + rho : src[i];
+        else tab[r * w + c] = src[i];
         tab[r * w + m + c] = (r == c) ? T(1) : T(0);
     }
     wave_sync();
@@ -122,10 +130,11 @@ __device__ __forceinline__ void wave_invert(const T *__restrict__ src, uint32_t 
 
 }  // namespace
 
-template <typename T>
+template <typename T, bool REG = false>
 __global__ __launch_bounds__(256) void schur_form_kernel(uint32_t nx, uint32_t nu, uint32_t N, uint64_t rows, const T *__restrict__ G,
                                                         const T *__restrict__ C, const T *__restrict__ g, const T *__restrict__ c,
-                                                        T *__restrict__ S, T *__restrict__ gamma, T *__restrict__ Ginv)
+                                                        T *__restrict__ S, T *__restrict__ gamma, T *__restrict__ Ginv,
+                                                        const T *__restrict__ rho)   // [batch], REG only
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -145,9 +154,13 @@ __global__ __launch_bounds__(256) void schur_form_kernel(uint32_t nx, uint32_t n
     const T *Gp = G + prob * d.szG, *Cp = C + prob * d.szC, *gp = g + prob * d.szg, *cp = c + prob * d.szc;
     T *Sk = S + (size_t)row * 3 * nn;
     T *Gi = Ginv ? Ginv + prob * d.szG : nullptr;
+    // the wave's problem as the scalar unit sees it: rho_b is one scalar load, and the wave of row k+1 adds the same number
+    // to the same Q_k, so R_k and L_{k+1} stay mirror images
+    T rb = T(0);
+    if constexpr (REG) rb = rho[__builtin_amdgcn_readfirstlane((uint32_t)prob)];
 
     // this knot: Q_k^-1, q_k, c_k, A_k
-    wave_invert(Gp + (size_t)k * d.sg, nx, tab, prow, pcol, Qc, lane);
+    wave_invert<T, REG>(Gp + (size_t)k * d.sg, nx, tab, prow, pcol, Qc, lane, rb);
     if (Gi)
         for (uint32_t i = lane; i < nn; i += 64) Gi[(size_t)k * d.sg + i] = Qc[i];
     for (uint32_t i = lane; i < nx; i += 64) {
@@ -163,8 +176,8 @@ __global__ __launch_bounds__(256) void schur_form_kernel(uint32_t nx, uint32_t n
         for (uint32_t i = lane; i < xu; i += 64) Bp[i] = Cp[(size_t)j * d.sc + nn + i];
         for (uint32_t i = lane; i < nx; i += 64) qp[i] = gp[(size_t)j * d.sv + i];
         for (uint32_t i = lane; i < nu; i += 64) rp[i] = gp[(size_t)j * d.sv + nx + i];
-        wave_invert(Gp + (size_t)j * d.sg, nx, tab, prow, pcol, Qp, lane);
-        wave_invert(Gp + (size_t)j * d.sg + nn, nu, tab, prow, pcol, Rp, lane);
+        wave_invert<T, REG>(Gp + (size_t)j * d.sg, nx, tab, prow, pcol, Qp, lane, rb);
+        wave_invert<T, REG>(Gp + (size_t)j * d.sg + nn, nu, tab, prow, pcol, Rp, lane, rb);
         if (Gi)
             for (uint32_t i = lane; i < uu; i += 64) Gi[(size_t)j * d.sg + nn + i] = Rp[i];
         // W = A_j Q_j^-1 (L_k = -W),  V = B_j R_j^-1
@@ -443,10 +456,11 @@ template <typename T, int NX, int NU> struct QuadGeom {
 
 }  // namespace
 
-template <typename T, int NX, int NU>
+template <typename T, int NX, int NU, bool REG>
 __device__ __forceinline__ void schur_form_quad_body(uint32_t N, uint32_t run, uint32_t waves, const T *__restrict__ G,
                                                      const T *__restrict__ C, const T *__restrict__ g, const T *__restrict__ c,
-                                                     T *__restrict__ S, T *__restrict__ gamma, T *__restrict__ Ginv)
+                                                     T *__restrict__ S, T *__restrict__ gamma, T *__restrict__ Ginv,
+                                                     const T *__restrict__ rho)
 {
     using Q = QuadGeom<T, NX, NU>;
     static_assert(NX <= 15 && NU <= 15 && NU <= NX, "one knot per 16-lane quarter, one spare lane for the vector");
@@ -463,6 +477,9 @@ __device__ __forceinline__ void schur_form_quad_body(uint32_t N, uint32_t run, u
     const uint32_t prob = w / rpp, j_start = (w - prob * rpp) * run;
     const KktDims d(NX, NU, N);
     const T *Gp = G + (size_t)prob * d.szG, *Cp = C + (size_t)prob * d.szC, *gp = g + (size_t)prob * d.szg, *cp = c + (size_t)prob * d.szc;
+    // REG: the run's problem comes from blockIdx -- rho_b is one scalar load, an SGPR operand of the adds below for the whole run
+    T rb = T(0);
+    if constexpr (REG) rb = rho[prob];
 
     // where the elements this lane stores in the S write-out sit in LDS (the same every step)
     // The write-outs move SW consecutive elements per lane and store (one 16-byte store in fp32: a store instruction costs this
@@ -598,6 +615,14 @@ __device__ __forceinline__ void schur_form_quad_body(uint32_t N, uint32_t run, u
             }
         }
         wave_sync();
+        if constexpr (REG) {
+            // G_j + rho_b I: lane l bumps element l of the column it is about to pick up (its own LDS write, read back by itself
+            // in program order: no other lane looks at that column) -- one add per block and lane, in the silent step of a run as
+            // in the others, so the Q_j^-1 a neighbouring run recomputes is this one bit for bit.  (A quarter without a knot, and
+            // the identity that stands in for the last knot's R, get the add too: nothing of theirs is stored.)
+            if (l < NX) rQ[l * NX + l] += rb;
+            if (l < NU) rR[l * NU + l] += rb;
+        }
         // this lane's columns: Q_j (lane NX: q_j), R_j (lane NU: r_j)
         T Qc[NX], Rc[NU];
         {
@@ -790,21 +815,22 @@ __device__ __forceinline__ void schur_form_quad_body(uint32_t N, uint32_t run, u
 #endif
 }
 
-template <typename T, int NX, int NU>
+template <typename T, int NX, int NU, bool REG = false>
 __global__ __launch_bounds__(64) void schur_form_quad_kernel(uint32_t N, uint32_t run, uint32_t waves, const T *__restrict__ G,
                                                             const T *__restrict__ C, const T *__restrict__ g,
                                                             const T *__restrict__ c, T *__restrict__ S, T *__restrict__ gamma,
-                                                            T *__restrict__ Ginv)
+                                                            T *__restrict__ Ginv, const T *__restrict__ rho)
 {
-    schur_form_quad_body<T, NX, NU>(N, run, waves, G, C, g, c, S, gamma, Ginv);
+    schur_form_quad_body<T, NX, NU, REG>(N, run, waves, G, C, g, c, S, gamma, Ginv, rho);
 }
 // The form with one input buffer (fp32): held to 256 registers so that two waves share a SIMD.
-template <int NX, int NU>
+template <int NX, int NU, bool REG = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void schur_form_quad2_kernel(
     uint32_t N, uint32_t run, uint32_t waves, const float *__restrict__ G, const float *__restrict__ C, const float *__restrict__ g,
-    const float *__restrict__ c, float *__restrict__ S, float *__restrict__ gamma, float *__restrict__ Ginv)
+    const float *__restrict__ c, float *__restrict__ S, float *__restrict__ gamma, float *__restrict__ Ginv,
+    const float *__restrict__ rho)
 {
-    schur_form_quad_body<float, NX, NU>(N, run, waves, G, C, g, c, S, gamma, Ginv);
+    schur_form_quad_body<float, NX, NU, REG>(N, run, waves, G, C, g, c, S, gamma, Ginv, rho);
 }
 
 // z = -G^-1 (g + C' lambda): x_k = -Q_k^-1 (q_k + lambda_k - A_k' lambda_{k+1}),  u_k = -R_k^-1 (r_k - B_k' lambda_{k+1}).
@@ -1142,6 +1168,8 @@ __global__ __launch_bounds__(256) void schur_gamma_quad_kernel(uint32_t N, uint6
 //     knot k+1, entry r: f = x_{k+1}[r] - c_{k+1}[r];         f = fma(A_k(r,q), -x_k[q], f), q < nx;  f = fma(B_k(r,q), -u_k[q], f), q < nu
 // in both kernels below (the negation of a vector entry is exact), so the entries agree bit for bit, and the maximum of their
 // magnitudes is exact in any fold order: the two kernels give the same bits.
+// REG (gbdpcg_kkt_residual_reg_*): Q_k(r,r) and R_k(r,r) enter their chains as fl(d + rho_b), as the formation kernels take them:
+// the stationarity of the regularised system (G + rho I) z + g + C' lambda; the feasibility rows do not contain G.
 // The maximum runs over the BIT PATTERN of |entry| as an unsigned integer: that orders the non-negative numbers as they are
 // ordered, puts Inf above them and every NaN above Inf -- a NaN anywhere in a problem's residual is that problem's norm, where
 // an fmax would drop it.  ONE WORKGROUP PER PROBLEM walks the problem's rows; every lane keeps two running maxima in registers,
@@ -1212,10 +1240,11 @@ __host__ __device__ inline uint32_t residual_wave_elems(uint32_t nx, uint32_t nu
 
 // Any block size: one wavefront per row (problem, k), blocks staged in LDS; the waves of a workgroup share one problem's rows.
 // SHARED (gbdpcg_kkt_residual_shared_*): G and C are ONE problem's blocks, read with a zero problem stride.
-template <typename T, bool SHARED = false>
+template <typename T, bool SHARED = false, bool REG = false>
 __global__ __launch_bounds__(256) void schur_residual_kernel(uint32_t nx, uint32_t nu, uint32_t N, const T *__restrict__ G,
                                                              const T *__restrict__ C, const T *__restrict__ g, const T *__restrict__ c,
-                                                             const T *__restrict__ z, const T *__restrict__ lambda, T *__restrict__ res)
+                                                             const T *__restrict__ z, const T *__restrict__ lambda, T *__restrict__ res,
+                                                             const T *__restrict__ rho)   // [batch], REG only
 {
     using U = decltype(abs_bits(T(0)));
     static_assert(sizeof(U) == sizeof(T), "the maxima live in the wave's own LDS block");
@@ -1230,17 +1259,28 @@ __global__ __launch_bounds__(256) void schur_residual_kernel(uint32_t nx, uint32
     const T *Gp = G + mprob * d.szG, *Cp = C + mprob * d.szC;
     const T *gp = g + prob * d.szg, *zp = z + prob * d.szg, *lp = lambda + prob * d.szc, *cp = c + prob * d.szc;
 
+    T rb = T(0);
+    if constexpr (REG) rb = rho[prob];   // (the workgroup's problem: a scalar load)
+
     U ms = 0, mf = 0;
     for (uint32_t k = wave; k < N; k += waves) {   // (whole waves)
         const bool has_next = k + 1 < N;
         const T *Gk = Gp + (size_t)k * d.sg, *Ck = Cp + (size_t)k * d.sc, *gk = gp + (size_t)k * d.sv, *zk = zp + (size_t)k * d.sv;
         const T *lk = lp + (size_t)k * nx, *ck = cp + (size_t)k * nx;
         wave_sync();   // the previous row has read its blocks
-        for (uint32_t i = lane; i < nn; i += 64) Q[i] = Gk[i];
+        if constexpr (REG) {   // (entry i of a column-major m x m block is on the diagonal where i is a multiple of m + 1)
+            for (uint32_t i = lane; i < nn; i += 64) Q[i] = i % (nx + 1) == 0 ? Gk[i] + rb : Gk[i];
+        } else {
+            for (uint32_t i = lane; i < nn; i += 64) Q[i] = Gk[i];
+        }
         for (uint32_t i = lane; i < nx; i += 64) xk[i] = zk[i];
         if (has_next) {
             for (uint32_t i = lane; i < nn; i += 64) A[i] = Ck[i];
-            for (uint32_t i = lane; i < uu; i += 64) R[i] = Gk[nn + i];
+            if constexpr (REG) {
+                for (uint32_t i = lane; i < uu; i += 64) R[i] = i % (nu + 1) == 0 ? Gk[nn + i] + rb : Gk[nn + i];
+            } else {
+                for (uint32_t i = lane; i < uu; i += 64) R[i] = Gk[nn + i];
+            }
             for (uint32_t i = lane; i < xu; i += 64) B[i] = Ck[nn + i];
             for (uint32_t i = lane; i < nx; i += 64) nl[i] = -lk[nx + i];
             for (uint32_t i = lane; i < nu; i += 64) uk[i] = zk[nx + i];
@@ -1280,11 +1320,13 @@ __global__ __launch_bounds__(256) void schur_residual_kernel(uint32_t nx, uint32
 //   * every load of a pass is requested before its first fma, and nothing is computed under a partial exec mask: rows past
 //     the horizon and the products the last knot does not have run on zeros and add 0 to the maxima.
 // Lanes of a quarter that own no entry (l >= NX; l >= NU in the u-part) repeat lane 0's: a maximum does not mind.
-template <typename T, int NX, int NU, bool SHARED = false>
+// REG: the lane that holds row l adds rho_b to the l-th of its NX (NU) elements -- the index is the lane's, the registers are
+// static, so the add is a select per element on a kernel that waits for memory.
+template <typename T, int NX, int NU, bool SHARED = false, bool REG = false>
 __global__ __launch_bounds__(256) void schur_residual_quad_kernel(uint32_t N, const T *__restrict__ G, const T *__restrict__ C,
                                                                   const T *__restrict__ g, const T *__restrict__ c,
                                                                   const T *__restrict__ z, const T *__restrict__ lambda,
-                                                                  T *__restrict__ res)
+                                                                  T *__restrict__ res, const T *__restrict__ rho)
 {
     static_assert(NX <= 16 && NU <= NX, "one row per 16-lane quarter");
     using U = decltype(abs_bits(T(0)));
@@ -1297,6 +1339,8 @@ __global__ __launch_bounds__(256) void schur_residual_quad_kernel(uint32_t N, co
     const uint64_t mprob = SHARED ? 0 : prob;
     const T *Gp = G + mprob * d.szG, *Cp = C + mprob * d.szC;
     const T *gp = g + prob * d.szg, *zp = z + prob * d.szg, *lp = lambda + prob * d.szc, *cp = c + prob * d.szc;
+    T rb = T(0);
+    if constexpr (REG) rb = rho[prob];   // (the workgroup's problem: a scalar load)
 
     U ms = 0, mf = 0;
     for (uint32_t k0 = 0; k0 < N; k0 += 16) {   // (the whole workgroup)
@@ -1313,6 +1357,10 @@ __global__ __launch_bounds__(256) void schur_residual_quad_kernel(uint32_t N, co
             sx = gk[cx] + lk[cx];
 #pragma unroll
             for (int q = 0; q < NX; ++q) qr[q] = Gk[q * NX + cx];
+            if constexpr (REG) {
+#pragma unroll
+                for (int q = 0; q < NX; ++q) qr[q] = (uint32_t)q == cx ? qr[q] + rb : qr[q];
+            }
         } else {
 #pragma unroll
             for (int q = 0; q < NX; ++q) qr[q] = T(0);
@@ -1333,6 +1381,10 @@ __global__ __launch_bounds__(256) void schur_residual_quad_kernel(uint32_t N, co
             for (int q = 0; q < NU; ++q) {
                 rr[q] = Gk[NX * NX + q * NU + cu];
                 br[q] = Ck[NX * NX + q * NX + cx];
+            }
+            if constexpr (REG) {
+#pragma unroll
+                for (int q = 0; q < NU; ++q) rr[q] = (uint32_t)q == cu ? rr[q] + rb : rr[q];
             }
         } else {
 #pragma unroll
@@ -1367,9 +1419,9 @@ static uint32_t waves_for(const DeviceInfo &dev, size_t wave_bytes)
 #define GBDPCG_QUAD_SHAPES(X) X(2, 1) X(4, 1) X(4, 2) X(6, 3) X(8, 4) X(10, 5) X(12, 4) X(12, 6) X(13, 4) X(14, 7) \
     X(3, 1) X(5, 2) X(6, 1) X(6, 2) X(7, 3) X(8, 2) X(9, 3) X(10, 4) X(11, 4) X(12, 3)   /* round 3: under-actuated and odd shapes (9 / 3, 1024 x 128: formation 512 -> 95 us, recovery 95 -> 30 us) */
 
-template <typename T, int NX, int NU>
+template <typename T, int NX, int NU, bool REG = false>
 hipError_t launch_form_quad(const DeviceInfo &dev, uint32_t N, uint32_t batch, const T *G, const T *C, const T *g, const T *c, T *S,
-                            T *gamma, T *Ginv, hipStream_t s)
+                            T *gamma, T *Ginv, hipStream_t s, const T *rho = nullptr)
 {
     using Q = QuadGeom<T, NX, NU>;
     // one run per problem when the batch alone fills the device, shorter runs (each pays one silent step) otherwise
@@ -1382,25 +1434,29 @@ hipError_t launch_form_quad(const DeviceInfo &dev, uint32_t N, uint32_t batch, c
     const uint64_t nwaves = (uint64_t)batch * (N / run);
     if (nwaves > 0x7fffffffull) return hipErrorInvalidValue;
     const size_t lds = (size_t)Q::TOTAL * sizeof(T);
-    void (*kern)(uint32_t, uint32_t, uint32_t, const T *, const T *, const T *, const T *, T *, T *, T *) = schur_form_quad_kernel<T, NX, NU>;
-    if constexpr (Q::SINGLE && sizeof(T) == 4) kern = schur_form_quad2_kernel<NX, NU>;
+    void (*kern)(uint32_t, uint32_t, uint32_t, const T *, const T *, const T *, const T *, T *, T *, T *, const T *) =
+        schur_form_quad_kernel<T, NX, NU, REG>;
+    if constexpr (Q::SINGLE && sizeof(T) == 4) kern = schur_form_quad2_kernel<NX, NU, REG>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3((uint32_t)nwaves), dim3(64), lds, s, N, run, (uint32_t)nwaves, G, C, g, c, S, gamma, Ginv);
+    hipLaunchKernelGGL(kern, dim3((uint32_t)nwaves), dim3(64), lds, s, N, run, (uint32_t)nwaves, G, C, g, c, S, gamma, Ginv, rho);
     return hipGetLastError();
 }
 
+// rho != nullptr: the REG instantiations (G_b + rho_b I); the same launch geometry either way.
 template <typename T>
 hipError_t launch_form_schur(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *G, const T *C,
-                             const T *g, const T *c, T *S, T *gamma, T *Ginv, hipStream_t s)
+                             const T *g, const T *c, T *S, T *gamma, T *Ginv, hipStream_t s, const T *rho)
 {
     // GBDPCG_SCHUR_GENERAL=1: the any-size kernel also where the four-knots-per-wave form exists (A/B runs, tests)
     const char *env = getenv("GBDPCG_SCHUR_GENERAL");
     if (!(env && env[0] == '1')) {
-#define GBDPCG_X(NX, NU) \
-    if (nx == NX && nu == NU) return launch_form_quad<T, NX, NU>(dev, N, batch, G, C, g, c, S, gamma, Ginv, s);
+#define GBDPCG_X(NX, NU)                                                                                                      \
+    if (nx == NX && nu == NU)                                                                                                 \
+        return rho ? launch_form_quad<T, NX, NU, true>(dev, N, batch, G, C, g, c, S, gamma, Ginv, s, rho)                      \
+                   : launch_form_quad<T, NX, NU>(dev, N, batch, G, C, g, c, S, gamma, Ginv, s);
         GBDPCG_QUAD_SHAPES(GBDPCG_X)
 #undef GBDPCG_X
     }
@@ -1411,12 +1467,12 @@ hipError_t launch_form_schur(const DeviceInfo &dev, uint32_t nx, uint32_t nu, ui
     const uint64_t grid = (rows + waves - 1) / waves;
     if (grid > 0x7fffffffull) return hipErrorInvalidValue;
     const size_t lds = waves * wave_bytes;
-    auto kern = schur_form_kernel<T>;
+    auto kern = rho ? schur_form_kernel<T, true> : schur_form_kernel<T>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(64 * waves), lds, s, nx, nu, N, rows, G, C, g, c, S, gamma, Ginv);
+    hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(64 * waves), lds, s, nx, nu, N, rows, G, C, g, c, S, gamma, Ginv, rho);
     return hipGetLastError();
 }
 
@@ -1494,18 +1550,21 @@ hipError_t launch_form_gamma(const DeviceInfo &dev, uint32_t nx, uint32_t nu, ui
 
 template <typename T>
 hipError_t launch_kkt_residual(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *G, const T *C,
-                               const T *g, const T *c, const T *z, const T *lambda, T *res, hipStream_t s, bool shared)
+                               const T *g, const T *c, const T *z, const T *lambda, T *res, hipStream_t s, bool shared, const T *rho)
 {
     if (batch > 0x7fffffffu) return hipErrorInvalidValue;   // one workgroup per problem
+    if (shared && rho) return hipErrorInvalidValue;         // (there is no shared twin of the REG form)
     // GBDPCG_SCHUR_GENERAL=1: the any-size kernel also where the four-rows-per-wave form exists (A/B runs, tests)
     const char *env = getenv("GBDPCG_SCHUR_GENERAL");
     if (!(env && env[0] == '1')) {
 #define GBDPCG_X(NX, NU)                                                                                                              \
     if (nx == NX && nu == NU) {                                                                                                       \
-        if (shared)                                                                                                                   \
-            hipLaunchKernelGGL((schur_residual_quad_kernel<T, NX, NU, true>), dim3(batch), dim3(256), 0, s, N, G, C, g, c, z, lambda, res); \
+        if (rho)                                                                                                                      \
+            hipLaunchKernelGGL((schur_residual_quad_kernel<T, NX, NU, false, true>), dim3(batch), dim3(256), 0, s, N, G, C, g, c, z, lambda, res, rho); \
+        else if (shared)                                                                                                              \
+            hipLaunchKernelGGL((schur_residual_quad_kernel<T, NX, NU, true>), dim3(batch), dim3(256), 0, s, N, G, C, g, c, z, lambda, res, rho); \
         else                                                                                                                          \
-            hipLaunchKernelGGL((schur_residual_quad_kernel<T, NX, NU>), dim3(batch), dim3(256), 0, s, N, G, C, g, c, z, lambda, res); \
+            hipLaunchKernelGGL((schur_residual_quad_kernel<T, NX, NU>), dim3(batch), dim3(256), 0, s, N, G, C, g, c, z, lambda, res, rho); \
         return hipGetLastError();                                                                                                     \
     }
         GBDPCG_QUAD_SHAPES(GBDPCG_X)
@@ -1515,12 +1574,12 @@ hipError_t launch_kkt_residual(const DeviceInfo &dev, uint32_t nx, uint32_t nu, 
     const uint32_t waves = waves_for(dev, wave_bytes);
     if (!waves) return hipErrorInvalidValue;
     const size_t lds = waves * wave_bytes;
-    auto kern = shared ? schur_residual_kernel<T, true> : schur_residual_kernel<T>;
+    auto kern = rho ? schur_residual_kernel<T, false, true> : shared ? schur_residual_kernel<T, true> : schur_residual_kernel<T>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(batch), dim3(64 * waves), lds, s, nx, nu, N, G, C, g, c, z, lambda, res);
+    hipLaunchKernelGGL(kern, dim3(batch), dim3(64 * waves), lds, s, nx, nu, N, G, C, g, c, z, lambda, res, rho);
     return hipGetLastError();
 }
 
@@ -1530,9 +1589,9 @@ template <typename T> bool schur_shape_ok(const DeviceInfo &dev, uint32_t nx, ui
 }
 
 template hipError_t launch_form_schur<float>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const float *, const float *,
-                                             const float *, const float *, float *, float *, float *, hipStream_t);
+                                             const float *, const float *, float *, float *, float *, hipStream_t, const float *);
 template hipError_t launch_form_schur<double>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const double *, const double *,
-                                              const double *, const double *, double *, double *, double *, hipStream_t);
+                                              const double *, const double *, double *, double *, double *, hipStream_t, const double *);
 template hipError_t launch_recover_primal<float>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const float *,
                                                  const float *, const float *, const float *, float *, hipStream_t, bool);
 template hipError_t launch_recover_primal<double>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const double *,
@@ -1542,10 +1601,11 @@ template hipError_t launch_form_gamma<float>(const DeviceInfo &, uint32_t, uint3
 template hipError_t launch_form_gamma<double>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const double *,
                                               const double *, const double *, const double *, double *, hipStream_t, bool);
 template hipError_t launch_kkt_residual<float>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const float *, const float *,
-                                               const float *, const float *, const float *, const float *, float *, hipStream_t, bool);
+                                               const float *, const float *, const float *, const float *, float *, hipStream_t, bool,
+                                               const float *);
 template hipError_t launch_kkt_residual<double>(const DeviceInfo &, uint32_t, uint32_t, uint32_t, uint32_t, const double *,
                                                 const double *, const double *, const double *, const double *, const double *,
-                                                double *, hipStream_t, bool);
+                                                double *, hipStream_t, bool, const double *);
 template bool schur_shape_ok<float>(const DeviceInfo &, uint32_t, uint32_t);
 template bool schur_shape_ok<double>(const DeviceInfo &, uint32_t, uint32_t);
 

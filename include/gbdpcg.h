@@ -307,7 +307,8 @@ gbdpcg_status gbdpcg_graph_create_form_pinv_solve_f64(gbdpcg_handle_t h, uint32_
  *     S lambda = gamma,  S = C G^-1 C',  gamma = -(c + C G^-1 g),      z = -G^-1 (g + C' lambda)
  * with D_0 = Q_0^-1, D_k = A_j Q_j^-1 A_j' + B_j R_j^-1 B_j' + Q_k^-1 (j = k-1), L_k = -A_j Q_j^-1, R_k = L_{k+1}'.
  * Packed device arrays, one problem after the other, every block column-major (nx = stateSize, nu = controlSize):
- *     d_G    [Q_0 R_0 Q_1 R_1 ... Q_{N-1}]   (nx^2+nu^2) N - nu^2     cost Hessians, symmetric positive definite
+ *     d_G    [Q_0 R_0 Q_1 R_1 ... Q_{N-1}]   (nx^2+nu^2) N - nu^2     cost Hessians, symmetric; positive definite for the calls
+ *                                                                     below, G + rho I positive definite for the _reg calls
  *     d_C    [A_0 B_0 A_1 B_1 ... B_{N-2}]   (nx^2+nx nu)(N-1)        dynamics Jacobians (A: nx x nx, B: nx x nu)
  *     d_g    [q_0 r_0 q_1 r_1 ... q_{N-1}]   (nx+nu) N - nu           cost gradients; d_z has this layout too
  *     d_c    [c_0 ... c_{N-1}]               nx N                     constraint residuals
@@ -507,6 +508,68 @@ gbdpcg_status gbdpcg_kkt_residual_shared_f32(gbdpcg_handle_t h, uint32_t nx, uin
 gbdpcg_status gbdpcg_kkt_residual_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
                                              const double *d_G, const double *d_C, const double *d_g, const double *d_c,
                                              const double *d_z, const double *d_lambda, double *d_res, void *stream);
+
+/* Per-problem regularisation: problem b is solved with G_b + rho_b I in place of G_b -- costs that are only positive SEMI-definite
+ * (a tracking cost on part of the state, an unpenalised input: the plain calls divide by a zero pivot and return Inf / NaN), the
+ * damping of a rejected SQP step, decided per problem, and the matrix a splitting method on a frozen factorisation needs.
+ * Each entry point takes the argument list of the one it extends with `d_rho` directly after `d_c`:
+ *     d_rho  [batch] elements in the call's precision, on the device; read when the kernel RUNS, not when the call is made
+ * Wherever a kernel picks up Q_k or R_k of problem b, every diagonal entry d is replaced by fl(d + rho_b) -- one rounding in the
+ * call's precision, done on chip: d_G is not modified, no second buffer, no extra launch -- and everything downstream is the
+ * arithmetic of the call without _reg.  So:
+ *  - d_Ginv holds the blocks of (G + rho I)^-1, S = C (G + rho I)^-1 C', gamma = -(c + C (G + rho I)^-1 g).
+ *  - gbdpcg_form_gamma_*, gbdpcg_recover_primal_*, gbdpcg_kkt_resolve_* and their shared twins need no _reg form: they work on
+ *    that d_Ginv (and S, Phi^-1) as they are and give the regularised gamma and step.
+ *  - rho_b is NOT validated on the device: negative values, NaN or Inf are added as they are, the outputs of that problem are
+ *    whatever the arithmetic gives, and the other problems of the batch are unaffected.
+ *  - with rho_b = 0 for every b each output is bit-identical with the entry point without _reg (d + 0 is exact).
+ *  - S stays exactly symmetric in storage (L_{k+1} == R_k' bit for bit: both uses of a block see the same sum), so the default
+ *    symmetric mode takes its resident kernels as it does behind gbdpcg_form_schur_*.
+ * gbdpcg_kkt_step_reg_* is gbdpcg_form_schur_reg_* + gbdpcg_form_pinv_solve_* + gbdpcg_recover_primal_*, same results bit for bit.
+ * The graph of gbdpcg_graph_create_kkt_step_reg_* keeps the POINTER d_rho: rewrite rho in place between replays, from the host or
+ * from a kernel on the same stream (the outer loop's accept / reject decision) -- no re-capture.
+ * gbdpcg_kkt_residual_reg_*: d_res[2b] = || (G + rho I) z + g + C' lambda ||_inf, the stationarity of the REGULARISED system
+ * ("did the regularised step solve what it was asked to"; gbdpcg_kkt_residual_* answers the same for the original system), and
+ * the unchanged feasibility norm in d_res[2b+1]; the same NaN-propagating maximum, the same determinism, one capturable launch.
+ * There is no shared-matrix twin of it (the shared matrices themselves come from gbdpcg_form_schur_reg_* with batch = 1; the
+ * regularised stationarity of a shared batch is gbdpcg_kkt_residual_shared_* on a G that holds G + rho I).
+ * d_rho == NULL: GBDPCG_ERR_INVALID, nothing is written; every other error rule is the one of the function extended. */
+gbdpcg_status gbdpcg_form_schur_reg_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                        const float *d_G, const float *d_C, const float *d_g, const float *d_c,
+                                        const float *d_rho, float *d_S, float *d_gamma, float *d_Ginv, void *stream);
+gbdpcg_status gbdpcg_form_schur_reg_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                        const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                        const double *d_rho, double *d_S, double *d_gamma, double *d_Ginv, void *stream);
+gbdpcg_status gbdpcg_kkt_step_reg_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_G,
+                                      const float *d_C, const float *d_g, const float *d_c, const float *d_rho, float *d_S,
+                                      float *d_gamma, float *d_Ginv, float *d_Pinv, gbdpcg_pinv_kind kind, float *d_lambda,
+                                      float *d_r, float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                      uint8_t *d_max_iter_exit, float *d_z, void *stream);
+gbdpcg_status gbdpcg_kkt_step_reg_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_G,
+                                      const double *d_C, const double *d_g, const double *d_c, const double *d_rho, double *d_S,
+                                      double *d_gamma, double *d_Ginv, double *d_Pinv, gbdpcg_pinv_kind kind, double *d_lambda,
+                                      double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                      uint8_t *d_max_iter_exit, double *d_z, void *stream);
+gbdpcg_status gbdpcg_graph_create_kkt_step_reg_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                   const float *d_G, const float *d_C, const float *d_g, const float *d_c,
+                                                   const float *d_rho, float *d_S, float *d_gamma, float *d_Ginv, float *d_Pinv,
+                                                   gbdpcg_pinv_kind kind, float *d_lambda, float *d_r, float *d_p, float tol,
+                                                   uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_z,
+                                                   gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_kkt_step_reg_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                   const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                                   const double *d_rho, double *d_S, double *d_gamma, double *d_Ginv,
+                                                   double *d_Pinv, gbdpcg_pinv_kind kind, double *d_lambda, double *d_r,
+                                                   double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                   uint8_t *d_max_iter_exit, double *d_z, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_kkt_residual_reg_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                          const float *d_G, const float *d_C, const float *d_g, const float *d_c,
+                                          const float *d_rho, const float *d_z, const float *d_lambda, float *d_res,
+                                          void *stream);
+gbdpcg_status gbdpcg_kkt_residual_reg_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                          const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                          const double *d_rho, const double *d_z, const double *d_lambda, double *d_res,
+                                          void *stream);
 
 /* CSR ingestion (f3): repacks a host CSR matrix (csr_t<T>, include/types.cuh:7-15) whose
  * sparsity lies inside the block-tridiagonal pattern into the [L|D|R] layout (host arrays).
