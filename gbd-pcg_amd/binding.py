@@ -43,6 +43,10 @@ SYMBOLS = [
     "gbdpcg_form_schur_reg_f32", "gbdpcg_form_schur_reg_f64", "gbdpcg_kkt_step_reg_f32", "gbdpcg_kkt_step_reg_f64",
     "gbdpcg_graph_create_kkt_step_reg_f32", "gbdpcg_graph_create_kkt_step_reg_f64",
     "gbdpcg_kkt_residual_reg_f32", "gbdpcg_kkt_residual_reg_f64",
+    "gbdpcg_admm_init_f32", "gbdpcg_admm_init_f64", "gbdpcg_admm_update_f32", "gbdpcg_admm_update_f64",
+    "gbdpcg_admm_step_f32", "gbdpcg_admm_step_f64", "gbdpcg_graph_create_admm_step_f32", "gbdpcg_graph_create_admm_step_f64",
+    "gbdpcg_admm_step_shared_f32", "gbdpcg_admm_step_shared_f64",
+    "gbdpcg_graph_create_admm_step_shared_f32", "gbdpcg_graph_create_admm_step_shared_f64",
     "gbdpcg_csr_to_bt_f32", "gbdpcg_csr_to_bt_f64", "gbdpcg_version",
 ]
 
@@ -73,6 +77,14 @@ def _resolve_argtypes(lib):
         getattr(lib, f"gbdpcg_kkt_step_reg_{suf}").argtypes = head + [vp] + step + [vp]
         getattr(lib, f"gbdpcg_graph_create_kkt_step_reg_{suf}").argtypes = head + [vp] + step + [ctypes.POINTER(vp)]
         getattr(lib, f"gbdpcg_kkt_residual_reg_{suf}").argtypes = head + [vp] + [vp, vp, vp, vp]   # rho | z, lambda, res, stream
+        # box-constrained ADMM on a kept factorisation: h, nx, nu, N, batch | g, lo, hi, rho | ...
+        sizes = [vp, u32, u32, u32, u32]
+        getattr(lib, f"gbdpcg_admm_init_{suf}").argtypes = sizes + [vp, vp, vp, vp] + [vp, vp, vp, vp]           # w, y, gt, stream
+        getattr(lib, f"gbdpcg_admm_update_{suf}").argtypes = sizes + [vp, vp, vp, vp] + [vp, vp, vp, vp, vp, vp]   # z, w, y, gt, res, stream
+        # Ginv, C, g, c | lo, hi, rho | the solve's arguments | w, y, gt, res | stream / graph out
+        for name in ("admm_step", "admm_step_shared"):
+            getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = head + [vp, vp, vp] + solve + [vp, vp, vp, vp] + [vp]
+            getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = head + [vp, vp, vp] + solve + [vp, vp, vp, vp] + [ctypes.POINTER(vp)]
 
 _lib = None
 
@@ -538,6 +550,96 @@ class Solver:
         self._check(fn(self.h, nx, nu, N, batch, _p(G), _p(C), _p(g), _p(c), _p(self._rho(rho, batch, G)), _p(z), _p(lam), _p(res),
                        self._stream(stream)), "kkt_residual_reg")
         return res.view(batch, 2)
+
+    # ---- box constraints on a kept factorisation: ADMM iterations around kkt_resolve (include/gbdpcg.h).  lo, hi, w, y, gt have the
+    # layout of g; rho is a device tensor [batch]; the matrices are those kkt_step_reg / form_schur_reg wrote with that rho
+    def _box(self, g, batch, *tensors):
+        for t in tensors:
+            assert t is not None and t.is_cuda and t.is_contiguous() and t.numel() == g.numel() and t.dtype == g.dtype
+        return tensors
+
+    def admm_init(self, nx, nu, N, batch, g, lo, hi, rho, w, y, gt=None, stream=None):
+        """gbdpcg_admm_init_*: w <- clip(w, lo, hi), gt <- g - rho (w - y); y is left alone.  Returns gt."""
+        import torch
+        suf, _ = _suffix(g)
+        if gt is None:
+            gt = torch.empty_like(g)
+        self._box(g, batch, lo, hi, w, y, gt)
+        fn = getattr(self.lib, f"gbdpcg_admm_init_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(g), _p(lo), _p(hi), _p(self._rho(rho, batch, g)), _p(w), _p(y), _p(gt),
+                       self._stream(stream)), "admm_init")
+        return gt
+
+    def admm_update(self, nx, nu, N, batch, g, lo, hi, rho, z, w, y, gt, res=None, stream=None):
+        """gbdpcg_admm_update_*: the update behind a solve that wrote z -- w, y, gt in place; returns the [batch, 2] tensor of
+        (||z - w||_inf, rho ||w - w_old||_inf) per problem."""
+        import torch
+        suf, _ = _suffix(g)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=g.dtype, device=g.device)
+        assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == g.dtype
+        self._box(g, batch, lo, hi, z, w, y, gt)
+        fn = getattr(self.lib, f"gbdpcg_admm_update_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(g), _p(lo), _p(hi), _p(self._rho(rho, batch, g)), _p(z), _p(w), _p(y), _p(gt),
+                       _p(res), self._stream(stream)), "admm_update")
+        return res.view(batch, 2)
+
+    def _admm_args(self, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters, mie, z, w, y,
+                   gt, res):
+        suf, _ = _suffix(g)
+        assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == g.dtype
+        self._box(g, batch, lo, hi, z, w, y, gt)
+        return suf, (self.h, nx, nu, N, batch, _p(Ginv), _p(C), _p(g), _p(c), _p(lo), _p(hi), _p(self._rho(rho, batch, g)), _p(S),
+                     _p(Pinv), _p(gamma), _p(lam), _p(r), _p(p), tol, max_iter, _p(iters), _p(mie), _p(z), _p(w), _p(y), _p(gt), _p(res))
+
+    def _admm_step(self, name, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, r, p, tol,
+                   max_iter, iters, max_iter_exit, stream):
+        import torch
+        if iters is None:
+            iters = torch.zeros(batch, dtype=torch.int32, device=g.device)
+        if max_iter_exit is None:
+            max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=g.device)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=g.dtype, device=g.device)
+        suf, args = self._admm_args(nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                                    max_iter_exit, z, w, y, gt, res)
+        self._check(getattr(self.lib, f"gbdpcg_{name}_{suf}")(*args, self._stream(stream)), name)
+        return iters, max_iter_exit, res.view(batch, 2)
+
+    def _graph_admm_step(self, name, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                         max_iter_exit, z, w, y, gt, res):
+        suf, args = self._admm_args(nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                                    max_iter_exit, z, w, y, gt, res)
+        gr = ctypes.c_void_p()
+        self._check(getattr(self.lib, f"gbdpcg_graph_create_{name}_{suf}")(*args, ctypes.byref(gr)), f"graph_create_{name}")
+        return Graph(self, gr, keep=(Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, iters, max_iter_exit, z, w, y, gt, res))
+
+    def admm_step(self, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=None, r=None, p=None,
+                  tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_admm_step_*: kkt_resolve with gt in the place of g (warm start from lam), then admm_update, one call.
+        Returns (iters, flags, res [batch, 2])."""
+        return self._admm_step("admm_step", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, r, p,
+                               tol, max_iter, iters, max_iter_exit, stream)
+
+    def graph_admm_step(self, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                        max_iter_exit, z, w, y, gt, res):
+        """Capture one ADMM iteration into a hipGraph (gbdpcg_graph_create_admm_step_*): replay it once per iteration; the graph
+        keeps rho's pointer."""
+        return self._graph_admm_step("admm_step", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                     max_iter, iters, max_iter_exit, z, w, y, gt, res)
+
+    def admm_step_shared(self, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=None, r=None,
+                         p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_admm_step_shared_*: ONE Ginv, C, S, Pinv for `batch` problems; box, rho and the state stay per problem."""
+        return self._admm_step("admm_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res,
+                               r, p, tol, max_iter, iters, max_iter_exit, stream)
+
+    def graph_admm_step_shared(self, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                               max_iter_exit, z, w, y, gt, res):
+        """Capture the shared-matrix iteration into a hipGraph (gbdpcg_graph_create_admm_step_shared_*)."""
+        return self._graph_admm_step("admm_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                     max_iter, iters, max_iter_exit, z, w, y, gt, res)
+
 
 
 class Graph:

@@ -1,0 +1,147 @@
+// admm.hip -- the splitting update of box-constrained ADMM on a kept KKT factorisation (gbdpcg_admm_init_*, gbdpcg_admm_update_*,
+// the third launch of gbdpcg_admm_step_*).  Problem b minimises 1/2 z'Gz + g'z subject to Cz = c and lo <= z <= hi; the matrices
+// of the solve belong to G + rho_b I (gbdpcg_form_schur_reg_*), w is the copy of z that lives in the box, y the scaled multiplier
+// of z = w (mu = rho y).  After the solve with the gradient gt has written z, per element, every line ONE IEEE operation or a
+// comparison, so w, y and the norms are defined to the bit whatever the launch shape:
+//     v   = z + y
+//     w+  = v < lo ? lo : (v > hi ? hi : v)          comparisons: a NaN v stays NaN, +-Inf bounds never bind
+//     y+  = v - w+                                   exactly 0 where nothing was clipped
+//     t   = w+ - y+
+//     gt+ = fma(-rho, t, g)                          ONE rounding: the build runs with -ffp-contract=off, the fma is written out
+//     res[2b]   = max |z - w+|                       primal residual ||z - w||_inf
+//     res[2b+1] = max |rho (w+ - w)|                 dual residual rho ||w+ - w||_inf
+// INIT (gbdpcg_admm_init_*): w <- clip(w), y unchanged (not written), gt = fma(-rho, w - y, g); z and res are not looked at.
+// The maxima are those of the KKT residual norms (norm_fold.hpp): over the bit pattern of |entry|, exact in any order, NaN on top.
+//
+// Shape: ONE WORKGROUP PER PROBLEM (the two norms are per problem: nothing crosses a workgroup, no atomics, no memset, nothing
+// read from res), one wave when nz <= 256, otherwise four.  9 element accesses per element of z (6 reads, 3 writes; INIT: 5 + 2),
+// rho_b once per workgroup through the scalar cache, two numbers out per problem.  All seven arrays are indexed at the same
+// offset b nz, so they are misaligned alike: when every base pointer is 16-byte aligned (vec != 0, decided by the host) the
+// workgroup peels a scalar head of (-b nz) mod (16 / sizeof T) elements, runs the body with 16-byte loads and stores and finishes
+// with a scalar tail; otherwise every element goes through the scalar form.  Same operations per element either way: same bits.
+// Default cache policy throughout: z was written by the recovery kernel just before, gt is read by the gamma kernel next.
+#include "internal.hpp"
+#include "norm_fold.hpp"
+
+namespace gbdpcg {
+
+namespace {
+
+template <typename T> struct AdmmVec;
+template <> struct AdmmVec<float> {
+    static constexpr uint32_t N = 4;
+    typedef float type __attribute__((ext_vector_type(4)));
+};
+template <> struct AdmmVec<double> {
+    static constexpr uint32_t N = 2;
+    typedef double type __attribute__((ext_vector_type(2)));
+};
+
+__device__ __forceinline__ float fma_once(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_once(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+template <typename T> __device__ __forceinline__ T clip(T v, T lo, T hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// One element.  w, y: in / out (INIT leaves y alone); mp, md: the running maxima of the two norms (not INIT).
+template <typename T, bool INIT, typename U>
+__device__ __forceinline__ T admm_element(T z, T &w, T &y, T lo, T hi, T g, T rho, U &mp, U &md)
+{
+    if constexpr (INIT) {
+        w = clip(w, lo, hi);
+        const T t = w - y;
+        return fma_once(-rho, t, g);
+    } else {
+        const T v = z + y;
+        const T wn = clip(v, lo, hi);
+        const T yn = v - wn;
+        const T t = wn - yn;
+        mp = umax(mp, abs_bits(z - wn));
+        md = umax(md, abs_bits(rho * (wn - w)));
+        w = wn;
+        y = yn;
+        return fma_once(-rho, t, g);
+    }
+}
+
+}  // namespace
+
+template <typename T, bool INIT>
+__global__ __launch_bounds__(256) void admm_update_kernel(uint64_t nz, uint32_t vec, const T *__restrict__ g, const T *__restrict__ lo,
+                                                          const T *__restrict__ hi, const T *__restrict__ rho, const T *__restrict__ z,
+                                                          T *__restrict__ w, T *__restrict__ y, T *__restrict__ gt, T *__restrict__ res)
+{
+    using U = decltype(abs_bits(T(0)));
+    using V = typename AdmmVec<T>::type;
+    constexpr uint32_t VN = AdmmVec<T>::N;
+    __shared__ U slots[8];   // two words per wave
+    const uint32_t prob = blockIdx.x, tid = threadIdx.x, threads = blockDim.x;
+    const uint64_t off = (uint64_t)prob * nz;   // 64-bit problem stride
+    g += off, lo += off, hi += off, w += off, y += off, gt += off;
+    if constexpr (!INIT) z += off;
+    const T r = rho[prob];
+    U mp = 0, md = 0;
+
+    auto scalar = [&](uint64_t i) {
+        T wi = w[i], yi = y[i];
+        const T zi = INIT ? T(0) : z[i];
+        gt[i] = admm_element<T, INIT>(zi, wi, yi, lo[i], hi[i], g[i], r, mp, md);
+        w[i] = wi;
+        if constexpr (!INIT) y[i] = yi;
+    };
+
+    uint64_t head = 0, body = 0;   // elements in front of the first 16-byte boundary, 16-byte groups behind it
+    if (vec) {
+        head = (VN - (uint32_t)(off % VN)) % VN;
+        if (head > nz) head = nz;
+        body = (nz - head) / VN;
+    }
+    if (tid < head) scalar(tid);
+    for (uint64_t q = tid; q < body; q += threads) {
+        const uint64_t i = head + q * VN;
+        V wv = *reinterpret_cast<const V *>(w + i), yv = *reinterpret_cast<const V *>(y + i);
+        const V lv = *reinterpret_cast<const V *>(lo + i), hv = *reinterpret_cast<const V *>(hi + i);
+        const V gv = *reinterpret_cast<const V *>(g + i);
+        V zv = {};
+        if constexpr (!INIT) zv = *reinterpret_cast<const V *>(z + i);
+        V tv;
+#pragma unroll
+        for (uint32_t e = 0; e < VN; ++e) {
+            T we = wv[e], ye = yv[e];
+            tv[e] = admm_element<T, INIT>(zv[e], we, ye, lv[e], hv[e], gv[e], r, mp, md);
+            wv[e] = we;
+            yv[e] = ye;
+        }
+        *reinterpret_cast<V *>(w + i) = wv;
+        if constexpr (!INIT) *reinterpret_cast<V *>(y + i) = yv;
+        *reinterpret_cast<V *>(gt + i) = tv;
+    }
+    for (uint64_t i = head + body * VN + tid; i < nz; i += threads) scalar(i);   // the tail; all of it without vec
+
+    if constexpr (!INIT)
+        store_norms(mp, md, tid >> 6, tid & 63u, threads >> 6, [&](uint32_t wv) { return slots + 2 * wv; }, res + 2 * (uint64_t)prob);
+}
+
+template <typename T>
+hipError_t launch_admm_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *g, const T *lo, const T *hi, const T *rho,
+                              const T *z, T *w, T *y, T *gt, T *res, hipStream_t s, bool init)
+{
+    if (batch > 0x7fffffffu) return hipErrorInvalidValue;   // one workgroup per problem
+    const uint64_t nz = ((uint64_t)nx + nu) * N - nu;
+    const void *ptrs[] = {g, lo, hi, w, y, gt, init ? (const void *)g : (const void *)z};
+    uint32_t vec = 1;
+    for (const void *p : ptrs)
+        if (reinterpret_cast<uintptr_t>(p) % 16) vec = 0;
+    const uint32_t threads = nz <= 256 ? 64 : 256;
+    if (init)
+        hipLaunchKernelGGL((admm_update_kernel<T, true>), dim3(batch), dim3(threads), 0, s, nz, vec, g, lo, hi, rho, z, w, y, gt, res);
+    else
+        hipLaunchKernelGGL((admm_update_kernel<T, false>), dim3(batch), dim3(threads), 0, s, nz, vec, g, lo, hi, rho, z, w, y, gt, res);
+    return hipGetLastError();
+}
+
+template hipError_t launch_admm_update<float>(uint32_t, uint32_t, uint32_t, uint32_t, const float *, const float *, const float *,
+                                              const float *, const float *, float *, float *, float *, float *, hipStream_t, bool);
+template hipError_t launch_admm_update<double>(uint32_t, uint32_t, uint32_t, uint32_t, const double *, const double *, const double *,
+                                               const double *, const double *, double *, double *, double *, double *, hipStream_t, bool);
+
+}  // namespace gbdpcg

@@ -555,6 +555,12 @@ gbdpcg_status form_gamma_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint3
                               const T *d_g, const T *d_c, T *d_gamma, void *stream, bool shared = false);
 // (shared: d_Ginv and d_C are one problem's blocks, used by every problem of the batch)
 
+// The box and the splitting state of gbdpcg_admm_step_*: every array has the layout of g, rho [batch], res [2 batch].
+template <typename T> struct AdmmOperands {
+    const T *lo, *hi, *rho;
+    T *w, *y, *gt, *res;
+};
+
 // The operands of the steps either side of the solve (gbdpcg_kkt_step_*): S and gamma are formed from them before, z after.
 template <typename T> struct KktOperands {
     uint32_t nu;
@@ -564,6 +570,7 @@ template <typename T> struct KktOperands {
     bool shared = false;    // gbdpcg_kkt_resolve_shared_*: Ginv, C, S and Pinv are ONE problem's, used by every problem of the batch
     const T *rho = nullptr; // gbdpcg_kkt_step_reg_*: [batch] on the device, read by the formation kernel when it runs
     bool reg = false;       // ... and the step is that of G_b + rho_b I (rho is then required)
+    const AdmmOperands<T> *admm = nullptr;   // gbdpcg_admm_step_* (with resolve): the solve takes admm->gt for g, the update follows
 };
 
 // KKT blocks -> S, gamma, G^-1 -> Phi^-1 -> PCG -> primal step, on one stream (capturable: no allocation after the first
@@ -623,6 +630,40 @@ gbdpcg_status kkt_resolve_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint
     return recover_primal_impl<T>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_lambda, d_z, stream, shared);
 }
 
+// The splitting update (admm.hip), one launch.  init: gbdpcg_admm_init_* -- d_z and d_res are not arguments.  No shape is refused:
+// the kernel is elementwise over the layout of g.
+template <typename T>
+gbdpcg_status admm_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_g, const T *d_lo,
+                               const T *d_hi, const T *d_rho, const T *d_z, T *d_w, T *d_y, T *d_gt, T *d_res, void *stream, bool init)
+{
+    if (!h || !d_g || !d_lo || !d_hi || !d_rho || !d_w || !d_y || !d_gt || (!init && (!d_z || !d_res)) || nx == 0 || nu == 0 ||
+        N == 0 || batch == 0)
+        return GBDPCG_ERR_INVALID;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_admm_update<T>(nx, nu, N, batch, d_g, d_lo, d_hi, d_rho, d_z, d_w, d_y, d_gt, d_res, (hipStream_t)stream, init));
+    return GBDPCG_OK;
+}
+
+// One iteration of box-constrained ADMM on a kept factorisation of G + rho I: kkt_resolve_impl with the shifted gradient a.gt in
+// the place of g (the gamma launch and the recovery launch read the same gt), then the update, which alone reads g, on the same
+// stream.  What either part would refuse for its arguments or the shape is refused here, before anything is written.
+template <typename T>
+gbdpcg_status admm_step_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv, const T *d_C,
+                             const T *d_g, const T *d_c, const AdmmOperands<T> &a, const T *d_S, const T *d_Pinv, T *d_gamma,
+                             T *d_lambda, T *d_r, T *d_p, T tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_exit, T *d_z,
+                             hipStream_t stream, bool shared = false)
+{
+    if (!h || !d_Ginv || !d_g || !d_c || !a.lo || !a.hi || !a.rho || !d_S || !d_gamma || !d_lambda || !d_iters || !d_z || !a.w ||
+        !a.y || !a.gt || !a.res || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))
+        return GBDPCG_ERR_INVALID;
+    if (!schur_shape_ok<T>(h->dev, nx, nu) || !mappable<T>(nx) || (shared && !fused_fits<T>(h->dev, nx, N)))
+        return GBDPCG_ERR_UNSUPPORTED;
+    const gbdpcg_status st = kkt_resolve_impl<T>(h, nx, nu, N, batch, d_Ginv, d_C, a.gt, d_c, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p,
+                                                 tol, max_iter, d_iters, d_exit, d_z, stream, shared);
+    if (st != GBDPCG_OK) return st;
+    return admm_update_impl<T>(h, nx, nu, N, batch, d_g, a.lo, a.hi, a.rho, d_z, a.w, a.y, a.gt, a.res, stream, false);
+}
+
 template <typename T>
 gbdpcg_status graph_create_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batch, const T *d_S,
                                 const T *d_Pinv, const T *d_gamma, T *d_lambda, T *d_r, T *d_p, T tol,
@@ -670,7 +711,10 @@ gbdpcg_status graph_create_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint3
     hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
     gbdpcg_status st = GBDPCG_OK;
     if (e == hipSuccess) {
-        if (kkt && kkt->resolve)
+        if (kkt && kkt->resolve && kkt->admm)
+            st = admm_step_impl<T>(h, n, kkt->nu, N, batch, kkt->Ginv, kkt->C, kkt->g, kkt->c, *kkt->admm, d_S, d_Pinv,
+                                   const_cast<T *>(d_gamma), d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, kkt->z, cs, kkt->shared);
+        else if (kkt && kkt->resolve)
             st = kkt_resolve_impl<T>(h, n, kkt->nu, N, batch, kkt->Ginv, kkt->C, kkt->g, kkt->c, d_S, d_Pinv, const_cast<T *>(d_gamma),
                                      d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, kkt->z, cs, kkt->shared);
         else if (kkt)
@@ -1341,6 +1385,60 @@ GBDPCG_KKT_RESIDUAL(f64, double)
 GBDPCG_REG(f32, float)
 GBDPCG_REG(f64, double)
 #undef GBDPCG_REG
+
+// ---- box constraints on a kept factorisation: ADMM iterations whose solve is gbdpcg_kkt_resolve_* on the matrices of G + rho I.
+// SHARED: the twin on one problem's Ginv, C, S, Pinv (the box, rho and the splitting state stay per problem).
+#define GBDPCG_ADMM_STEP(NAME, SUF, TYPE, SHARED)                                                                                   \
+    gbdpcg_status gbdpcg_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const TYPE *d_Ginv,  \
+                                        const TYPE *d_C, const TYPE *d_g, const TYPE *d_c, const TYPE *d_lo, const TYPE *d_hi,        \
+                                        const TYPE *d_rho, const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda,        \
+                                        TYPE *d_r, TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters,                        \
+                                        uint8_t *d_max_iter_exit, TYPE *d_z, TYPE *d_w, TYPE *d_y, TYPE *d_gt, TYPE *d_res,           \
+                                        void *stream)                                                                               \
+    {                                                                                                                               \
+        const AdmmOperands<TYPE> a{d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res};                                                       \
+        return admm_step_impl<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, a, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol,    \
+                                    max_iter, d_iters, d_max_iter_exit, d_z, (hipStream_t)stream, SHARED);                          \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_graph_create_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,         \
+                                                     const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c,           \
+                                                     const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho, const TYPE *d_S,          \
+                                                     const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda, TYPE *d_r, TYPE *d_p,         \
+                                                     TYPE tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,       \
+                                                     TYPE *d_z, TYPE *d_w, TYPE *d_y, TYPE *d_gt, TYPE *d_res, gbdpcg_graph_t *out)   \
+    {                                                                                                                               \
+        /* what the captured calls would refuse is refused before anything is reserved or captured */                                \
+        if (!h || !out || !d_Ginv || !d_g || !d_c || !d_lo || !d_hi || !d_rho || !d_S || !d_gamma || !d_lambda || !d_iters ||       \
+            !d_z || !d_w || !d_y || !d_gt || !d_res || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))                       \
+            return GBDPCG_ERR_INVALID;                                                                                              \
+        if (!schur_shape_ok<TYPE>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;                                                   \
+        const AdmmOperands<TYPE> a{d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res};                                                       \
+        KktOperands<TYPE> k{nu, nullptr, d_C, d_g, d_c, const_cast<TYPE *>(d_Ginv), d_z};                                           \
+        k.resolve = true;                                                                                                           \
+        k.shared = SHARED;                                                                                                          \
+        k.admm = &a;                                                                                                                \
+        return graph_create_impl<TYPE>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters,            \
+                                       d_max_iter_exit, out, -1, &k);                                                               \
+    }
+#define GBDPCG_ADMM(SUF, TYPE)                                                                                                      \
+    gbdpcg_status gbdpcg_admm_init_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const TYPE *d_g,    \
+                                         const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho, TYPE *d_w, TYPE *d_y, TYPE *d_gt,     \
+                                         void *stream)                                                                              \
+    {                                                                                                                               \
+        return admm_update_impl<TYPE>(h, nx, nu, N, batch, d_g, d_lo, d_hi, d_rho, nullptr, d_w, d_y, d_gt, nullptr, stream, true);  \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_update_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const TYPE *d_g,  \
+                                           const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho, const TYPE *d_z, TYPE *d_w,         \
+                                           TYPE *d_y, TYPE *d_gt, TYPE *d_res, void *stream)                                         \
+    {                                                                                                                               \
+        return admm_update_impl<TYPE>(h, nx, nu, N, batch, d_g, d_lo, d_hi, d_rho, d_z, d_w, d_y, d_gt, d_res, stream, false);       \
+    }                                                                                                                               \
+    GBDPCG_ADMM_STEP(admm_step, SUF, TYPE, false)                                                                                   \
+    GBDPCG_ADMM_STEP(admm_step_shared, SUF, TYPE, true)
+GBDPCG_ADMM(f32, float)
+GBDPCG_ADMM(f64, double)
+#undef GBDPCG_ADMM
+#undef GBDPCG_ADMM_STEP
 
 gbdpcg_status gbdpcg_csr_to_bt_f32(uint32_t n, uint32_t N, const uint32_t *row_ptr, const uint32_t *col_ind,
                                    const float *val, float *h_M)

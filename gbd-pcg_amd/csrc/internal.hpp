@@ -220,4 +220,12 @@ hipError_t launch_kkt_residual(const DeviceInfo &dev, uint32_t nx, uint32_t nu, 
 // (shared, the three launchers: Ginv / G and C are one problem's blocks, used by every problem of the batch)
 template <typename T> bool schur_shape_ok(const DeviceInfo &dev, uint32_t nx, uint32_t nu);
 
+// ---- admm.hip : the splitting update of box-constrained ADMM on a kept factorisation, one launch, one workgroup per problem.
+// Every array has the layout of g ((nx + nu) N - nu elements per problem), rho [batch], res [2 batch]:
+//     w <- clip(z + y, lo, hi), y <- (z + y) - w, gt <- fma(-rho_b, w - y, g), res[2b] = ||z - w||_inf, res[2b+1] = rho_b ||w - w_old||_inf
+// init: w <- clip(w, lo, hi), gt <- fma(-rho_b, w - y, g); y is not written, z and res are not looked at (may be null).
+template <typename T>
+hipError_t launch_admm_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *g, const T *lo, const T *hi, const T *rho,
+                              const T *z, T *w, T *y, T *gt, T *res, hipStream_t s, bool init);
+
 }  // namespace gbdpcg

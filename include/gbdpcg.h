@@ -571,6 +571,109 @@ gbdpcg_status gbdpcg_kkt_residual_reg_f64(gbdpcg_handle_t h, uint32_t nx, uint32
                                           const double *d_rho, const double *d_z, const double *d_lambda, double *d_res,
                                           void *stream);
 
+/* Box constraints on a kept linearisation: ADMM iterations whose solve is gbdpcg_kkt_resolve_* on a frozen factorisation.  Problem b is
+ *     minimise 1/2 z'Gz + g'z   subject to   Cz = c,   lo <= z <= hi
+ * and is split into z (which satisfies the dynamics Cz = c) and a copy w (which lies in the box), held together by the scaled
+ * multiplier y of z = w, with a per-problem penalty rho_b > 0.  The matrices come from gbdpcg_form_schur_reg_* or
+ * gbdpcg_kkt_step_reg_* with that rho, so d_Ginv, d_S and d_Pinv belong to G + rho I and stay as they are for every iteration; only
+ * the gradient of the solve changes.  d_lo, d_hi (per element; -Inf / +Inf: no bound), the state d_w, d_y and the shifted gradient
+ * d_gt have the layout of d_g; d_rho has `batch` elements and d_res 2 batch, all on the device in the call's precision.
+ * One iteration (gbdpcg_admm_step_*), per element of problem b:
+ *     (z, lambda) = gbdpcg_kkt_resolve_* with d_gt in the place of d_g        warm start from d_lambda
+ *     v   = fl(z + y)
+ *     w+  = v < lo ? lo : (v > hi ? hi : v)                                   comparisons, not fmin / fmax: a NaN v stays NaN
+ *     y+  = fl(v - w+)                                                        exactly 0 wherever nothing was clipped
+ *     gt+ = fma(-rho_b, fl(w+ - y+), g)                                       one rounding
+ *     d_res[2b]   = max_i |fl(z_i - w+_i)|                                    primal residual || z - w ||_inf
+ *     d_res[2b+1] = max_i |fl(rho_b fl(w+_i - w_i))|                          dual residual rho || w+ - w ||_inf
+ * Every line is a single IEEE operation or a comparison, so d_w, d_y, d_gt and d_res are defined to the bit; the two maxima are
+ * those of gbdpcg_kkt_residual_* (over bit patterns: exact in any order, a NaN is that problem's norm, Inf stays Inf) and d_res is
+ * overwritten whatever it held.  Which output is which: d_z satisfies the dynamics to the accuracy of the solve, d_w satisfies the
+ * box exactly; they agree to d_res[2b], and at convergence either is the solution.  The multiplier of the bounds is mu = rho y:
+ * y_i > 0 where the upper bound is active, y_i < 0 where the lower one is, and G z + g + C' lambda + rho y -> 0.
+ *  - gbdpcg_admm_init_*: before the first iteration.  w <- clip(w, lo, hi) by the same comparisons, y is left as it is,
+ *    gt <- fma(-rho_b, fl(w - y), g).  With w = y = 0 and 0 inside the box gt = g: the first solve is the equality-constrained one.
+ *    A warm start passes the w and y of the previous control step.
+ *  - gbdpcg_admm_update_*: everything behind the solve, one launch -- reads z, w, y, lo, hi, g, writes w, y, gt and d_res.
+ *  - gbdpcg_admm_step_*: gbdpcg_kkt_resolve_* (with d_gt for d_g) followed by gbdpcg_admm_update_* on the same stream, same results
+ *    bit for bit; d_g itself is read by the update only.  The solve runs in the handle's symmetric mode like any kkt_resolve.
+ *  - gbdpcg_admm_step_shared_*: d_Ginv, d_C, d_S, d_Pinv are ONE problem's, as in gbdpcg_kkt_resolve_shared_*; every vector, d_lo,
+ *    d_hi, d_rho [batch], d_w, d_y, d_gt and d_res stay per problem.  The caller fills d_rho with the rho the single matrices were
+ *    formed with; nothing checks that.
+ *  - the graphs keep the POINTER d_rho like gbdpcg_graph_create_kkt_step_reg_* (rewriting rho in place changes the update, not the
+ *    matrices: a new rho needs gbdpcg_kkt_step_reg_* again); the constructors reserve what the solve needs, nothing allocates under
+ *    capture.  Replay the graph once per iteration and read d_res every few replays to stop.
+ *  - d_rho, d_lo, d_hi are NOT validated on the device: lo > hi, NaN or a negative rho give what the formulas give, inside their
+ *    own problem only.
+ * Null handle or required pointer, nx, nu, N or batch == 0: GBDPCG_ERR_INVALID, nothing is written (d_r, d_p, d_max_iter_exit and
+ * d_Pinv may be NULL as in gbdpcg_kkt_resolve_*, d_C when N == 1).  init and update are elementwise and refuse no shape; step
+ * inherits every refusal of gbdpcg_kkt_resolve_* or its shared twin and refuses before anything is written. */
+gbdpcg_status gbdpcg_admm_init_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_g,
+                                   const float *d_lo, const float *d_hi, const float *d_rho, float *d_w, float *d_y, float *d_gt,
+                                   void *stream);
+gbdpcg_status gbdpcg_admm_init_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_g,
+                                   const double *d_lo, const double *d_hi, const double *d_rho, double *d_w, double *d_y,
+                                   double *d_gt, void *stream);
+gbdpcg_status gbdpcg_admm_update_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_g,
+                                     const float *d_lo, const float *d_hi, const float *d_rho, const float *d_z, float *d_w,
+                                     float *d_y, float *d_gt, float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_update_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_g,
+                                     const double *d_lo, const double *d_hi, const double *d_rho, const double *d_z, double *d_w,
+                                     double *d_y, double *d_gt, double *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_Ginv,
+                                   const float *d_C, const float *d_g, const float *d_c, const float *d_lo, const float *d_hi,
+                                   const float *d_rho, const float *d_S, const float *d_Pinv, float *d_gamma, float *d_lambda,
+                                   float *d_r, float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                   uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res,
+                                   void *stream);
+gbdpcg_status gbdpcg_admm_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_Ginv,
+                                   const double *d_C, const double *d_g, const double *d_c, const double *d_lo,
+                                   const double *d_hi, const double *d_rho, const double *d_S, const double *d_Pinv,
+                                   double *d_gamma, double *d_lambda, double *d_r, double *d_p, double tol, uint32_t max_iter,
+                                   uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y,
+                                   double *d_gt, double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                                const float *d_lo, const float *d_hi, const float *d_rho, const float *d_S,
+                                                const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r, float *d_p,
+                                                float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                                float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res,
+                                                gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                const double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                                const double *d_lo, const double *d_hi, const double *d_rho, const double *d_S,
+                                                const double *d_Pinv, double *d_gamma, double *d_lambda, double *d_r, double *d_p,
+                                                double tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                                double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res,
+                                                gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_admm_step_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                          const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                          const float *d_lo, const float *d_hi, const float *d_rho, const float *d_S,
+                                          const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r, float *d_p, float tol,
+                                          uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_z, float *d_w,
+                                          float *d_y, float *d_gt, float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_step_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                          const double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                          const double *d_lo, const double *d_hi, const double *d_rho, const double *d_S,
+                                          const double *d_Pinv, double *d_gamma, double *d_lambda, double *d_r, double *d_p,
+                                          double tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z,
+                                          double *d_w, double *d_y, double *d_gt, double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_step_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                       const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                                       const float *d_lo, const float *d_hi, const float *d_rho, const float *d_S,
+                                                       const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r,
+                                                       float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                                       uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y, float *d_gt,
+                                                       float *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_step_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                       const double *d_Ginv, const double *d_C, const double *d_g,
+                                                       const double *d_c, const double *d_lo, const double *d_hi,
+                                                       const double *d_rho, const double *d_S, const double *d_Pinv,
+                                                       double *d_gamma, double *d_lambda, double *d_r, double *d_p, double tol,
+                                                       uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                                       double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res,
+                                                       gbdpcg_graph_t *out);
+
 /* CSR ingestion (f3): repacks a host CSR matrix (csr_t<T>, include/types.cuh:7-15) whose
  * sparsity lies inside the block-tridiagonal pattern into the [L|D|R] layout (host arrays).
  * Entries outside the pattern give GBDPCG_ERR_INVALID.  Implements what the stub overload
