@@ -22,6 +22,9 @@ struct gbdpcg_context {
     int symmetric = 2;  // gbdpcg_set_symmetric: 0 never, 1 assume, 2 check on the device (default)
     uint8_t *sym_flags = nullptr;  // [sym_cap] per-problem result of the check
     size_t sym_cap = 0;
+    // Behind the verdict bytes, at sym_flags + sym_cap (256-byte aligned: it shares no dword, and no cache line, with a verdict
+    // byte): the two words of PcgArgs::reject_count.  Zeroed once when the buffer is allocated; a step leaves them zero.
+    size_t sym_alloc = 0;          // bytes of the allocation: sym_cap + kRejectRoom
     hipError_t last_err = hipSuccess;
     // status words for the blocking entry points (replace the per-call cudaMalloc of interface.cuh:105-108)
     uint32_t *d_iters = nullptr;
@@ -265,9 +268,21 @@ template <typename T> uint32_t persist_slices(gbdpcg_handle_t h, uint32_t n, uin
     return cap;
 }
 
-gbdpcg_status ensure_sym_flags(gbdpcg_handle_t h, size_t batch)
+// `bytes` verdict bytes and, behind them, the reject words (gbdpcg_context::sym_alloc).  Never called while a stream of this handle
+// is capturing.
+constexpr size_t kRejectRoom = 256;
+uint32_t *reject_words(gbdpcg_handle_t h) { return reinterpret_cast<uint32_t *>(h->sym_flags + h->sym_cap); }
+gbdpcg_status ensure_sym_flags(gbdpcg_handle_t h, size_t bytes)
 {
-    return grow_buffer(h, reinterpret_cast<void **>(&h->sym_flags), &h->sym_cap, batch);
+    if (h->sym_flags && bytes <= h->sym_cap) return GBDPCG_OK;
+    const gbdpcg_status st =
+        grow_buffer(h, reinterpret_cast<void **>(&h->sym_flags), &h->sym_alloc, (bytes + 255) / 256 * 256 + kRejectRoom);
+    if (st != GBDPCG_OK) return st;
+    h->sym_cap = h->sym_alloc - kRejectRoom;   // (grow_buffer rounds to 256 bytes)
+    // the count reads 0 wherever no verifying launch has counted: done before any stream of the caller can use the buffer
+    hipError_t e = hipMemset(reject_words(h), 0, kRejectRoom);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    return e == hipSuccess ? GBDPCG_OK : fail(h, e);
 }
 
 template <typename T>
@@ -359,6 +374,11 @@ gbdpcg_status solve_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t bat
             }
             a.symmetric = true;
             a.verdict_out = h->sym_flags;
+            // the problems it rejects are counted on the device, and the general launch below returns at once when there are none
+            // (whichever kernel launch_pcg_fused picks for it: the cluster kernel, or pcg_fused_kernel where that path is off or
+            // refuses max_iter; the shapes of pcg_resident.hip never get here).  When there are some, that launch puts the count
+            // back to 0 as it ends, so a step leaves the word as it found it: nothing to initialise, eager or captured.
+            a.reject_count = reject_words(h);
             hipError_t rerr = hipSuccess;
             if (!launch_pcg_resident_sym_verify<T>(h->dev, a, stream, &rerr)) return GBDPCG_ERR_UNSUPPORTED;
             HIP_TRY(h, rerr);
@@ -368,6 +388,7 @@ gbdpcg_status solve_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t bat
             a.sel = h->sym_flags;
             a.want = 0;
             HIP_TRY(h, launch_pcg_fused<T>(h->dev, a, stream, shared));
+            a.reject_count = nullptr;
         } else if (has_sym && h->symmetric == 2) {
             // AUTO: test L_{k+1} == R_k^T on the device (S, then Pinv and-ed in), then launch BOTH kernels:
             // the symmetric one takes the problems that passed, the general one the rest.  No host
@@ -442,7 +463,9 @@ gbdpcg_status spmv_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batc
 
 // Verdict bytes a (n, N, batch) solve in symmetric mode 2 may need: the larger of what the test kernel and the
 // one-launch stair kernel write per problem.
-// (never less than one byte per problem: the verifying resident launch writes that many)
+// (never less than one byte per problem: the verifying resident launch writes that many; the words in which that launch counts
+// the problems it rejects come on top, in ensure_sym_flags, through which every caller of this -- gbdpcg_reserve and the graph
+// constructors -- allocates)
 template <typename T> size_t verdict_bytes(uint32_t n, uint32_t N, uint32_t batch)
 {
     const uint32_t a = check_pair_chunks<T>(n, N), b = pinv_verdict_chunks<T>(n, N, GBDPCG_PINV_STAIR);
@@ -1452,6 +1475,18 @@ gbdpcg_status gbdpcg_csr_to_bt_f64(uint32_t n, uint32_t N, const uint32_t *row_p
 }
 
 const char *gbdpcg_version(void) { return "gbdpcg 0.1 gfx950"; }
+
+// For the tests and tools of this repository only (not in gbdpcg.h, may change): where the handle keeps device state that no entry
+// point returns.  which = 0: the verdict bytes of symmetric mode 2, 1: the reject words behind them (PcgArgs::reject_count),
+// 2: the cluster path's workspace (u64 word 31 is the launch number).  nullptr: not allocated yet, or no such state.
+void *gbdpcg_internal_state(gbdpcg_handle_t h, int which)
+{
+    if (!h) return nullptr;
+    if (which == 0) return h->sym_flags;
+    if (which == 1) return h->sym_flags ? reject_words(h) : nullptr;
+    if (which == 2) return h->cluster_ws;
+    return nullptr;
+}
 
 #if defined(GBDPCG_CL_STAMPS) || defined(GBDPCG_RS_STAMPS)
 // diagnostic builds only (tools/cluster_stamps.py, tools/rs_stamps.py): the cluster path's workspace holds the stamps

@@ -52,6 +52,29 @@ __device__ __forceinline__ unsigned long long pcg_takes_mask(const A &a, uint32_
     return __ballot(mine);
 }
 
+// The general launch behind a verifying launch (PcgArgs::reject_count): true when the verifying launch rejected nothing, so that
+// this launch owns nothing and the workgroup may return at once.  Called first thing by EVERY thread of the launch; the word is
+// written by the launch before this one alone, so every workgroup reads the same value and all of them take the same branch --
+// which is what makes leaving safe for kernels whose workgroups wait for each other (pcg_cluster.hip).
+template <typename A> __device__ __forceinline__ bool pcg_reject_none(const A &a)
+{
+    return a.reject_count && __hip_atomic_load(a.reject_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
+}
+// ... and at the end of a launch that did not return there: the workgroup that leaves last puts the count (and the word that
+// tells it that it is the last) back to 0 for the next verifying launch.  Every workgroup has read the count by then.
+template <typename A> __device__ __forceinline__ void pcg_reject_leave(const A &a)
+{
+    if (!a.reject_count) return;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t before = __hip_atomic_fetch_add(a.reject_count + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (before == gridDim.x - 1u) {
+            __hip_atomic_store(a.reject_count + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.reject_count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
 template <typename T> struct SpmvArgs {
     const T *M;
     const T *x;
@@ -83,6 +106,12 @@ template <typename T> struct PcgArgs {
     // The verifying resident kernel (launch_pcg_resident_sym_verify) writes its symmetry verdict here, one byte per problem
     // (1 = symmetric, solved; 0 = left untouched for the general launch).  Read by no other kernel.
     uint8_t *verdict_out = nullptr;
+    // Problems the verifying launch rejected, counted on the device: [0] the count, [1] workgroups of the general launch that
+    // have left (gbdpcg_context::sym_flags holds both, behind the verdict bytes).  The verifying launch adds to [0]; the general
+    // launch that follows it on the stream gets the same pointer, reads [0] before anything else and returns when it is 0
+    // (pcg_reject_none); when it is not, the workgroup of that launch that leaves last puts both words back to 0
+    // (pcg_reject_leave).  nullptr: a launch that does not follow a verifying launch -- nothing is read or written.
+    uint32_t *reject_count = nullptr;
     // Split path, blocking entry points only: a counter in host-visible memory that a problem bumps when
     // it converges, so that the host can stop enqueueing iteration launches (nullptr: not used).
     uint32_t *host_done = nullptr;

@@ -136,6 +136,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(ClusterLigh
 void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
                                                           uint32_t clusters, uint32_t spin_limit, uint32_t drop_block, bool no_plain)
 {
+    // Behind a verifying launch that rejected nothing (PcgArgs::reject_count) this launch owns nothing: leave before anything is
+    // set up.  Safe for the hand-off protocol only because EVERY workgroup of the launch reads the same count and so takes the
+    // same branch: nobody is left polling for a member that has gone.  Such a launch touches neither the slots nor the launch
+    // number: it publishes no tag, so it needs no number of its own, and the next launch that owns a problem still gets a
+    // number no earlier launch has used (a launch that owned nothing used to take one; it left the slots alone as well).
+    if (pcg_reject_none(a)) return;
 #ifndef GBDPCG_TEST_HOOKS
     drop_block = 0xffffffffu;   // the hook that silences one workgroup exists in variants/libgbdpcg_hooks.so only
 #endif
@@ -709,6 +715,7 @@ void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
             __hip_atomic_fetch_add(ctl + 31, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+    pcg_reject_leave(a);   // (a launch that got here behind a verifying launch: some problem was rejected)
     GBDPCG_CL_STAMP_WG(1)
 #undef GBDPCG_CL_HANDOFF
 #undef GBDPCG_CL_STAMP

@@ -24,6 +24,7 @@ namespace gbdpcg {
 template <typename T, int NCT, int V, int WAVES, bool SYM, bool SHARED = false>
 __global__ __launch_bounds__(WAVES * 64) void pcg_fused_kernel(PcgArgs<T> a)
 {
+    if (pcg_reject_none(a)) return;   // behind a verifying launch that rejected nothing: this launch owns nothing
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *smem = reinterpret_cast<T *>(smem_raw);
     const uint32_t n = NCT ? (uint32_t)NCT : a.n;
@@ -33,6 +34,7 @@ __global__ __launch_bounds__(WAVES * 64) void pcg_fused_kernel(PcgArgs<T> a)
         if (!pcg_takes<SHARED>(a, prob)) continue;  // this launch is not the one that owns the problem
         sv.template solve<SHARED>(a, prob, smem + cv.xa, smem + cv.xb, smem + cv.yc, smem + cv.lam, smem + cv.red, smem + cv.zc);
     }
+    pcg_reject_leave(a);
 }
 
 template <typename T> bool fused_has_symmetric(const DeviceInfo &dev, uint32_t n, uint32_t N, uint32_t batch)

@@ -352,6 +352,15 @@ __device__ __forceinline__ bool symres_r_differs(const float4 (&r)[NCT / 2], con
 // first read of the destination.
 __device__ __forceinline__ void symres_dma_dword(const float *base, uint32_t off, uint32_t lds_addr)
 {
+#ifdef GBDPCG_RS_STAMPS
+    // (diagnostic build: with the stamps' stores in the problem loop hipcc no longer proves the base uniform and refuses the "s"
+    // operand below; it is uniform)
+    {
+        const uint64_t b = reinterpret_cast<uint64_t>(base);
+        base = reinterpret_cast<const float *>(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
+                                               __builtin_amdgcn_readfirstlane((uint32_t)b));
+    }
+#endif
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %2, %1\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "s"(base), "v"(off), "s"(lds_addr) : "memory");
@@ -744,7 +753,11 @@ __global__ __launch_bounds__(512) void pcg_resident_sym_kernel(PcgArgs<float> a)
                 if (a.max_iter_exit) a.max_iter_exit[prob] = max_iter_exit ? 1 : 0;
             }
         }
-        if (VERIFY && tid == 0) a.verdict_out[prob] = keep ? 1 : 0;
+        if (VERIFY && tid == 0) {
+            a.verdict_out[prob] = keep ? 1 : 0;
+            // one more problem for the general launch, which returns at once while this count is 0 (pcg_reject_none)
+            if (!keep && a.reject_count) __hip_atomic_fetch_add(a.reject_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         __syncthreads();  // LDS (tile, vectors, verdict word) is reused by the next problem
         GBDPCG_RS_STAMP(6)
     }

@@ -3,8 +3,12 @@
 wave 0 of every workgroup at the phase boundaries of each of its problems, read from the diagnostic build of the library.
 
     make -C gbd-pcg_amd/csrc fvariant NAME=rsstamps EXTRA=-DGBDPCG_RS_STAMPS UNITS="pcg_resident_sym"
-    GBDPCG_LIB=gbd-pcg_amd/csrc/variants/libgbdpcg_rsstamps.so python gbd-pcg_amd/tools/rs_stamps.py
+    GBDPCG_LIB=gbd-pcg_amd/csrc/variants/libgbdpcg_rsstamps.so python gbd-pcg_amd/tools/rs_stamps.py [--mode 2]
+
+--mode 1 (default): the plain kernel (the caller's word).  --mode 2: the default mode, the verifying kernel -- its last phase is
+then the symmetry tail plus the write-back.
 """
+import argparse
 import ctypes
 import os
 import sys
@@ -15,6 +19,10 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from gbd_pcg_amd import binding, synth  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--mode", type=int, choices=(1, 2), default=1, help="symmetric mode of the handle")
+args = ap.parse_args()
 
 n, N, B = 14, 128, 1024
 s = binding.Solver(0)
@@ -27,8 +35,9 @@ fl = torch.zeros(B, dtype=torch.uint8, device="cuda")
 fn = s.lib.gbdpcg_internal_cluster_ws
 fn.restype = ctypes.c_void_p
 hip = ctypes.CDLL("libamdhip64.so")
-s.set_symmetric(1)
-names = ["loads issued", "tiles parked + picked", "vectors in, barrier", "prologue (2 products)", "iterations", "write-back + barrier"]
+s.set_symmetric(args.mode)
+names = ["loads issued", "tiles parked + picked", "vectors in, barrier", "prologue (2 products)", "iterations",
+         "tail + write-back" if args.mode == 2 else "write-back + barrier"]
 for label, tol, mi in (("25 fixed iterations", 0.0, 25), ("to 1e-6 (9 iterations)", 1e-6, 25)):
     gr = s.graph_solve(n, N, B, S, P, gamma, lam, None, None, tol, mi, it, fl)
     for _ in range(6):
