@@ -1,0 +1,101 @@
+"""torch.autograd through the batched KKT solve: (G, C, g, c[, rho]) -> (z, lambda) with gradients from the device backward pass.
+
+Plumbing over binding.Solver: the forward pass is gbdpcg_kkt_step_* (gbdpcg_kkt_step_reg_* when rho is given; for a shared-matrix
+batch gbdpcg_kkt_step_* at batch 1 followed by gbdpcg_kkt_resolve_shared_*), the backward pass is gbdpcg_kkt_backward_* on the S,
+Phi^-1 and G^-1 the forward pass left behind -- one adjoint solve and one gradient launch (include/gbdpcg.h has the formulas).
+Nothing here computes a gradient in torch except dl/drho = a_z' z, one dot product per problem.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import binding
+
+
+def _sizes(nx, nu, N):
+    return {"G": (nx * nx + nu * nu) * N - nu * nu, "C": (nx * nx + nx * nu) * (N - 1), "g": (nx + nu) * N - nu, "c": nx * N}
+
+
+class _KktSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, G, C, g, c, rho, solver, nx, nu, N, batch, shared, tol, max_iter):
+        sz = _sizes(nx, nu, N)
+        mats = 1 if shared else batch
+        kw = dict(dtype=g.dtype, device=g.device)
+        S = torch.empty(mats * 3 * nx * nx * N, **kw)
+        Pinv, Ginv = torch.empty_like(S), torch.empty(mats * sz["G"], **kw)
+        gamma = torch.empty(batch * sz["c"], **kw)
+        lam, z = torch.zeros(batch * sz["c"], **kw), torch.empty(batch * sz["g"], **kw)
+        ctx.shapes = tuple(t.shape for t in (G, C, g, c))
+        G, C, g, c = (t.detach().reshape(-1) for t in (G, C, g, c))
+        if shared:
+            # the single matrices are what the step writes at batch 1 (here on the first problem's vectors); every problem is
+            # then solved on them
+            lam0, z0 = torch.zeros(sz["c"], **kw), torch.empty(sz["g"], **kw)
+            solver.kkt_step(nx, nu, N, 1, G, C, g[:sz["g"]], c[:sz["c"]], S, gamma[:sz["c"]], Ginv, Pinv, lam0, z0, tol=tol,
+                            max_iter=max_iter)
+            solver.kkt_resolve_shared(nx, nu, N, batch, Ginv, C, g, c, S, Pinv, gamma, lam, z, tol=tol, max_iter=max_iter)
+        elif rho is not None:
+            solver.kkt_step_reg(nx, nu, N, batch, G, C, g, c, rho.detach(), S, gamma, Ginv, Pinv, lam, z, tol=tol, max_iter=max_iter)
+        else:
+            solver.kkt_step(nx, nu, N, batch, G, C, g, c, S, gamma, Ginv, Pinv, lam, z, tol=tol, max_iter=max_iter)
+        ctx.save_for_backward(Ginv, S, Pinv, C, z, lam)
+        ctx.args = (solver, nx, nu, N, batch, shared, tol, max_iter, rho is not None)
+        return z, lam
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gz, glam):
+        Ginv, S, Pinv, C, z, lam = ctx.saved_tensors
+        solver, nx, nu, N, batch, shared, tol, max_iter, has_rho = ctx.args
+        sz = _sizes(nx, nu, N)
+        mats = 1 if shared else batch
+        gz = torch.zeros_like(z) if gz is None else gz.contiguous()
+        nglam = torch.zeros_like(lam) if glam is None else -glam.contiguous()
+        gamma, alam, az = torch.empty_like(lam), torch.zeros_like(lam), torch.empty_like(z)
+        need_G, need_C = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and N > 1
+        gG = torch.empty(mats * sz["G"], dtype=z.dtype, device=z.device) if need_G else None
+        gC = torch.empty(mats * sz["C"], dtype=z.dtype, device=z.device) if need_C else None
+        if need_G or need_C:
+            back = solver.kkt_backward_shared if shared else solver.kkt_backward
+            back(nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, gG, gC, tol=tol, max_iter=max_iter)
+        else:   # only the adjoint pair is asked for: the solve alone
+            resolve = solver.kkt_resolve_shared if shared else solver.kkt_resolve
+            resolve(nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, alam, az, tol=tol, max_iter=max_iter)
+        if ctx.needs_input_grad[1] and N == 1:
+            gC = torch.zeros(mats * sz["C"], dtype=z.dtype, device=z.device)
+        grho = (az.view(batch, -1) * z.view(batch, -1)).sum(1) if has_rho and ctx.needs_input_grad[4] else None
+        grads = [t if t is None else t.view(s) for t, s in zip((gG, gC, az, -alam), ctx.shapes)]
+        return (*grads, grho) + (None,) * 8
+
+
+def kkt_solve(solver, nx, nu, N, G, C, g, c, rho=None, shared=False, tol=1e-6, max_iter=25):
+    """(z, lambda) of  G z + g + C' lambda = 0,  C z = c  for a batch of problems, differentiable in G, C, g, c (and rho).
+
+    Flat contiguous device tensors of one dtype in the packed layouts of include/gbdpcg.h; the batch is g.numel() over one
+    problem's extent.  rho: [batch], the per-problem regularisation of gbdpcg_kkt_step_reg_* (problem b is solved with
+    G_b + rho_b I).  shared=True: G and C are ONE problem's blocks, used by every problem of the batch, and their gradients are
+    the sums over the batch.  tol, max_iter: the PCG settings of the forward and of the adjoint solve.  The gradient in G is
+    the symmetrised one (the library reads G as symmetric).  The handle's symmetric mode and path are left as found."""
+    if not isinstance(solver, binding.Solver):
+        raise TypeError("kkt_solve: solver is a binding.Solver")
+    sz = _sizes(nx, nu, N)
+    for name, t in (("G", G), ("C", C), ("g", g), ("c", c)) + ((("rho", rho),) if rho is not None else ()):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == g.dtype):
+            raise ValueError(f"kkt_solve: {name} must be a contiguous device tensor of g's dtype")
+    if g.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"kkt_solve: unsupported dtype {g.dtype}")
+    if g.numel() == 0 or g.numel() % sz["g"]:
+        raise ValueError("kkt_solve: g is not a whole number of problems")
+    batch = g.numel() // sz["g"]
+    if shared and rho is not None:
+        raise ValueError("kkt_solve: rho is per problem and has no shared-matrix form (regularise the single G instead)")
+    mats = 1 if shared else batch
+    want = {"G": mats * sz["G"], "C": mats * sz["C"], "g": batch * sz["g"], "c": batch * sz["c"]}
+    for name, t in (("G", G), ("C", C), ("g", g), ("c", c)):
+        if t.numel() != want[name]:
+            raise ValueError(f"kkt_solve: {name} has {t.numel()} elements, the layout takes {want[name]}")
+    if rho is not None and rho.numel() != batch:
+        raise ValueError("kkt_solve: rho has one element per problem")
+    return _KktSolve.apply(G, C, g, c, rho, solver, nx, nu, N, batch, shared, tol, max_iter)

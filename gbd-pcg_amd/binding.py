@@ -47,6 +47,10 @@ SYMBOLS = [
     "gbdpcg_admm_step_f32", "gbdpcg_admm_step_f64", "gbdpcg_graph_create_admm_step_f32", "gbdpcg_graph_create_admm_step_f64",
     "gbdpcg_admm_step_shared_f32", "gbdpcg_admm_step_shared_f64",
     "gbdpcg_graph_create_admm_step_shared_f32", "gbdpcg_graph_create_admm_step_shared_f64",
+    "gbdpcg_kkt_grad_f32", "gbdpcg_kkt_grad_f64", "gbdpcg_kkt_grad_shared_f32", "gbdpcg_kkt_grad_shared_f64",
+    "gbdpcg_kkt_backward_f32", "gbdpcg_kkt_backward_f64", "gbdpcg_kkt_backward_shared_f32", "gbdpcg_kkt_backward_shared_f64",
+    "gbdpcg_graph_create_kkt_backward_f32", "gbdpcg_graph_create_kkt_backward_f64",
+    "gbdpcg_graph_create_kkt_backward_shared_f32", "gbdpcg_graph_create_kkt_backward_shared_f64",
     "gbdpcg_csr_to_bt_f32", "gbdpcg_csr_to_bt_f64", "gbdpcg_version",
 ]
 
@@ -85,6 +89,14 @@ def _resolve_argtypes(lib):
         for name in ("admm_step", "admm_step_shared"):
             getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = head + [vp, vp, vp] + solve + [vp, vp, vp, vp] + [vp]
             getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = head + [vp, vp, vp] + solve + [vp, vp, vp, vp] + [ctypes.POINTER(vp)]
+        # the backward pass: z, lambda, az, alambda | gG, gC, stream
+        for name in ("kkt_grad", "kkt_grad_shared"):
+            getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = sizes + [vp, vp, vp, vp] + [vp, vp, vp]
+        # Ginv, C, gz, nglam | S, Pinv, gamma | z, lambda, az, alambda | r, p, tol, max_iter, iters, flags | gG, gC | stream / graph out
+        back = head + [vp, vp, vp] + [vp, vp, vp, vp] + [vp, vp, ft, u32, vp, vp] + [vp, vp]
+        for name in ("kkt_backward", "kkt_backward_shared"):
+            getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = back + [vp]
+            getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = back + [ctypes.POINTER(vp)]
 
 _lib = None
 
@@ -640,6 +652,93 @@ class Solver:
         return self._graph_admm_step("admm_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
                                      max_iter, iters, max_iter_exit, z, w, y, gt, res)
 
+    # ---- the backward pass (include/gbdpcg.h): gradients of a scalar in G and C from the forward point (z, lam) and the adjoint pair
+    # (az, alam), which is kkt_resolve with g := dl/dz, c := -dl/dlambda on the kept factorisation
+    def _grad_args(self, nx, nu, N, batch, z, lam, az, alam, gG, gC, shared):
+        import torch
+        suf, _ = _suffix(z)
+        nz, nl, mats = (nx + nu) * N - nu, nx * N, 1 if shared else batch
+        for t, cnt in ((z, batch * nz), (az, batch * nz), (lam, batch * nl), (alam, batch * nl),
+                       (gG, mats * ((nx * nx + nu * nu) * N - nu * nu)), (gC, mats * (nx * nx + nx * nu) * (N - 1))):
+            if t is not None:
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() == cnt and t.dtype == z.dtype):
+                    raise ValueError("the backward pass takes contiguous device tensors of one dtype in the layouts of include/gbdpcg.h")
+        return suf
+
+    def _kkt_grad(self, name, nx, nu, N, batch, z, lam, az, alam, gG, gC, want, stream):
+        import torch
+        shared = name.endswith("shared")
+        mats = 1 if shared else batch
+        if gG is None and "G" in want:
+            gG = torch.empty(mats * ((nx * nx + nu * nu) * N - nu * nu), dtype=z.dtype, device=z.device)
+        if gC is None and "C" in want:
+            gC = torch.empty(mats * (nx * nx + nx * nu) * (N - 1), dtype=z.dtype, device=z.device)
+        suf = self._grad_args(nx, nu, N, batch, z, lam, az, alam, gG, gC, shared)
+        fn = getattr(self.lib, f"gbdpcg_{name}_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(z), _p(lam), _p(az), _p(alam), _p(gG), _p(gC), self._stream(stream)), name)
+        return gG, gC
+
+    def kkt_grad(self, nx, nu, N, batch, z, lam, az, alam, gG=None, gC=None, want="GC", stream=None):
+        """gbdpcg_kkt_grad_*: (gG, gC) in the layouts of G and C, per problem.  want: which outputs to allocate when none is passed
+        ("G", "C" or "GC"); an output that is neither passed nor wanted is skipped (None)."""
+        return self._kkt_grad("kkt_grad", nx, nu, N, batch, z, lam, az, alam, gG, gC, want, stream)
+
+    def kkt_grad_shared(self, nx, nu, N, batch, z, lam, az, alam, gG=None, gC=None, want="GC", stream=None):
+        """gbdpcg_kkt_grad_shared_*: ONE problem's worth of gG, gC, summed over the batch in a fixed order."""
+        return self._kkt_grad("kkt_grad_shared", nx, nu, N, batch, z, lam, az, alam, gG, gC, want, stream)
+
+    def _backward_args(self, shared, nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, r, p, tol, max_iter, iters,
+                       mie, gG, gC):
+        suf = self._grad_args(nx, nu, N, batch, z, lam, az, alam, gG, gC, shared)
+        self._grad_args(nx, nu, N, batch, gz, nglam, gz, gamma, None, None, shared)
+        return suf, (self.h, nx, nu, N, batch, _p(Ginv), _p(C), _p(gz), _p(nglam), _p(S), _p(Pinv), _p(gamma), _p(z), _p(lam), _p(az),
+                     _p(alam), _p(r), _p(p), tol, max_iter, _p(iters), _p(mie), _p(gG), _p(gC))
+
+    def _kkt_backward(self, name, nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, gG, gC, r, p, tol, max_iter,
+                      iters, max_iter_exit, stream):
+        import torch
+        if iters is None:
+            iters = torch.zeros(batch, dtype=torch.int32, device=z.device)
+        if max_iter_exit is None:
+            max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=z.device)
+        suf, args = self._backward_args(name.endswith("shared"), nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, r,
+                                        p, tol, max_iter, iters, max_iter_exit, gG, gC)
+        self._check(getattr(self.lib, f"gbdpcg_{name}_{suf}")(*args, self._stream(stream)), name)
+        return iters, max_iter_exit
+
+    def _graph_kkt_backward(self, name, nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, r, p, tol, max_iter,
+                            iters, max_iter_exit, gG, gC):
+        suf, args = self._backward_args(name.endswith("shared"), nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, r,
+                                        p, tol, max_iter, iters, max_iter_exit, gG, gC)
+        gr = ctypes.c_void_p()
+        self._check(getattr(self.lib, f"gbdpcg_graph_create_{name}_{suf}")(*args, ctypes.byref(gr)), f"graph_create_{name}")
+        return Graph(self, gr, keep=(Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, r, p, iters, max_iter_exit, gG, gC))
+
+    def kkt_backward(self, nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, gG, gC, r=None, p=None, tol=1e-6,
+                     max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_kkt_backward_*: the adjoint solve (kkt_resolve with g := gz, c := nglam = -dl/dlambda, warm start from alam, writing
+        alam and az) and kkt_grad on (z, lam, az, alam), one call.  Returns the (iters, flags) of the adjoint solve."""
+        return self._kkt_backward("kkt_backward", nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, gG, gC, r, p,
+                                  tol, max_iter, iters, max_iter_exit, stream)
+
+    def kkt_backward_shared(self, nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, gG, gC, r=None, p=None,
+                            tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_kkt_backward_shared_*: ONE Ginv, C, S, Pinv; gG, gC one problem's worth, summed over the batch."""
+        return self._kkt_backward("kkt_backward_shared", nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, gG, gC,
+                                  r, p, tol, max_iter, iters, max_iter_exit, stream)
+
+    def graph_kkt_backward(self, nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, r, p, tol, max_iter, iters,
+                           max_iter_exit, gG, gC):
+        """Capture the adjoint solve and the gradient launch into one hipGraph (gbdpcg_graph_create_kkt_backward_*): rewrite gz and
+        nglam in place between replays."""
+        return self._graph_kkt_backward("kkt_backward", nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, r, p,
+                                        tol, max_iter, iters, max_iter_exit, gG, gC)
+
+    def graph_kkt_backward_shared(self, nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, r, p, tol, max_iter,
+                                  iters, max_iter_exit, gG, gC):
+        """Capture the shared-matrix backward pass into one hipGraph (gbdpcg_graph_create_kkt_backward_shared_*)."""
+        return self._graph_kkt_backward("kkt_backward_shared", nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam,
+                                        r, p, tol, max_iter, iters, max_iter_exit, gG, gC)
 
 
 class Graph:

@@ -584,6 +584,13 @@ template <typename T> struct AdmmOperands {
     T *w, *y, *gt, *res;
 };
 
+// The forward point and the outputs of gbdpcg_kkt_backward_*: z has the layout of g, lambda that of c, gG / gC those of G / C (one
+// problem's worth in the shared form; either may be null).
+template <typename T> struct GradOperands {
+    const T *z, *lambda;
+    T *gG, *gC;
+};
+
 // The operands of the steps either side of the solve (gbdpcg_kkt_step_*): S and gamma are formed from them before, z after.
 template <typename T> struct KktOperands {
     uint32_t nu;
@@ -594,6 +601,7 @@ template <typename T> struct KktOperands {
     const T *rho = nullptr; // gbdpcg_kkt_step_reg_*: [batch] on the device, read by the formation kernel when it runs
     bool reg = false;       // ... and the step is that of G_b + rho_b I (rho is then required)
     const AdmmOperands<T> *admm = nullptr;   // gbdpcg_admm_step_* (with resolve): the solve takes admm->gt for g, the update follows
+    const GradOperands<T> *grad = nullptr;   // gbdpcg_kkt_backward_* (with resolve): the solve is the adjoint one, the grad launch follows
 };
 
 // KKT blocks -> S, gamma, G^-1 -> Phi^-1 -> PCG -> primal step, on one stream (capturable: no allocation after the first
@@ -687,6 +695,39 @@ gbdpcg_status admm_step_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32
     return admm_update_impl<T>(h, nx, nu, N, batch, d_g, a.lo, a.hi, a.rho, d_z, a.w, a.y, a.gt, a.res, stream, false);
 }
 
+// The gradient launch (kkt_grad.hip), no handle state.  shared: gG, gC are one problem's worth, summed over the batch.
+template <typename T>
+gbdpcg_status kkt_grad_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_z, const T *d_lambda,
+                            const T *d_az, const T *d_alambda, T *d_gG, T *d_gC, void *stream, bool shared)
+{
+    if (!h || !d_z || !d_lambda || !d_az || !d_alambda || (!d_gG && !d_gC) || nu == 0 || !shape_ok(nx, N, batch))
+        return GBDPCG_ERR_INVALID;
+    if (!schur_shape_ok<T>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_kkt_grad<T>(nx, nu, N, batch, d_z, d_lambda, d_az, d_alambda, d_gG, d_gC, (hipStream_t)stream, shared));
+    return GBDPCG_OK;
+}
+
+// The backward pass on a kept factorisation: the KKT matrix is symmetric, so the adjoint pair (az, alambda) is kkt_resolve_impl
+// with the upstream gradient gz in the place of g and nglam = -dl/dlambda in the place of c (warm start from alambda), and the
+// gradient launch follows on the same stream.  What either part would refuse is refused here, before anything is written.
+template <typename T>
+gbdpcg_status kkt_backward_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv, const T *d_C,
+                                const T *d_gz, const T *d_nglam, const T *d_S, const T *d_Pinv, T *d_gamma, const GradOperands<T> &f,
+                                T *d_az, T *d_alambda, T *d_r, T *d_p, T tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_exit,
+                                hipStream_t stream, bool shared = false)
+{
+    if (!h || !d_Ginv || !d_gz || !d_nglam || !d_S || !d_gamma || !f.z || !f.lambda || !d_az || !d_alambda || !d_iters ||
+        (!f.gG && !f.gC) || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))
+        return GBDPCG_ERR_INVALID;
+    if (!schur_shape_ok<T>(h->dev, nx, nu) || !mappable<T>(nx) || (shared && !fused_fits<T>(h->dev, nx, N)))
+        return GBDPCG_ERR_UNSUPPORTED;
+    const gbdpcg_status st = kkt_resolve_impl<T>(h, nx, nu, N, batch, d_Ginv, d_C, d_gz, d_nglam, d_S, d_Pinv, d_gamma, d_alambda, d_r,
+                                                 d_p, tol, max_iter, d_iters, d_exit, d_az, stream, shared);
+    if (st != GBDPCG_OK) return st;
+    return kkt_grad_impl<T>(h, nx, nu, N, batch, f.z, f.lambda, d_az, d_alambda, f.gG, f.gC, stream, shared);
+}
+
 template <typename T>
 gbdpcg_status graph_create_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batch, const T *d_S,
                                 const T *d_Pinv, const T *d_gamma, T *d_lambda, T *d_r, T *d_p, T tol,
@@ -734,7 +775,10 @@ gbdpcg_status graph_create_impl(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint3
     hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
     gbdpcg_status st = GBDPCG_OK;
     if (e == hipSuccess) {
-        if (kkt && kkt->resolve && kkt->admm)
+        if (kkt && kkt->resolve && kkt->grad)
+            st = kkt_backward_impl<T>(h, n, kkt->nu, N, batch, kkt->Ginv, kkt->C, kkt->g, kkt->c, d_S, d_Pinv, const_cast<T *>(d_gamma),
+                                      *kkt->grad, kkt->z, d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, cs, kkt->shared);
+        else if (kkt && kkt->resolve && kkt->admm)
             st = admm_step_impl<T>(h, n, kkt->nu, N, batch, kkt->Ginv, kkt->C, kkt->g, kkt->c, *kkt->admm, d_S, d_Pinv,
                                    const_cast<T *>(d_gamma), d_lambda, d_r, d_p, tol, max_iter, d_iters, d_exit, kkt->z, cs, kkt->shared);
         else if (kkt && kkt->resolve)
@@ -1462,6 +1506,51 @@ GBDPCG_ADMM(f32, float)
 GBDPCG_ADMM(f64, double)
 #undef GBDPCG_ADMM
 #undef GBDPCG_ADMM_STEP
+
+// ---- the KKT backward pass: the gradients of a scalar in G and C from (z, lambda) and the adjoint pair, and the adjoint solve +
+// gradient launch as one call / one graph.  SHARED: one problem's Ginv, C, S, Pinv, and gG, gC summed over the batch.
+#define GBDPCG_KKT_BACKWARD(NAME, SUF, TYPE, SHARED)                                                                                \
+    gbdpcg_status gbdpcg_kkt_grad##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,              \
+                                                const TYPE *d_z, const TYPE *d_lambda, const TYPE *d_az, const TYPE *d_alambda,      \
+                                                TYPE *d_gG, TYPE *d_gC, void *stream)                                                \
+    {                                                                                                                               \
+        return kkt_grad_impl<TYPE>(h, nx, nu, N, batch, d_z, d_lambda, d_az, d_alambda, d_gG, d_gC, stream, SHARED);                 \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_kkt_backward##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,          \
+                                                    const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_gz, const TYPE *d_nglam,      \
+                                                    const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma, const TYPE *d_z,             \
+                                                    const TYPE *d_lambda, TYPE *d_az, TYPE *d_alambda, TYPE *d_r, TYPE *d_p,         \
+                                                    TYPE tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,        \
+                                                    TYPE *d_gG, TYPE *d_gC, void *stream)                                            \
+    {                                                                                                                               \
+        const GradOperands<TYPE> f{d_z, d_lambda, d_gG, d_gC};                                                                      \
+        return kkt_backward_impl<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_gz, d_nglam, d_S, d_Pinv, d_gamma, f, d_az, d_alambda,    \
+                                       d_r, d_p, tol, max_iter, d_iters, d_max_iter_exit, (hipStream_t)stream, SHARED);             \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_graph_create_kkt_backward##NAME##_##SUF(                                                                    \
+        gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const TYPE *d_Ginv, const TYPE *d_C,               \
+        const TYPE *d_gz, const TYPE *d_nglam, const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma, const TYPE *d_z,                 \
+        const TYPE *d_lambda, TYPE *d_az, TYPE *d_alambda, TYPE *d_r, TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters,    \
+        uint8_t *d_max_iter_exit, TYPE *d_gG, TYPE *d_gC, gbdpcg_graph_t *out)                                                      \
+    {                                                                                                                               \
+        /* what the captured calls would refuse is refused before anything is reserved or captured */                                \
+        if (!h || !out || !d_Ginv || !d_gz || !d_nglam || !d_S || !d_gamma || !d_z || !d_lambda || !d_az || !d_alambda ||           \
+            !d_iters || (!d_gG && !d_gC) || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))                                  \
+            return GBDPCG_ERR_INVALID;                                                                                              \
+        if (!schur_shape_ok<TYPE>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;                                                   \
+        const GradOperands<TYPE> f{d_z, d_lambda, d_gG, d_gC};                                                                      \
+        KktOperands<TYPE> k{nu, nullptr, d_C, d_gz, d_nglam, const_cast<TYPE *>(d_Ginv), d_az};                                     \
+        k.resolve = true;                                                                                                           \
+        k.shared = SHARED;                                                                                                          \
+        k.grad = &f;                                                                                                                \
+        return graph_create_impl<TYPE>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_alambda, d_r, d_p, tol, max_iter, d_iters,           \
+                                       d_max_iter_exit, out, -1, &k);                                                               \
+    }
+GBDPCG_KKT_BACKWARD(, f32, float, false)
+GBDPCG_KKT_BACKWARD(, f64, double, false)
+GBDPCG_KKT_BACKWARD(_shared, f32, float, true)
+GBDPCG_KKT_BACKWARD(_shared, f64, double, true)
+#undef GBDPCG_KKT_BACKWARD
 
 gbdpcg_status gbdpcg_csr_to_bt_f32(uint32_t n, uint32_t N, const uint32_t *row_ptr, const uint32_t *col_ind,
                                    const float *val, float *h_M)

@@ -257,4 +257,12 @@ template <typename T>
 hipError_t launch_admm_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *g, const T *lo, const T *hi, const T *rho,
                               const T *z, T *w, T *y, T *gt, T *res, hipStream_t s, bool init);
 
+// ---- kkt_grad.hip : the gradients of a scalar in the packed KKT blocks from the forward pair (z, lambda) and the adjoint pair
+// (az, alam), one launch.  gG has the layout of G, gC that of C; either may be null (not written):
+//     gQ_k = 1/2 (ax_k x_k' + x_k ax_k'), gR_k likewise with u;  [gA_k | gB_k] = -(alam_{k+1} z_k' + lam_{k+1} az_k')
+// shared: gG, gC are ONE problem's worth, the sum over the batch in the order b = 0, 1, ...
+template <typename T>
+hipError_t launch_kkt_grad(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *z, const T *lam, const T *az, const T *alam,
+                           T *gG, T *gC, hipStream_t s, bool shared = false);
+
 }  // namespace gbdpcg

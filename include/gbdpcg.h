@@ -674,6 +674,105 @@ gbdpcg_status gbdpcg_graph_create_admm_step_shared_f64(gbdpcg_handle_t h, uint32
                                                        double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res,
                                                        gbdpcg_graph_t *out);
 
+/* The backward pass: gradients of a scalar through (G, C, g, c) -> (z, lambda), on the device.  Forward convention as above:
+ * G z + g + C' lambda = 0, C z = c.  For a scalar l with upstream gradients gz = dl/dz (layout of d_g) and glam = dl/dlambda (layout
+ * of d_c) let (a_z, a_lambda) solve the SAME KKT matrix with the right-hand side (-gz, -glam).  The matrix is symmetric, so this
+ * is exactly gbdpcg_kkt_resolve_* called with g := gz, c := -glam on the S, Phi^-1 and G^-1 the forward pass left behind: the
+ * adjoint solve needs no kernel of its own.  Split a_z into ax_k, au_k and z into x_k, u_k; then (checked entry by entry against
+ * fp64 autograd through a dense solve of the same system, tests/test_kkt_grad_reference.py):
+ *     dl/dg = a_z                                   dl/dc = -a_lambda
+ *     dl/dQ_k(i,j) = 1/2 (ax_k,i x_k,j + x_k,i ax_k,j)                        and dl/dR_k likewise with u
+ *     dl/dA_k(i,j) = -(a_lambda,k+1,i x_k,j + lambda_k+1,i ax_k,j)
+ *     dl/dB_k(i,j) = -(a_lambda,k+1,i u_k,j + lambda_k+1,i au_k,j)
+ * The symmetrised form is the one for G because the library reads G as symmetric (the gradient with G entering as 1/2 (G + G')).
+ * Row block 0 of C is the identity and has no parameter.  With the _reg calls dl/drho_b = a_z' z of problem b and the gradient in
+ * G is unchanged; the backward pass works on whatever d_Ginv, d_S, d_Pinv the forward pass factored.  dl/dg, dl/dc and dl/drho
+ * are the adjoint pair itself or one dot product of it: the caller's.
+ *  - gbdpcg_kkt_grad_*: (d_z, d_lambda, d_az, d_alambda) -> d_gG (layout and size of d_G) and d_gC (layout and size of d_C), per
+ *    problem, one launch.  Each entry is two rounded products and one rounded add in the call's precision, then an exact * 0.5 (G)
+ *    or an exact negation (C), with the operands in the order written above: defined to the bit whatever the launch shape, and
+ *    gQ_k, gR_k come out bit-symmetric.  Every output element is written exactly once and does not depend on what the buffer
+ *    held: no atomics, no memset, no scratch.  A NaN in problem b's inputs stays in problem b's outputs.  Either output pointer
+ *    may be NULL, which skips it (both NULL: GBDPCG_ERR_INVALID); d_gC is not touched when N == 1.  No handle state:
+ *    asynchronous on `stream`, capturable, never allocates, needs nothing from gbdpcg_reserve.
+ *  - gbdpcg_kkt_grad_shared_*: d_gG, d_gC are ONE problem's worth, the sum over the batch of the expressions above -- the gradient
+ *    in the single G and C of a shared-matrix batch.  Problem b's term is the per-problem entry; the terms are added in the order
+ *    b = 0, 1, ..., batch - 1 by one thread per entry, without atomics: bit-identical from call to call, and batch = 1 gives the
+ *    bits of the per-problem call.
+ *  - gbdpcg_kkt_backward_*: gbdpcg_kkt_resolve_* with g := d_gz, c := d_nglam, writing d_alambda (its lambda: read first as the warm
+ *    start of the adjoint PCG, as d_lambda is for the forward pass) and d_az (its z), followed by gbdpcg_kkt_grad_* on (d_z,
+ *    d_lambda, d_az, d_alambda) on the same stream; same results as the two calls, bit for bit.  d_nglam holds MINUS dl/dlambda;
+ *    the caller passes zeros when l does not depend on lambda.  d_z, d_lambda are the forward point, read only.  d_gamma, d_r, d_p,
+ *    d_iters, d_max_iter_exit are those of the adjoint solve (d_r, d_p, d_max_iter_exit, d_Pinv may be NULL as in
+ *    gbdpcg_kkt_resolve_*, d_C when N == 1).  The solve runs in the handle's symmetric mode and path like any kkt_resolve.
+ *  - gbdpcg_kkt_backward_shared_*: the same on ONE problem's d_Ginv, d_C, d_S, d_Pinv (gbdpcg_kkt_resolve_shared_*), with the
+ *    summed d_gG, d_gC of gbdpcg_kkt_grad_shared_*; every vector stays per problem.
+ *  - the graph constructors capture both steps for fixed buffers and reserve what the solve needs, like those of
+ *    gbdpcg_kkt_resolve_*: replay after rewriting d_gz and d_nglam (and d_alambda, if no warm start is wanted) in place.
+ * Null handle or required pointer, nx, nu, N or batch == 0: GBDPCG_ERR_INVALID; a shape gbdpcg_form_schur_* refuses:
+ * GBDPCG_ERR_UNSUPPORTED; the backward calls also inherit every refusal of gbdpcg_kkt_resolve_* or its shared twin.  Refusals
+ * come before anything is written. */
+gbdpcg_status gbdpcg_kkt_grad_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_z,
+                                  const float *d_lambda, const float *d_az, const float *d_alambda, float *d_gG, float *d_gC,
+                                  void *stream);
+gbdpcg_status gbdpcg_kkt_grad_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_z,
+                                  const double *d_lambda, const double *d_az, const double *d_alambda, double *d_gG, double *d_gC,
+                                  void *stream);
+gbdpcg_status gbdpcg_kkt_grad_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_z,
+                                         const float *d_lambda, const float *d_az, const float *d_alambda, float *d_gG,
+                                         float *d_gC, void *stream);
+gbdpcg_status gbdpcg_kkt_grad_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_z,
+                                         const double *d_lambda, const double *d_az, const double *d_alambda, double *d_gG,
+                                         double *d_gC, void *stream);
+gbdpcg_status gbdpcg_kkt_backward_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_Ginv,
+                                      const float *d_C, const float *d_gz, const float *d_nglam, const float *d_S,
+                                      const float *d_Pinv, float *d_gamma, const float *d_z, const float *d_lambda, float *d_az,
+                                      float *d_alambda, float *d_r, float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                      uint8_t *d_max_iter_exit, float *d_gG, float *d_gC, void *stream);
+gbdpcg_status gbdpcg_kkt_backward_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_Ginv,
+                                      const double *d_C, const double *d_gz, const double *d_nglam, const double *d_S,
+                                      const double *d_Pinv, double *d_gamma, const double *d_z, const double *d_lambda, double *d_az,
+                                      double *d_alambda, double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                      uint8_t *d_max_iter_exit, double *d_gG, double *d_gC, void *stream);
+gbdpcg_status gbdpcg_kkt_backward_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                             const float *d_Ginv, const float *d_C, const float *d_gz, const float *d_nglam,
+                                             const float *d_S, const float *d_Pinv, float *d_gamma, const float *d_z,
+                                             const float *d_lambda, float *d_az, float *d_alambda, float *d_r, float *d_p,
+                                             float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                             float *d_gG, float *d_gC, void *stream);
+gbdpcg_status gbdpcg_kkt_backward_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                             const double *d_Ginv, const double *d_C, const double *d_gz, const double *d_nglam,
+                                             const double *d_S, const double *d_Pinv, double *d_gamma, const double *d_z,
+                                             const double *d_lambda, double *d_az, double *d_alambda, double *d_r, double *d_p,
+                                             double tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                             double *d_gG, double *d_gC, void *stream);
+gbdpcg_status gbdpcg_graph_create_kkt_backward_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                   const float *d_Ginv, const float *d_C, const float *d_gz, const float *d_nglam,
+                                                   const float *d_S, const float *d_Pinv, float *d_gamma, const float *d_z,
+                                                   const float *d_lambda, float *d_az, float *d_alambda, float *d_r, float *d_p,
+                                                   float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                                   float *d_gG, float *d_gC, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_kkt_backward_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                   const double *d_Ginv, const double *d_C, const double *d_gz,
+                                                   const double *d_nglam, const double *d_S, const double *d_Pinv, double *d_gamma,
+                                                   const double *d_z, const double *d_lambda, double *d_az, double *d_alambda,
+                                                   double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                   uint8_t *d_max_iter_exit, double *d_gG, double *d_gC, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_kkt_backward_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                          const float *d_Ginv, const float *d_C, const float *d_gz,
+                                                          const float *d_nglam, const float *d_S, const float *d_Pinv,
+                                                          float *d_gamma, const float *d_z, const float *d_lambda, float *d_az,
+                                                          float *d_alambda, float *d_r, float *d_p, float tol, uint32_t max_iter,
+                                                          uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_gG, float *d_gC,
+                                                          gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_kkt_backward_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                          const double *d_Ginv, const double *d_C, const double *d_gz,
+                                                          const double *d_nglam, const double *d_S, const double *d_Pinv,
+                                                          double *d_gamma, const double *d_z, const double *d_lambda, double *d_az,
+                                                          double *d_alambda, double *d_r, double *d_p, double tol,
+                                                          uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                                          double *d_gG, double *d_gC, gbdpcg_graph_t *out);
+
 /* CSR ingestion (f3): repacks a host CSR matrix (csr_t<T>, include/types.cuh:7-15) whose
  * sparsity lies inside the block-tridiagonal pattern into the [L|D|R] layout (host arrays).
  * Entries outside the pattern give GBDPCG_ERR_INVALID.  Implements what the stub overload

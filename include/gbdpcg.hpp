@@ -396,6 +396,52 @@ void kktResolveShared(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoi
     }
 }
 
+// ---- the backward pass (gbdpcg.h): gradients of a scalar in the packed blocks of G and C from the forward point (d_z, d_lambda) and
+// the adjoint pair (d_az, d_alambda); either output may be null.  The Shared forms write ONE problem's worth, summed over the batch.
+#define GBDPCG_HPP_GRAD(NAME, SYM)                                                                                                  \
+    template <typename T>                                                                                                           \
+    void NAME(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoints, uint32_t batch, const T *d_z, const T *d_lambda,       \
+              const T *d_az, const T *d_alambda, T *d_gG, T *d_gC, hipStream_t stream = nullptr)                                    \
+    {                                                                                                                               \
+        static_assert(gbdpcg_detail::is_f32<T> || gbdpcg_detail::is_f64<T>, #NAME "<T>: T is float or double");                     \
+        gbdpcg_handle_t h = gbdpcg_detail::handle();                                                                                \
+        if constexpr (gbdpcg_detail::is_f32<T>) {                                                                                   \
+            GBDPCG_CHECK(SYM##_f32(h, stateSize, controlSize, knotPoints, batch, d_z, d_lambda, d_az, d_alambda, d_gG, d_gC, stream), \
+                         #NAME);                                                                                                    \
+        } else {                                                                                                                    \
+            GBDPCG_CHECK(SYM##_f64(h, stateSize, controlSize, knotPoints, batch, d_z, d_lambda, d_az, d_alambda, d_gG, d_gC, stream), \
+                         #NAME);                                                                                                    \
+        }                                                                                                                           \
+    }
+GBDPCG_HPP_GRAD(kktGrad, gbdpcg_kkt_grad)
+GBDPCG_HPP_GRAD(kktGradShared, gbdpcg_kkt_grad_shared)
+#undef GBDPCG_HPP_GRAD
+
+// ... and with the adjoint solve in front: kktResolve with g := d_gz (dl/dz), c := d_nglam (MINUS dl/dlambda; zeros when l does not
+// depend on lambda), warm start from d_alambda, writing d_alambda and d_az, then kktGrad.  Same results as the two calls.
+#define GBDPCG_HPP_BACKWARD(NAME, SYM)                                                                                              \
+    template <typename T>                                                                                                           \
+    void NAME(uint32_t stateSize, uint32_t controlSize, uint32_t knotPoints, uint32_t batch, const T *d_Ginv, const T *d_C,         \
+              const T *d_gz, const T *d_nglam, const T *d_S, const T *d_Pinv, T *d_gamma, const T *d_z, const T *d_lambda, T *d_az,  \
+              T *d_alambda, uint32_t *d_iters, uint8_t *d_max_iter_exit, T *d_gG, T *d_gC, struct pcg_config<T> *config,            \
+              hipStream_t stream = nullptr)                                                                                         \
+    {                                                                                                                               \
+        static_assert(gbdpcg_detail::is_f32<T> || gbdpcg_detail::is_f64<T>, #NAME "<T>: T is float or double");                     \
+        gbdpcg_handle_t h = gbdpcg_detail::handle();                                                                                \
+        if constexpr (gbdpcg_detail::is_f32<T>) {                                                                                   \
+            GBDPCG_CHECK(SYM##_f32(h, stateSize, controlSize, knotPoints, batch, d_Ginv, d_C, d_gz, d_nglam, d_S, d_Pinv, d_gamma, d_z,  \
+                                   d_lambda, d_az, d_alambda, nullptr, nullptr, config->pcg_exit_tol, config->pcg_max_iter, d_iters,  \
+                                   d_max_iter_exit, d_gG, d_gC, stream), #NAME);                                                    \
+        } else {                                                                                                                    \
+            GBDPCG_CHECK(SYM##_f64(h, stateSize, controlSize, knotPoints, batch, d_Ginv, d_C, d_gz, d_nglam, d_S, d_Pinv, d_gamma, d_z,  \
+                                   d_lambda, d_az, d_alambda, nullptr, nullptr, config->pcg_exit_tol, config->pcg_max_iter, d_iters,  \
+                                   d_max_iter_exit, d_gG, d_gC, stream), #NAME);                                                    \
+        }                                                                                                                           \
+    }
+GBDPCG_HPP_BACKWARD(kktBackward, gbdpcg_kkt_backward)
+GBDPCG_HPP_BACKWARD(kktBackwardShared, gbdpcg_kkt_backward_shared)
+#undef GBDPCG_HPP_BACKWARD
+
 // ---- KKT residual norms of a point (z, lambda) on the device (gbdpcg.h): d_res[2b] = ||G z + g + C' lambda||_inf,
 // d_res[2b+1] = ||C z - c||_inf of problem b.  d_G holds the Hessians (not G^-1).  One launch on `stream`, capturable behind a step.
 template <typename T>
