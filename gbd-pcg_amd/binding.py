@@ -47,6 +47,11 @@ SYMBOLS = [
     "gbdpcg_admm_step_f32", "gbdpcg_admm_step_f64", "gbdpcg_graph_create_admm_step_f32", "gbdpcg_graph_create_admm_step_f64",
     "gbdpcg_admm_step_shared_f32", "gbdpcg_admm_step_shared_f64",
     "gbdpcg_graph_create_admm_step_shared_f32", "gbdpcg_graph_create_admm_step_shared_f64",
+    "gbdpcg_admm_lin_form_f32", "gbdpcg_admm_lin_form_f64", "gbdpcg_admm_lin_init_f32", "gbdpcg_admm_lin_init_f64",
+    "gbdpcg_admm_lin_update_f32", "gbdpcg_admm_lin_update_f64", "gbdpcg_admm_lin_step_f32", "gbdpcg_admm_lin_step_f64",
+    "gbdpcg_graph_create_admm_lin_step_f32", "gbdpcg_graph_create_admm_lin_step_f64",
+    "gbdpcg_admm_lin_step_shared_f32", "gbdpcg_admm_lin_step_shared_f64",
+    "gbdpcg_graph_create_admm_lin_step_shared_f32", "gbdpcg_graph_create_admm_lin_step_shared_f64",
     "gbdpcg_kkt_grad_f32", "gbdpcg_kkt_grad_f64", "gbdpcg_kkt_grad_shared_f32", "gbdpcg_kkt_grad_shared_f64",
     "gbdpcg_kkt_backward_f32", "gbdpcg_kkt_backward_f64", "gbdpcg_kkt_backward_shared_f32", "gbdpcg_kkt_backward_shared_f64",
     "gbdpcg_graph_create_kkt_backward_f32", "gbdpcg_graph_create_kkt_backward_f64",
@@ -89,6 +94,15 @@ def _resolve_argtypes(lib):
         for name in ("admm_step", "admm_step_shared"):
             getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = head + [vp, vp, vp] + solve + [vp, vp, vp, vp] + [vp]
             getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = head + [vp, vp, vp] + solve + [vp, vp, vp, vp] + [ctypes.POINTER(vp)]
+        # stage-wise linear rows: h, nx, nu, mx, mu, N, batch | ... with E in front of lo
+        lsizes = [vp, u32, u32, u32, u32, u32, u32]
+        getattr(lib, f"gbdpcg_admm_lin_form_{suf}").argtypes = lsizes + [vp, vp, vp, vp, vp]                          # G, E, rho, Gt, stream
+        getattr(lib, f"gbdpcg_admm_lin_init_{suf}").argtypes = lsizes + [vp, vp, vp, vp, vp] + [vp, vp, vp, vp]       # g, E, lo, hi, rho | w, y, gt, stream
+        getattr(lib, f"gbdpcg_admm_lin_update_{suf}").argtypes = lsizes + [vp, vp, vp, vp, vp] + [vp, vp, vp, vp, vp, vp]
+        for name in ("admm_lin_step", "admm_lin_step_shared"):   # Ginv, C, g, c | E, lo, hi, rho | the solve | w, y, gt, res | last
+            getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = lsizes + [vp, vp, vp, vp] + [vp, vp, vp, vp] + solve + [vp, vp, vp, vp] + [vp]
+            getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = (lsizes + [vp, vp, vp, vp] + [vp, vp, vp, vp] + solve +
+                                                                          [vp, vp, vp, vp] + [ctypes.POINTER(vp)])
         # the backward pass: z, lambda, az, alambda | gG, gC, stream
         for name in ("kkt_grad", "kkt_grad_shared"):
             getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = sizes + [vp, vp, vp, vp] + [vp, vp, vp]
@@ -651,6 +665,117 @@ class Solver:
         """Capture the shared-matrix iteration into a hipGraph (gbdpcg_graph_create_admm_step_shared_*)."""
         return self._graph_admm_step("admm_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
                                      max_iter, iters, max_iter_exit, z, w, y, gt, res)
+
+    # ---- stage-wise linear rows lo <= E z <= hi on a kept factorisation of G + rho E'E (include/gbdpcg.h).  E: [Ex_0 Eu_0 ... Ex_{N-1}]
+    # column-major blocks (one problem's in the shared calls); lo, hi, w, y have the layout of the rows; gt that of g
+    @staticmethod
+    def _lin_sizes(nx, nu, mx, mu, N):
+        """(nz, nw, ne, ng): elements per problem of g / the rows / E / G."""
+        return (nx + nu) * N - nu, (mx + mu) * N - mu, (mx * nx + mu * nu) * N - mu * nu, (nx * nx + nu * nu) * N - nu * nu
+
+    def _lin(self, g, batch, nx, nu, mx, mu, N, E, rows, vectors, mats=None):
+        """The sizes of E (`mats` problems' worth, default batch), of the row arrays and of the arrays laid out like g."""
+        nz, nw, ne, _ = self._lin_sizes(nx, nu, mx, mu, N)
+        for t, cnt in [(E, (batch if mats is None else mats) * ne)] + [(t, batch * nw) for t in rows] + [(t, batch * nz) for t in vectors]:
+            assert t is not None and t.is_cuda and t.is_contiguous() and t.numel() == cnt and t.dtype == g.dtype
+
+    def admm_lin_form(self, nx, nu, mx, mu, N, batch, G, E, rho, Gt=None, stream=None):
+        """gbdpcg_admm_lin_form_*: Gt = G + rho E'E in the layout of G (Gt may be G).  Returns Gt."""
+        import torch
+        suf, _ = _suffix(G)
+        if Gt is None:
+            Gt = torch.empty_like(G)
+        _, _, ne, ng = self._lin_sizes(nx, nu, mx, mu, N)
+        for t, cnt in ((G, batch * ng), (Gt, batch * ng), (E, batch * ne)):
+            assert t is not None and t.is_cuda and t.is_contiguous() and t.numel() == cnt and t.dtype == G.dtype
+        fn = getattr(self.lib, f"gbdpcg_admm_lin_form_{suf}")
+        self._check(fn(self.h, nx, nu, mx, mu, N, batch, _p(G), _p(E), _p(self._rho(rho, batch, G)), _p(Gt), self._stream(stream)),
+                    "admm_lin_form")
+        return Gt
+
+    def admm_lin_init(self, nx, nu, mx, mu, N, batch, g, E, lo, hi, rho, w, y, gt=None, stream=None):
+        """gbdpcg_admm_lin_init_*: w <- clip(w, lo, hi), gt <- g - rho E'(w - y); y is left alone.  Returns gt."""
+        import torch
+        suf, _ = _suffix(g)
+        if gt is None:
+            gt = torch.empty_like(g)
+        self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y), (g, gt))
+        fn = getattr(self.lib, f"gbdpcg_admm_lin_init_{suf}")
+        self._check(fn(self.h, nx, nu, mx, mu, N, batch, _p(g), _p(E), _p(lo), _p(hi), _p(self._rho(rho, batch, g)), _p(w), _p(y),
+                       _p(gt), self._stream(stream)), "admm_lin_init")
+        return gt
+
+    def admm_lin_update(self, nx, nu, mx, mu, N, batch, g, E, lo, hi, rho, z, w, y, gt, res=None, stream=None):
+        """gbdpcg_admm_lin_update_*: the update behind a solve that wrote z -- w, y, gt in place; returns the [batch, 2] tensor of
+        (||E z - w||_inf, rho ||E'(w - w_old)||_inf) per problem."""
+        import torch
+        suf, _ = _suffix(g)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=g.dtype, device=g.device)
+        assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == g.dtype
+        self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y), (g, z, gt))
+        fn = getattr(self.lib, f"gbdpcg_admm_lin_update_{suf}")
+        self._check(fn(self.h, nx, nu, mx, mu, N, batch, _p(g), _p(E), _p(lo), _p(hi), _p(self._rho(rho, batch, g)), _p(z), _p(w),
+                       _p(y), _p(gt), _p(res), self._stream(stream)), "admm_lin_update")
+        return res.view(batch, 2)
+
+    def _admm_lin_args(self, shared, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter,
+                       iters, mie, z, w, y, gt, res):
+        suf, _ = _suffix(g)
+        assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == g.dtype
+        self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y), (g, z, gt), mats=1 if shared else None)
+        return suf, (self.h, nx, nu, mx, mu, N, batch, _p(Ginv), _p(C), _p(g), _p(c), _p(E), _p(lo), _p(hi),
+                     _p(self._rho(rho, batch, g)), _p(S), _p(Pinv), _p(gamma), _p(lam), _p(r), _p(p), tol, max_iter, _p(iters), _p(mie),
+                     _p(z), _p(w), _p(y), _p(gt), _p(res))
+
+    def _admm_lin_step(self, name, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, r, p,
+                       tol, max_iter, iters, max_iter_exit, stream):
+        import torch
+        if iters is None:
+            iters = torch.zeros(batch, dtype=torch.int32, device=g.device)
+        if max_iter_exit is None:
+            max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=g.device)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=g.dtype, device=g.device)
+        suf, args = self._admm_lin_args(name.endswith("shared"), nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
+                                        lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
+        self._check(getattr(self.lib, f"gbdpcg_{name}_{suf}")(*args, self._stream(stream)), name)
+        return iters, max_iter_exit, res.view(batch, 2)
+
+    def _graph_admm_lin_step(self, name, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter,
+                             iters, max_iter_exit, z, w, y, gt, res):
+        suf, args = self._admm_lin_args(name.endswith("shared"), nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
+                                        lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
+        gr = ctypes.c_void_p()
+        self._check(getattr(self.lib, f"gbdpcg_graph_create_{name}_{suf}")(*args, ctypes.byref(gr)), f"graph_create_{name}")
+        return Graph(self, gr, keep=(Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, iters, max_iter_exit, z, w, y, gt, res))
+
+    def admm_lin_step(self, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=None, r=None,
+                      p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_admm_lin_step_*: kkt_resolve with gt in the place of g (warm start from lam), then admm_lin_update, one call.
+        Returns (iters, flags, res [batch, 2])."""
+        return self._admm_lin_step("admm_lin_step", nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y,
+                                   gt, res, r, p, tol, max_iter, iters, max_iter_exit, stream)
+
+    def graph_admm_lin_step(self, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                            max_iter_exit, z, w, y, gt, res):
+        """Capture one iteration into a hipGraph (gbdpcg_graph_create_admm_lin_step_*): replay it once per iteration; the graph
+        keeps rho's pointer."""
+        return self._graph_admm_lin_step("admm_lin_step", nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r,
+                                         p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
+
+    def admm_lin_step_shared(self, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=None,
+                             r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_admm_lin_step_shared_*: ONE Ginv, C, S, Pinv and E for `batch` problems; bounds, rho and the state stay per
+        problem."""
+        return self._admm_lin_step("admm_lin_step_shared", nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z,
+                                   w, y, gt, res, r, p, tol, max_iter, iters, max_iter_exit, stream)
+
+    def graph_admm_lin_step_shared(self, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                   max_iter, iters, max_iter_exit, z, w, y, gt, res):
+        """Capture the shared-matrix iteration into a hipGraph (gbdpcg_graph_create_admm_lin_step_shared_*)."""
+        return self._graph_admm_lin_step("admm_lin_step_shared", nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
+                                         lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
 
     # ---- the backward pass (include/gbdpcg.h): gradients of a scalar in G and C from the forward point (z, lam) and the adjoint pair
     # (az, alam), which is kkt_resolve with g := dl/dz, c := -dl/dlambda on the kept factorisation

@@ -257,6 +257,23 @@ template <typename T>
 hipError_t launch_admm_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *g, const T *lo, const T *hi, const T *rho,
                               const T *z, T *w, T *y, T *gt, T *res, hipStream_t s, bool init);
 
+// ---- admm_lin.hip : ADMM with stage-wise linear rows lo <= E z <= hi (layouts in include/gbdpcg.h), two kernels.
+//     form:   Gt = G + rho_b E'E per diagonal block, one lane per entry (Gt may be G)
+//     update: w <- clip(E z + y), y <- (E z + y) - w, gt <- g - rho_b E'(w - y), res[2b] = ||E z - w||_inf,
+//             res[2b+1] = rho_b ||E'(w - w_old)||_inf; one workgroup per problem, the horizon in chunks of admm_lin_knot_chunk knots
+// init: w <- clip(w), gt <- g - rho_b E'(w - y); y is not written, z and res are not looked at (may be null).
+// shared: E is one problem's blocks, used by every problem of the batch.
+template <typename T>
+hipError_t launch_admm_lin_form(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *G, const T *E,
+                                const T *rho, T *Gt, hipStream_t s);
+template <typename T>
+hipError_t launch_admm_lin_update(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *g, const T *E,
+                                  const T *lo, const T *hi, const T *rho, const T *z, T *w, T *y, T *gt, T *res, hipStream_t s,
+                                  bool init, bool shared = false);
+// (mx, mu <= 64 and one knot's E blocks, z, t, d within the kernel's LDS)
+template <typename T> bool admm_lin_shape_ok(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu);
+uint32_t admm_lin_knot_chunk(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu);
+
 // ---- kkt_grad.hip : the gradients of a scalar in the packed KKT blocks from the forward pair (z, lambda) and the adjoint pair
 // (az, alam), one launch.  gG has the layout of G, gC that of C; either may be null (not written):
 //     gQ_k = 1/2 (ax_k x_k' + x_k ax_k'), gR_k likewise with u;  [gA_k | gB_k] = -(alam_{k+1} z_k' + lam_{k+1} az_k')

@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""What the launches of ADMM with stage-wise linear inequality rows cost, next to the box update and the solve, in ONE process on
+one device:
+    python gbd-pcg_amd/tools/admm_lin_time.py [--warmup W] [--steps K] [--rounds R] > profiles/rNN_admm_lin.txt
+
+At 1024 x (nx 14, nu 7, N 128) with mx = 4, mu = 2 random rows, fp32 and fp64: the gbdpcg_admm_lin_update_* launch alone, the
+gbdpcg_admm_lin_form_* launch alone and the gbdpcg_admm_update_* (box) launch alone (K launches between two device events each),
+then windows of K graph replays, kkt_resolve / admm_lin_step alternating, R rounds; median and range over the rounds.  The
+factorisation is that of G + rho E'E (admm_lin_form, kkt_step; rho = 2), the bounds hold every row within half of the largest row of
+the solution without them, and every replay starts from lambda = 0 (the zero fill is inside every window alike).
+Algorithmic bytes, s = element size:
+    lin update  (6 nw + 3 nz + ne) s + 3 s per problem     w, y, lo, hi in, w, y out; z, g in, gt out; E once; rho and two norms
+    lin form    (2 ng + ne) s + s per problem              G in, Gt out; E once (its re-reads are the caches'); rho
+    box update  9 nz s + 3 s per problem                   (tools/admm_time.py)
+each over its time, against the box update of the same run and against the HBM rates: 8 TB/s peak, about 6.3 TB/s achievable."""
+import argparse
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, __file__.rsplit("/gbd-pcg_amd/", 1)[0])
+from gbd_pcg_amd import binding  # noqa: E402
+from oracle import schur_oracle as so  # noqa: E402
+
+HBM_PEAK, HBM_ACHIEVABLE = 8.0e12, 6.3e12   # bytes / s
+
+
+def window(fn, count):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(count):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / count   # ms per call
+
+
+def stat(v):
+    return f"{statistics.median(v):.4f} ms (min {min(v):.4f}, max {max(v):.4f})"
+
+
+def rate(nbytes, ms):
+    r = nbytes / (ms * 1e-3)
+    return f"{nbytes / 1e6:.1f} MB -> {r / 1e12:.2f} TB/s, {100.0 * r / HBM_PEAK:.0f} % of peak, {100.0 * r / HBM_ACHIEVABLE:.0f} % of achievable"
+
+
+def one_shape(s, nx, nu, N, B, mx, mu, dtype, a):
+    td = torch.float32 if dtype == np.float32 else torch.float64
+    base = so.gen(nx, nu, N, seed=77, batch=8, dtype=dtype)
+    arr = {k: np.tile(base[k], ((B + 7) // 8, 1))[:B] for k in "GCgc"}
+    arr["g"] = arr["g"] * (1.0 + np.arange(B, dtype=dtype)[:, None] / B)
+    G, C, g, c = (torch.from_numpy(np.ascontiguousarray(arr[k].reshape(-1))).cuda() for k in "GCgc")
+    sv, sw = nx + nu, mx + mu
+    nz, nw, ne, ng = sv * N - nu, sw * N - mu, (mx * nx + mu * nu) * N - mu * nu, (nx * nx + nu * nu) * N - nu * nu
+    E = torch.from_numpy(np.tile((0.5 * np.random.default_rng(3).standard_normal(ne)).astype(dtype), B)).cuda()
+    rho = torch.full((B,), 2.0, dtype=td, device="cuda")
+    S = torch.empty(B * 3 * nx * nx * N, dtype=td, device="cuda")
+    Pinv, Ginv, Gt = torch.empty_like(S), torch.empty_like(G), torch.empty_like(G)
+    gamma = torch.empty(B * nx * N, dtype=td, device="cuda")
+    lam, z = torch.zeros_like(gamma), torch.empty_like(g)
+    it = torch.zeros(B, dtype=torch.int32, device="cuda")
+    fl = torch.zeros(B, dtype=torch.uint8, device="cuda")
+    res, bres = torch.empty(B, 2, dtype=td, device="cuda"), torch.empty(B, 2, dtype=td, device="cuda")
+    s.admm_lin_form(nx, nu, mx, mu, N, B, G, E, rho, Gt=Gt)
+    s.kkt_step(nx, nu, N, B, Gt, C, g, c, S, gamma, Ginv, Pinv, lam, z, tol=a.tol, max_iter=a.max_iter, iters=it, max_iter_exit=fl)
+    torch.cuda.synchronize()
+    # every row within half of the largest row of the solution without the rows
+    Ed = torch.zeros(nw, nz, dtype=td, device="cuda")
+    Eh = E[:ne]
+    for k in range(N):
+        eo, ro, co = k * (mx * nx + mu * nu), k * sw, k * sv
+        Ed[ro:ro + mx, co:co + nx] = Eh[eo:eo + mx * nx].view(nx, mx).T
+        if k < N - 1:
+            Ed[ro + mx:ro + sw, co + nx:co + sv] = Eh[eo + mx * nx:eo + mx * nx + mu * nu].view(nu, mu).T
+    bound = 0.5 * (z.view(B, nz) @ Ed.T).abs().amax(dim=1, keepdim=True)
+    lo, hi = (-bound).expand(B, nw).reshape(-1).contiguous(), bound.expand(B, nw).reshape(-1).contiguous()
+    w, y = torch.zeros_like(lo), torch.zeros_like(lo)
+    gt = s.admm_lin_init(nx, nu, mx, mu, N, B, g, E, lo, hi, rho, w, y)
+    g_res = s.graph_kkt_resolve(nx, nu, N, B, Ginv, C, gt, c, S, Pinv, gamma, lam, None, None, a.tol, a.max_iter, it, fl, z)
+    g_lin = s.graph_admm_lin_step(nx, nu, mx, mu, N, B, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, None, None, a.tol, a.max_iter,
+                                  it, fl, z, w, y, gt, res)
+    # the box update of the same run, on buffers of its own in the layout of z
+    blo, bhi = torch.full_like(g, -1.0), torch.full_like(g, 1.0)
+    bw, by, bgt = torch.zeros_like(g), torch.zeros_like(g), torch.empty_like(g)
+
+    def replay(gr):
+        lam.zero_()
+        gr.launch()
+
+    calls = {"lin update": lambda: s.admm_lin_update(nx, nu, mx, mu, N, B, g, E, lo, hi, rho, z, w, y, gt, res=res),
+             "lin form": lambda: s.admm_lin_form(nx, nu, mx, mu, N, B, G, E, rho, Gt=Gt),
+             "box update": lambda: s.admm_update(nx, nu, N, B, g, blo, bhi, rho, z, bw, by, bgt, res=bres),
+             "resolve replay": lambda: replay(g_res), "lin step replay": lambda: replay(g_lin)}
+    for _ in range(30):      # a few iterations first: the loop does what it is for
+        g_lin.launch()
+    torch.cuda.synchronize()
+    print(f"  after 30 iterations: max ||E z - w||_inf {float(res[:, 0].max()):.2e}, max rho ||E'(w+ - w)||_inf {float(res[:, 1].max()):.2e}, "
+          f"{int((y != 0).sum())} of {nw * B} rows active, PCG iterations mean {float(it.float().mean()):.2f}, ran out {int(fl.sum())}")
+    for _ in range(2):
+        for fn in calls.values():
+            window(fn, a.warmup)
+    t = {k: [] for k in calls}
+    for _ in range(a.rounds):
+        for k, fn in calls.items():
+            t[k].append(window(fn, a.steps))
+    es = np.dtype(dtype).itemsize
+    must = {"lin update": ((6 * nw + 3 * nz + ne) * es + 3 * es) * B, "lin form": ((2 * ng + ne) * es + es) * B,
+            "box update": (9 * nz * es + 3 * es) * B}
+    med = {k: statistics.median(v) for k, v in t.items()}
+    for k in ("lin update", "lin form", "box update"):
+        print(f"  {k + ' launch alone':30s} {stat(t[k])}; algorithmic bytes {rate(must[k], med[k])}")
+    print(f"  {'kkt_resolve graph replay':30s} {stat(t['resolve replay'])}")
+    print(f"  {'admm_lin_step graph replay':30s} {stat(t['lin step replay'])}")
+    bl, bb = must["lin update"] / med["lin update"], must["box update"] / med["box update"]
+    print(f"  lin update / box update: time {med['lin update'] / med['box update']:.2f} x, bytes {must['lin update'] / must['box update']:.2f} x, "
+          f"bytes over time {bl / bb:.2f} x;  lin update alone / resolve replay {100.0 * med['lin update'] / med['resolve replay']:.1f} %;  "
+          f"lin step replay - resolve replay {1e3 * (med['lin step replay'] - med['resolve replay']):.1f} us")
+    for gr in (g_res, g_lin):
+        gr.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--tol", type=float, default=1e-6)
+    ap.add_argument("--max-iter", type=int, default=25)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the MI355X: there is no CPU path"
+    s = binding.Solver(0)
+    print(f"# admm_lin_time.py --warmup {a.warmup} --steps {a.steps} --rounds {a.rounds} --tol {a.tol} --max-iter {a.max_iter}; "
+          f"{torch.cuda.get_device_name(0)}; {s.lib.gbdpcg_version().decode()}")
+    for dtype in (np.float32, np.float64):
+        nx, nu, N, B, mx, mu = 14, 7, 128, 1024, 4, 2
+        print(f"{B} x (nx {nx}, nu {nu}, N {N}), mx {mx}, mu {mu}, {np.dtype(dtype).name}")
+        one_shape(s, nx, nu, N, B, mx, mu, dtype, a)
+    s.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -674,6 +674,129 @@ gbdpcg_status gbdpcg_graph_create_admm_step_shared_f64(gbdpcg_handle_t h, uint32
                                                        double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res,
                                                        gbdpcg_graph_t *out);
 
+/* Stage-wise linear inequality rows on a kept linearisation: the ADMM iterations of the box section with a matrix in front of z.
+ * Problem b is
+ *     minimise 1/2 z'Gz + g'z   subject to   Cz = c,   lo <= E z <= hi
+ * E is block-diagonal with the blocks of G: Ex_k (mx x nx) acts on x_k, Eu_k (mu x nu) on u_k, the row counts mx, mu are the
+ * same for every knot (rows that mix x_k and u_k are out of scope: G has no x-u block for E'E to land in).  The box is E = I.
+ * Layouts, one problem after the other, every block column-major, all on the device in the call's precision:
+ *     d_E                    [Ex_0 Eu_0 Ex_1 Eu_1 ... Ex_{N-1}]        (mx nx + mu nu) N - mu nu elements per problem
+ *     d_lo, d_hi, d_w, d_y   rows [mx | mu | mx | ... | mx]            (mx + mu) N - mu per problem; -Inf / +Inf: no bound
+ *     d_Gt as d_G, d_gt as d_g, d_rho `batch` elements, d_res 2 batch.
+ * E z is split into E z (z satisfies the dynamics) and a copy w between the bounds, held together by the scaled multiplier y of
+ * E z = w with a per-problem penalty rho_b > 0; the matrices of the solve belong to Gt = G + rho E'E, which stays block-diagonal
+ * in the layout of d_G.  Every line below is ONE IEEE operation or a comparison, so every output is defined to the bit whatever
+ * the launch shape.  A "chain" is acc = +0; acc = fma(a_i, b_i, acc) over the stated index in ascending order.
+ *  - gbdpcg_admm_lin_form_*: per diagonal block P(i,j) = chain over rows r of E(r,i) E(r,j), Gt(i,j) = fma(rho_b, P(i,j), G(i,j)).
+ *    Gt is bit-symmetric when G is; a block with no rows gives fma(rho_b, +0, G).  Every element is written once by the lane that
+ *    read it: d_Gt == d_G is allowed.  The caller then runs gbdpcg_kkt_step_* on d_Gt (or gbdpcg_kkt_step_reg_* for an additional
+ *    sigma I); the d_Ginv, d_S, d_Pinv it writes are kept for every iteration.
+ *  - gbdpcg_admm_lin_update_*: after the resolve with d_gt in the place of d_g has written z,
+ *        v_r  = chain over columns j of E(r,j) z_j           (rows of the block that owns z's segment)
+ *        s_r  = fl(v_r + y_r)
+ *        w+_r = s_r < lo_r ? lo_r : (s_r > hi_r ? hi_r : s_r)                    comparisons: a NaN stays NaN
+ *        y+_r = fl(s_r - w+_r)                                                   exactly 0 where nothing was clipped
+ *        t_r  = fl(w+_r - y+_r);   d_r = fl(w+_r - w_r)
+ *        u_j  = chain over rows r of E(r,j) t_r;   e_j = chain over rows r of E(r,j) d_r
+ *        gt_j = fma(-rho_b, u_j, g_j)
+ *        d_res[2b]   = max_r |fl(v_r - w+_r)|                                    primal residual || E z - w ||_inf
+ *        d_res[2b+1] = max_j |fl(rho_b e_j)|                                     dual residual rho || E'(w+ - w) ||_inf
+ *    The maxima are those of gbdpcg_kkt_residual_* (over bit patterns, a NaN on top); d_res is overwritten whatever it held.  The
+ *    multiplier of the rows is mu = rho y: y_r > 0 where the upper bound is active, < 0 where the lower one is, and
+ *    G z + g + C' lambda + rho E'y -> 0.  d_w satisfies the bounds exactly, E z agrees with it to d_res[2b].
+ *  - gbdpcg_admm_lin_init_*: before the first iteration.  w <- clip(w) by the same comparisons, y is not written,
+ *    t = fl(w - y), gt_j = fma(-rho_b, u_j, g_j); z and res are not touched.
+ *  - gbdpcg_admm_lin_step_*: gbdpcg_kkt_resolve_* with d_gt for d_g, then the update on the same stream, the same bits as the two
+ *    calls.  gbdpcg_graph_create_admm_lin_step_* is its graph form: it keeps the POINTER d_rho (rewriting rho in place changes the
+ *    update, not the matrices), reserves what the solve needs, and nothing allocates under capture.
+ *  - the _shared twins of step and graph take ONE problem's d_Ginv, d_C, d_S, d_Pinv AND d_E; the vectors, the bounds, d_rho,
+ *    d_w, d_y, d_gt and d_res stay per problem.
+ *  - d_lo, d_hi, d_rho and d_E are NOT validated on the device: bad values stay inside their own problem.
+ * Refused before anything is written: null handle or required pointer, nx, nu, N or batch == 0, no row at all (mx = mu = 0, or
+ * mx = 0 with N = 1): GBDPCG_ERR_INVALID.  mx or mu above 64, or a knot whose blocks of E with its x, u and two copies of its rows
+ * exceed 60 KB (the update kernel stages them in LDS): GBDPCG_ERR_UNSUPPORTED.  Step and graph inherit every refusal of
+ * gbdpcg_kkt_resolve_* or its shared twin (d_r, d_p, d_max_iter_exit and d_Pinv may be NULL, d_C when N == 1). */
+gbdpcg_status gbdpcg_admm_lin_form_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                       uint32_t batch, const float *d_G, const float *d_E, const float *d_rho, float *d_Gt,
+                                       void *stream);
+gbdpcg_status gbdpcg_admm_lin_form_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                       uint32_t batch, const double *d_G, const double *d_E, const double *d_rho, double *d_Gt,
+                                       void *stream);
+gbdpcg_status gbdpcg_admm_lin_init_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                       uint32_t batch, const float *d_g, const float *d_E, const float *d_lo, const float *d_hi,
+                                       const float *d_rho, float *d_w, float *d_y, float *d_gt, void *stream);
+gbdpcg_status gbdpcg_admm_lin_init_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                       uint32_t batch, const double *d_g, const double *d_E, const double *d_lo,
+                                       const double *d_hi, const double *d_rho, double *d_w, double *d_y, double *d_gt,
+                                       void *stream);
+gbdpcg_status gbdpcg_admm_lin_update_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                         uint32_t batch, const float *d_g, const float *d_E, const float *d_lo, const float *d_hi,
+                                         const float *d_rho, const float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res,
+                                         void *stream);
+gbdpcg_status gbdpcg_admm_lin_update_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                         uint32_t batch, const double *d_g, const double *d_E, const double *d_lo,
+                                         const double *d_hi, const double *d_rho, const double *d_z, double *d_w, double *d_y,
+                                         double *d_gt, double *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_lin_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                       uint32_t batch, const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                       const float *d_E, const float *d_lo, const float *d_hi, const float *d_rho,
+                                       const float *d_S, const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r,
+                                       float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                       float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_lin_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                       uint32_t batch, const double *d_Ginv, const double *d_C, const double *d_g,
+                                       const double *d_c, const double *d_E, const double *d_lo, const double *d_hi,
+                                       const double *d_rho, const double *d_S, const double *d_Pinv, double *d_gamma,
+                                       double *d_lambda, double *d_r, double *d_p, double tol, uint32_t max_iter,
+                                       uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y,
+                                       double *d_gt, double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_lin_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                    uint32_t N, uint32_t batch, const float *d_Ginv, const float *d_C,
+                                                    const float *d_g, const float *d_c, const float *d_E, const float *d_lo,
+                                                    const float *d_hi, const float *d_rho, const float *d_S, const float *d_Pinv,
+                                                    float *d_gamma, float *d_lambda, float *d_r, float *d_p, float tol,
+                                                    uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_z,
+                                                    float *d_w, float *d_y, float *d_gt, float *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_lin_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                    uint32_t N, uint32_t batch, const double *d_Ginv, const double *d_C,
+                                                    const double *d_g, const double *d_c, const double *d_E, const double *d_lo,
+                                                    const double *d_hi, const double *d_rho, const double *d_S,
+                                                    const double *d_Pinv, double *d_gamma, double *d_lambda, double *d_r,
+                                                    double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                    uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y, double *d_gt,
+                                                    double *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_admm_lin_step_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                              uint32_t batch, const float *d_Ginv, const float *d_C, const float *d_g,
+                                              const float *d_c, const float *d_E, const float *d_lo, const float *d_hi,
+                                              const float *d_rho, const float *d_S, const float *d_Pinv, float *d_gamma,
+                                              float *d_lambda, float *d_r, float *d_p, float tol, uint32_t max_iter,
+                                              uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y,
+                                              float *d_gt, float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_lin_step_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                              uint32_t batch, const double *d_Ginv, const double *d_C, const double *d_g,
+                                              const double *d_c, const double *d_E, const double *d_lo, const double *d_hi,
+                                              const double *d_rho, const double *d_S, const double *d_Pinv, double *d_gamma,
+                                              double *d_lambda, double *d_r, double *d_p, double tol, uint32_t max_iter,
+                                              uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y,
+                                              double *d_gt, double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_lin_step_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                           uint32_t N, uint32_t batch, const float *d_Ginv, const float *d_C,
+                                                           const float *d_g, const float *d_c, const float *d_E,
+                                                           const float *d_lo, const float *d_hi, const float *d_rho,
+                                                           const float *d_S, const float *d_Pinv, float *d_gamma, float *d_lambda,
+                                                           float *d_r, float *d_p, float tol, uint32_t max_iter,
+                                                           uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_z, float *d_w,
+                                                           float *d_y, float *d_gt, float *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_lin_step_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                           uint32_t N, uint32_t batch, const double *d_Ginv, const double *d_C,
+                                                           const double *d_g, const double *d_c, const double *d_E,
+                                                           const double *d_lo, const double *d_hi, const double *d_rho,
+                                                           const double *d_S, const double *d_Pinv, double *d_gamma,
+                                                           double *d_lambda, double *d_r, double *d_p, double tol,
+                                                           uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                                           double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res,
+                                                           gbdpcg_graph_t *out);
+
 /* The backward pass: gradients of a scalar through (G, C, g, c) -> (z, lambda), on the device.  Forward convention as above:
  * G z + g + C' lambda = 0, C z = c.  For a scalar l with upstream gradients gz = dl/dz (layout of d_g) and glam = dl/dlambda (layout
  * of d_c) let (a_z, a_lambda) solve the SAME KKT matrix with the right-hand side (-gz, -glam).  The matrix is symmetric, so this
