@@ -52,6 +52,11 @@ SYMBOLS = [
     "gbdpcg_graph_create_admm_lin_step_f32", "gbdpcg_graph_create_admm_lin_step_f64",
     "gbdpcg_admm_lin_step_shared_f32", "gbdpcg_admm_lin_step_shared_f64",
     "gbdpcg_graph_create_admm_lin_step_shared_f32", "gbdpcg_graph_create_admm_lin_step_shared_f64",
+    "gbdpcg_admm_soc_init_f32", "gbdpcg_admm_soc_init_f64", "gbdpcg_admm_soc_update_f32", "gbdpcg_admm_soc_update_f64",
+    "gbdpcg_admm_soc_step_f32", "gbdpcg_admm_soc_step_f64",
+    "gbdpcg_graph_create_admm_soc_step_f32", "gbdpcg_graph_create_admm_soc_step_f64",
+    "gbdpcg_admm_soc_step_shared_f32", "gbdpcg_admm_soc_step_shared_f64",
+    "gbdpcg_graph_create_admm_soc_step_shared_f32", "gbdpcg_graph_create_admm_soc_step_shared_f64",
     "gbdpcg_kkt_grad_f32", "gbdpcg_kkt_grad_f64", "gbdpcg_kkt_grad_shared_f32", "gbdpcg_kkt_grad_shared_f64",
     "gbdpcg_kkt_backward_f32", "gbdpcg_kkt_backward_f64", "gbdpcg_kkt_backward_shared_f32", "gbdpcg_kkt_backward_shared_f64",
     "gbdpcg_graph_create_kkt_backward_f32", "gbdpcg_graph_create_kkt_backward_f64",
@@ -102,6 +107,14 @@ def _resolve_argtypes(lib):
         for name in ("admm_lin_step", "admm_lin_step_shared"):   # Ginv, C, g, c | E, lo, hi, rho | the solve | w, y, gt, res | last
             getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = lsizes + [vp, vp, vp, vp] + [vp, vp, vp, vp] + solve + [vp, vp, vp, vp] + [vp]
             getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = (lsizes + [vp, vp, vp, vp] + [vp, vp, vp, vp] + solve +
+                                                                          [vp, vp, vp, vp] + [ctypes.POINTER(vp)])
+        # second-order cone rows: h, nx, nu, mx, mu, lx, qx, lu, qu, N, batch | the lists of admm_lin
+        csizes = [vp] + [u32] * 10
+        getattr(lib, f"gbdpcg_admm_soc_init_{suf}").argtypes = csizes + [vp, vp, vp, vp, vp] + [vp, vp, vp, vp]
+        getattr(lib, f"gbdpcg_admm_soc_update_{suf}").argtypes = csizes + [vp, vp, vp, vp, vp] + [vp, vp, vp, vp, vp, vp]
+        for name in ("admm_soc_step", "admm_soc_step_shared"):
+            getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = csizes + [vp, vp, vp, vp] + [vp, vp, vp, vp] + solve + [vp, vp, vp, vp] + [vp]
+            getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = (csizes + [vp, vp, vp, vp] + [vp, vp, vp, vp] + solve +
                                                                           [vp, vp, vp, vp] + [ctypes.POINTER(vp)])
         # the backward pass: z, lambda, az, alambda | gG, gC, stream
         for name in ("kkt_grad", "kkt_grad_shared"):
@@ -776,6 +789,89 @@ class Solver:
         """Capture the shared-matrix iteration into a hipGraph (gbdpcg_graph_create_admm_lin_step_shared_*)."""
         return self._graph_admm_lin_step("admm_lin_step_shared", nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
                                          lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
+
+    # ---- second-order cone rows next to the linear ones (include/gbdpcg.h): cones = (lx, qx, lu, qu) -- the first lx rows of an x
+    # block are linear, the rest cones of dimension qx, head row first; on a cone row lo holds the offset f and hi is not read.  The
+    # formation is admm_lin_form.
+    def admm_soc_init(self, nx, nu, mx, mu, cones, N, batch, g, E, lo, hi, rho, w, y, gt=None, stream=None):
+        """gbdpcg_admm_soc_init_*: w <- its projection on the bounds / cones, gt <- g - rho E'(w - f - y); y is left alone.  Returns gt."""
+        import torch
+        suf, _ = _suffix(g)
+        if gt is None:
+            gt = torch.empty_like(g)
+        self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y), (g, gt))
+        fn = getattr(self.lib, f"gbdpcg_admm_soc_init_{suf}")
+        self._check(fn(self.h, nx, nu, mx, mu, *cones, N, batch, _p(g), _p(E), _p(lo), _p(hi), _p(self._rho(rho, batch, g)), _p(w), _p(y),
+                       _p(gt), self._stream(stream)), "admm_soc_init")
+        return gt
+
+    def admm_soc_update(self, nx, nu, mx, mu, cones, N, batch, g, E, lo, hi, rho, z, w, y, gt, res=None, stream=None):
+        """gbdpcg_admm_soc_update_*: the update behind a solve that wrote z -- w, y, gt in place; returns the [batch, 2] tensor of
+        (||E z + f - w||_inf, rho ||E'(w - w_old)||_inf) per problem."""
+        import torch
+        suf, _ = _suffix(g)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=g.dtype, device=g.device)
+        assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == g.dtype
+        self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y), (g, z, gt))
+        fn = getattr(self.lib, f"gbdpcg_admm_soc_update_{suf}")
+        self._check(fn(self.h, nx, nu, mx, mu, *cones, N, batch, _p(g), _p(E), _p(lo), _p(hi), _p(self._rho(rho, batch, g)), _p(z), _p(w),
+                       _p(y), _p(gt), _p(res), self._stream(stream)), "admm_soc_update")
+        return res.view(batch, 2)
+
+    def _admm_soc_args(self, cones, args):
+        """The argument tuple of the admm_lin step with the four cone sizes behind mx, mu."""
+        assert len(cones) == 4
+        return args[:5] + tuple(int(v) for v in cones) + args[5:]
+
+    def _admm_soc_step(self, name, nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res,
+                       r, p, tol, max_iter, iters, max_iter_exit, stream):
+        import torch
+        if iters is None:
+            iters = torch.zeros(batch, dtype=torch.int32, device=g.device)
+        if max_iter_exit is None:
+            max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=g.device)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=g.dtype, device=g.device)
+        suf, args = self._admm_lin_args(name.endswith("shared"), nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
+                                        lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
+        self._check(getattr(self.lib, f"gbdpcg_{name}_{suf}")(*self._admm_soc_args(cones, args), self._stream(stream)), name)
+        return iters, max_iter_exit, res.view(batch, 2)
+
+    def _graph_admm_soc_step(self, name, nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                             max_iter, iters, max_iter_exit, z, w, y, gt, res):
+        suf, args = self._admm_lin_args(name.endswith("shared"), nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
+                                        lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
+        gr = ctypes.c_void_p()
+        self._check(getattr(self.lib, f"gbdpcg_graph_create_{name}_{suf}")(*self._admm_soc_args(cones, args), ctypes.byref(gr)),
+                    f"graph_create_{name}")
+        return Graph(self, gr, keep=(Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, iters, max_iter_exit, z, w, y, gt, res))
+
+    def admm_soc_step(self, nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=None,
+                      r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_admm_soc_step_*: kkt_resolve with gt in the place of g (warm start from lam), then admm_soc_update, one call.
+        Returns (iters, flags, res [batch, 2])."""
+        return self._admm_soc_step("admm_soc_step", nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z,
+                                   w, y, gt, res, r, p, tol, max_iter, iters, max_iter_exit, stream)
+
+    def graph_admm_soc_step(self, nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter,
+                            iters, max_iter_exit, z, w, y, gt, res):
+        """Capture one iteration into a hipGraph (gbdpcg_graph_create_admm_soc_step_*); the graph keeps rho's pointer."""
+        return self._graph_admm_soc_step("admm_soc_step", nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
+                                         lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
+
+    def admm_soc_step_shared(self, nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt,
+                             res=None, r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_admm_soc_step_shared_*: ONE Ginv, C, S, Pinv and E for `batch` problems; bounds, offsets, rho and the state stay per
+        problem."""
+        return self._admm_soc_step("admm_soc_step_shared", nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
+                                   lam, z, w, y, gt, res, r, p, tol, max_iter, iters, max_iter_exit, stream)
+
+    def graph_admm_soc_step_shared(self, nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                   max_iter, iters, max_iter_exit, z, w, y, gt, res):
+        """Capture the shared-matrix iteration into a hipGraph (gbdpcg_graph_create_admm_soc_step_shared_*)."""
+        return self._graph_admm_soc_step("admm_soc_step_shared", nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv,
+                                         gamma, lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
 
     # ---- the backward pass (include/gbdpcg.h): gradients of a scalar in G and C from the forward point (z, lam) and the adjoint pair
     # (az, alam), which is kkt_resolve with g := dl/dz, c := -dl/dlambda on the kept factorisation

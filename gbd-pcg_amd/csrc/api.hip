@@ -580,13 +580,16 @@ gbdpcg_status form_gamma_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint3
 
 // The box and the splitting state of gbdpcg_admm_step_*: every array has the layout of g, rho [batch], res [2 batch].
 // lin (gbdpcg_admm_lin_step_*): the bounds are on E z -- lo, hi, w, y have the layout of the rows, E is one problem's in the
-// shared form.
+// shared form.  soc (gbdpcg_admm_soc_step_*, with lin): the rows behind the first lx / lu of a block are cones of dimension qx /
+// qu, lo holds their offsets.
 template <typename T> struct AdmmOperands {
     const T *lo, *hi, *rho;
     T *w, *y, *gt, *res;
     bool lin = false;
     const T *E = nullptr;
     uint32_t mx = 0, mu = 0;
+    bool soc = false;
+    uint32_t lx = 0, qx = 0, lu = 0, qu = 0;
 };
 
 // The forward point and the outputs of gbdpcg_kkt_backward_*: z has the layout of g, lambda that of c, gG / gC those of G / C (one
@@ -718,6 +721,35 @@ gbdpcg_status admm_lin_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, 
     return GBDPCG_OK;
 }
 
+// What the rows of gbdpcg_admm_soc_* are refused for, before anything is written: what admm_lin_rows refuses, and row classes that
+// do not fit the blocks (lx > mx, lu > mu, cone rows with q = 0 or not a whole number of cones) INVALID.  Every INVALID comes
+// before UNSUPPORTED.
+template <typename T>
+gbdpcg_status admm_soc_rows(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu,
+                            uint32_t N)
+{
+    if (((uint64_t)mx + mu) * N == mu || !admm_soc_classes_ok(mx, mu, lx, qx, lu, qu)) return GBDPCG_ERR_INVALID;
+    return admm_lin_rows<T>(nx, nu, mx, mu, N);
+}
+
+// The splitting update for linear and cone rows (admm_soc.hip), one launch.  init: gbdpcg_admm_soc_init_*.
+template <typename T>
+gbdpcg_status admm_soc_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx, uint32_t qx,
+                                   uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const T *d_g, const T *d_E, const T *d_lo,
+                                   const T *d_hi, const T *d_rho, const T *d_z, T *d_w, T *d_y, T *d_gt, T *d_res, void *stream,
+                                   bool init, bool shared = false)
+{
+    if (!h || !d_g || !d_E || !d_lo || !d_hi || !d_rho || !d_w || !d_y || !d_gt || (!init && (!d_z || !d_res)) || nx == 0 ||
+        nu == 0 || N == 0 || batch == 0)
+        return GBDPCG_ERR_INVALID;
+    const gbdpcg_status st = admm_soc_rows<T>(nx, nu, mx, mu, lx, qx, lu, qu, N);
+    if (st != GBDPCG_OK) return st;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_admm_soc_update<T>(nx, nu, mx, mu, lx, qx, lu, qu, N, batch, d_g, d_E, d_lo, d_hi, d_rho, d_z, d_w, d_y, d_gt,
+                                         d_res, (hipStream_t)stream, init, shared));
+    return GBDPCG_OK;
+}
+
 // One iteration of box-constrained ADMM on a kept factorisation of G + rho I: kkt_resolve_impl with the shifted gradient a.gt in
 // the place of g (the gamma launch and the recovery launch read the same gt), then the update, which alone reads g, on the same
 // stream.  What either part would refuse for its arguments or the shape is refused here, before anything is written.
@@ -730,13 +762,17 @@ gbdpcg_status admm_step_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32
     if (!h || !d_Ginv || !d_g || !d_c || !a.lo || !a.hi || !a.rho || !d_S || !d_gamma || !d_lambda || !d_iters || !d_z || !a.w ||
         !a.y || !a.gt || !a.res || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))
         return GBDPCG_ERR_INVALID;
-    const gbdpcg_status rows = a.lin ? (a.E ? admm_lin_rows<T>(nx, nu, a.mx, a.mu, N) : GBDPCG_ERR_INVALID) : GBDPCG_OK;
+    gbdpcg_status rows = a.lin ? (a.E ? admm_lin_rows<T>(nx, nu, a.mx, a.mu, N) : GBDPCG_ERR_INVALID) : GBDPCG_OK;
+    if (a.lin && a.soc && a.E) rows = admm_soc_rows<T>(nx, nu, a.mx, a.mu, a.lx, a.qx, a.lu, a.qu, N);
     if (rows == GBDPCG_ERR_INVALID) return rows;
     if (!schur_shape_ok<T>(h->dev, nx, nu) || !mappable<T>(nx) || (shared && !fused_fits<T>(h->dev, nx, N)) || rows != GBDPCG_OK)
         return GBDPCG_ERR_UNSUPPORTED;
     const gbdpcg_status st = kkt_resolve_impl<T>(h, nx, nu, N, batch, d_Ginv, d_C, a.gt, d_c, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p,
                                                  tol, max_iter, d_iters, d_exit, d_z, stream, shared);
     if (st != GBDPCG_OK) return st;
+    if (a.soc)   // (linear and cone rows: the update of admm_soc.hip)
+        return admm_soc_update_impl<T>(h, nx, nu, a.mx, a.mu, a.lx, a.qx, a.lu, a.qu, N, batch, d_g, a.E, a.lo, a.hi, a.rho, d_z, a.w, a.y,
+                                       a.gt, a.res, stream, false, shared);
     if (a.lin)   // (with the rows and the kept matrices of G + rho E'E: the same two calls, the update of admm_lin.hip)
         return admm_lin_update_impl<T>(h, nx, nu, a.mx, a.mu, N, batch, d_g, a.E, a.lo, a.hi, a.rho, d_z, a.w, a.y, a.gt, a.res, stream,
                                        false, shared);
@@ -1620,6 +1656,70 @@ GBDPCG_ADMM_LIN(f32, float)
 GBDPCG_ADMM_LIN(f64, double)
 #undef GBDPCG_ADMM_LIN
 #undef GBDPCG_ADMM_LIN_STEP
+
+// ---- second-order cone rows next to the linear ones (admm_soc.hip): init, update, and the iteration whose solve is
+// gbdpcg_kkt_resolve_* on the matrices of G + rho E'E (formed by gbdpcg_admm_lin_form_*).  SHARED: one problem's Ginv, C, S, Pinv, E.
+#define GBDPCG_ADMM_SOC_STEP(NAME, SUF, TYPE, SHARED)                                                                               \
+    gbdpcg_status gbdpcg_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,           \
+                                        uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const TYPE *d_Ginv,       \
+                                        const TYPE *d_C, const TYPE *d_g, const TYPE *d_c, const TYPE *d_E, const TYPE *d_lo,         \
+                                        const TYPE *d_hi, const TYPE *d_rho, const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma,      \
+                                        TYPE *d_lambda, TYPE *d_r, TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters,        \
+                                        uint8_t *d_max_iter_exit, TYPE *d_z, TYPE *d_w, TYPE *d_y, TYPE *d_gt, TYPE *d_res,           \
+                                        void *stream)                                                                               \
+    {                                                                                                                               \
+        const AdmmOperands<TYPE> a{d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res, true, d_E, mx, mu, true, lx, qx, lu, qu};              \
+        return admm_step_impl<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, a, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol,    \
+                                    max_iter, d_iters, d_max_iter_exit, d_z, (hipStream_t)stream, SHARED);                          \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_graph_create_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,           \
+                                                     uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, \
+                                                     const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c,           \
+                                                     const TYPE *d_E, const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho,          \
+                                                     const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda, TYPE *d_r,   \
+                                                     TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters,                      \
+                                                     uint8_t *d_max_iter_exit, TYPE *d_z, TYPE *d_w, TYPE *d_y, TYPE *d_gt,           \
+                                                     TYPE *d_res, gbdpcg_graph_t *out)                                               \
+    {                                                                                                                               \
+        /* what the captured calls would refuse is refused before anything is reserved or captured */                                \
+        if (out) *out = nullptr;                                                                                                    \
+        if (!h || !out || !d_Ginv || !d_g || !d_c || !d_E || !d_lo || !d_hi || !d_rho || !d_S || !d_gamma || !d_lambda ||           \
+            !d_iters || !d_z || !d_w || !d_y || !d_gt || !d_res || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))           \
+            return GBDPCG_ERR_INVALID;                                                                                              \
+        const gbdpcg_status rows = admm_soc_rows<TYPE>(nx, nu, mx, mu, lx, qx, lu, qu, N);                                          \
+        if (rows == GBDPCG_ERR_INVALID) return rows;                                                                                \
+        if (!schur_shape_ok<TYPE>(h->dev, nx, nu) || rows != GBDPCG_OK) return GBDPCG_ERR_UNSUPPORTED;                              \
+        const AdmmOperands<TYPE> a{d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res, true, d_E, mx, mu, true, lx, qx, lu, qu};              \
+        KktOperands<TYPE> k{nu, nullptr, d_C, d_g, d_c, const_cast<TYPE *>(d_Ginv), d_z};                                           \
+        k.resolve = true;                                                                                                           \
+        k.shared = SHARED;                                                                                                          \
+        k.admm = &a;                                                                                                                \
+        return graph_create_impl<TYPE>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters,            \
+                                       d_max_iter_exit, out, -1, &k);                                                               \
+    }
+#define GBDPCG_ADMM_SOC(SUF, TYPE)                                                                                                  \
+    gbdpcg_status gbdpcg_admm_soc_init_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,      \
+                                             uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const TYPE *d_g,     \
+                                             const TYPE *d_E, const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho, TYPE *d_w,      \
+                                             TYPE *d_y, TYPE *d_gt, void *stream)                                                    \
+    {                                                                                                                               \
+        return admm_soc_update_impl<TYPE>(h, nx, nu, mx, mu, lx, qx, lu, qu, N, batch, d_g, d_E, d_lo, d_hi, d_rho, nullptr, d_w,   \
+                                          d_y, d_gt, nullptr, stream, true);                                                        \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_soc_update_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,    \
+                                               uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const TYPE *d_g,   \
+                                               const TYPE *d_E, const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho,               \
+                                               const TYPE *d_z, TYPE *d_w, TYPE *d_y, TYPE *d_gt, TYPE *d_res, void *stream)          \
+    {                                                                                                                               \
+        return admm_soc_update_impl<TYPE>(h, nx, nu, mx, mu, lx, qx, lu, qu, N, batch, d_g, d_E, d_lo, d_hi, d_rho, d_z, d_w, d_y,  \
+                                          d_gt, d_res, stream, false);                                                              \
+    }                                                                                                                               \
+    GBDPCG_ADMM_SOC_STEP(admm_soc_step, SUF, TYPE, false)                                                                           \
+    GBDPCG_ADMM_SOC_STEP(admm_soc_step_shared, SUF, TYPE, true)
+GBDPCG_ADMM_SOC(f32, float)
+GBDPCG_ADMM_SOC(f64, double)
+#undef GBDPCG_ADMM_SOC
+#undef GBDPCG_ADMM_SOC_STEP
 
 // ---- the KKT backward pass: the gradients of a scalar in G and C from (z, lambda) and the adjoint pair, and the adjoint solve +
 // gradient launch as one call / one graph.  SHARED: one problem's Ginv, C, S, Pinv, and gG, gC summed over the batch.

@@ -274,6 +274,17 @@ hipError_t launch_admm_lin_update(uint32_t nx, uint32_t nu, uint32_t mx, uint32_
 template <typename T> bool admm_lin_shape_ok(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu);
 uint32_t admm_lin_knot_chunk(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu);
 
+// ---- admm_soc.hip : the update of admm_lin.hip with second-order cone rows (layouts and lines in include/gbdpcg.h), one kernel.
+// In every x block the first lx rows are linear, the other mx - lx are consecutive cones of dimension qx, head row first (lu, qu:
+// the u blocks); on a cone row lo holds the offset f and hi is not read.  Same chunks, same LDS budget, same refusals as
+// launch_admm_lin_update, and the row classes must pass admm_soc_classes_ok.  The formation is launch_admm_lin_form.
+template <typename T>
+hipError_t launch_admm_soc_update(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu,
+                                  uint32_t N, uint32_t batch, const T *g, const T *E, const T *lo, const T *hi, const T *rho, const T *z,
+                                  T *w, T *y, T *gt, T *res, hipStream_t s, bool init, bool shared = false);
+// (lx <= mx, lu <= mu; where a block has cone rows its q is not 0 and divides their number; q is ignored where it has none)
+bool admm_soc_classes_ok(uint32_t mx, uint32_t mu, uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu);
+
 // ---- kkt_grad.hip : the gradients of a scalar in the packed KKT blocks from the forward pair (z, lambda) and the adjoint pair
 // (az, alam), one launch.  gG has the layout of G, gC that of C; either may be null (not written):
 //     gQ_k = 1/2 (ax_k x_k' + x_k ax_k'), gR_k likewise with u;  [gA_k | gB_k] = -(alam_{k+1} z_k' + lam_{k+1} az_k')

@@ -797,6 +797,126 @@ gbdpcg_status gbdpcg_graph_create_admm_lin_step_shared_f64(gbdpcg_handle_t h, ui
                                                            double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res,
                                                            gbdpcg_graph_t *out);
 
+/* Second-order cone rows next to the linear ones: norm bounds ||u_k||_2 <= r, friction cones ||(f_x, f_y)||_2 <= mu f_z, speed
+ * limits.  Problem b is
+ *     minimise 1/2 z'Gz + g'z   subject to   Cz = c,   lo <= (E z)_r <= hi on linear rows,   (E z + f)_cone in K_q on cone rows
+ * with K_q = {(s_0, s_1 .. s_{q-1}) : ||(s_1 .. s_{q-1})||_2 <= s_0}.  d_E, its layout, the row packing [mx | mu | mx | ... | mx],
+ * d_w, d_y, d_gt, d_rho and d_res are exactly those of gbdpcg_admm_lin_*, and Gt = G + rho E'E is formed by gbdpcg_admm_lin_form_*,
+ * which does not depend on the set the rows are projected on.
+ * ROW CLASSES, the four sizes directly behind mx, mu: in every x block the first lx rows are linear, the remaining mx - lx rows are
+ * consecutive cones of dimension qx, head row (s_0) first; lu, qu do the same for the u blocks.  The split is the same for every
+ * knot and every problem.  ON A CONE ROW d_lo[r] HOLDS THE OFFSET f_r AND d_hi[r] IS NOT READ (no further array, and less traffic
+ * on a cone row than on a linear one).  A constant bound ||u||_2 <= r is a head row with a zero row of E and f = r.
+ * Every line is one IEEE operation or a comparison, chains run in ascending index order, sqrt and / are correctly rounded:
+ *  - gbdpcg_admm_soc_update_*: linear rows take the lines of gbdpcg_admm_lin_update_* unchanged.  Cone rows:
+ *        v_r  = chain over columns j of E(r,j) z_j, SEEDED with f_r instead of +0    (acc = f_r; acc = fma(E(r,j), z_j, acc))
+ *        s_r  = fl(v_r + y_r)
+ *        per cone (its rows 0 .. q-1):
+ *          n2 = chain over i = 1 .. q-1 of s_i s_i                                   (acc = +0; acc = fma(s_i, s_i, acc))
+ *          a  = sqrt(n2)
+ *          if      a <=  s_0 : w+ = s                                                (all rows of the cone)
+ *          else if a <= -s_0 : w+ = +0                                               (all rows)
+ *          else    h = fl(0.5 fl(s_0 + a));  c = fl(h / a);  w+_0 = h;  w+_i = fl(c s_i)
+ *        y+_r = fl(s_r - w+_r)
+ *        t_r  = fl(fl(w+_r - y+_r) - f_r);   d_r = fl(w+_r - w_r)
+ *    then, as for the linear rows, u_j and e_j are the column chains of t and d, gt_j = fma(-rho_b, u_j, g_j),
+ *    d_res[2b] = max_r |fl(v_r - w+_r)| and d_res[2b+1] = max_j |fl(rho_b e_j)|, the maxima over bit patterns with a NaN on top.
+ *    A NaN fails both comparisons, takes the third branch and stays NaN.  q = 1 is the half-line s_0 >= 0: an empty chain, a = +0.
+ *    The multiplier of a cone, mu = rho y, lies in -K (minus the cone), and G z + g + C' lambda + rho E'y -> 0.  Unlike the clip,
+ *    d_w satisfies ||w_{1..}||_2 <= w_0 only to a few ulp: c s_i is rounded.  E z + f agrees with w to d_res[2b].
+ *  - gbdpcg_admm_soc_init_*: before the first iteration.  w <- the projection of w by the same lines with s := w; y is not written,
+ *    t = fl(fl(w_r - y_r) - f_r) on cone rows and fl(w_r - y_r) on linear ones, gt_j = fma(-rho_b, u_j, g_j); z and res are not
+ *    touched.
+ *  - gbdpcg_admm_soc_step_*: gbdpcg_kkt_resolve_* with d_gt for d_g, then the update on the same stream, the same bits as the two
+ *    calls; gbdpcg_graph_create_admm_soc_step_* is its graph form (it keeps the POINTER d_rho).  The _shared twins of step and graph
+ *    take ONE problem's d_Ginv, d_C, d_S, d_Pinv AND d_E; everything else stays per problem.
+ *  - with lx = mx and lu = mu (no cone row) every output has the bits of the gbdpcg_admm_lin_* call, and qx, qu are ignored.
+ * Refused before anything is written: everything gbdpcg_admm_lin_* refuses (d_hi is required even where no row reads it), and with
+ * GBDPCG_ERR_INVALID lx > mx, lu > mu, qx == 0 with mx > lx or qu == 0 with mu > lu, (mx - lx) % qx != 0, (mu - lu) % qu != 0.
+ * Every INVALID is reported before any UNSUPPORTED.  Rows that mix x_k and u_k, cones of differing dimension inside one block,
+ * rotated cones and a backward pass through the cone rows are out of scope. */
+gbdpcg_status gbdpcg_admm_soc_init_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,
+                                       uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const float *d_g,
+                                       const float *d_E, const float *d_lo, const float *d_hi, const float *d_rho, float *d_w,
+                                       float *d_y, float *d_gt, void *stream);
+gbdpcg_status gbdpcg_admm_soc_init_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,
+                                       uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const double *d_g,
+                                       const double *d_E, const double *d_lo, const double *d_hi, const double *d_rho, double *d_w,
+                                       double *d_y, double *d_gt, void *stream);
+gbdpcg_status gbdpcg_admm_soc_update_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,
+                                         uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const float *d_g,
+                                         const float *d_E, const float *d_lo, const float *d_hi, const float *d_rho,
+                                         const float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_soc_update_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,
+                                         uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const double *d_g,
+                                         const double *d_E, const double *d_lo, const double *d_hi, const double *d_rho,
+                                         const double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_soc_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,
+                                       uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const float *d_Ginv,
+                                       const float *d_C, const float *d_g, const float *d_c, const float *d_E, const float *d_lo,
+                                       const float *d_hi, const float *d_rho, const float *d_S, const float *d_Pinv, float *d_gamma,
+                                       float *d_lambda, float *d_r, float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                       uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res,
+                                       void *stream);
+gbdpcg_status gbdpcg_admm_soc_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,
+                                       uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const double *d_Ginv,
+                                       const double *d_C, const double *d_g, const double *d_c, const double *d_E,
+                                       const double *d_lo, const double *d_hi, const double *d_rho, const double *d_S,
+                                       const double *d_Pinv, double *d_gamma, double *d_lambda, double *d_r, double *d_p, double tol,
+                                       uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z, double *d_w,
+                                       double *d_y, double *d_gt, double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_soc_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                    uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch,
+                                                    const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                                    const float *d_E, const float *d_lo, const float *d_hi, const float *d_rho,
+                                                    const float *d_S, const float *d_Pinv, float *d_gamma, float *d_lambda,
+                                                    float *d_r, float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                                    uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y, float *d_gt,
+                                                    float *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_soc_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                    uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch,
+                                                    const double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                                    const double *d_E, const double *d_lo, const double *d_hi, const double *d_rho,
+                                                    const double *d_S, const double *d_Pinv, double *d_gamma, double *d_lambda,
+                                                    double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                    uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y, double *d_gt,
+                                                    double *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_admm_soc_step_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,
+                                              uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch,
+                                              const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                              const float *d_E, const float *d_lo, const float *d_hi, const float *d_rho,
+                                              const float *d_S, const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r,
+                                              float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                              uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y, float *d_gt,
+                                              float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_soc_step_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,
+                                              uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch,
+                                              const double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                              const double *d_E, const double *d_lo, const double *d_hi, const double *d_rho,
+                                              const double *d_S, const double *d_Pinv, double *d_gamma, double *d_lambda,
+                                              double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                              uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y, double *d_gt,
+                                              double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_soc_step_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                           uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N,
+                                                           uint32_t batch, const float *d_Ginv, const float *d_C, const float *d_g,
+                                                           const float *d_c, const float *d_E, const float *d_lo,
+                                                           const float *d_hi, const float *d_rho, const float *d_S,
+                                                           const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r,
+                                                           float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                                           uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y,
+                                                           float *d_gt, float *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_soc_step_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                           uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N,
+                                                           uint32_t batch, const double *d_Ginv, const double *d_C,
+                                                           const double *d_g, const double *d_c, const double *d_E,
+                                                           const double *d_lo, const double *d_hi, const double *d_rho,
+                                                           const double *d_S, const double *d_Pinv, double *d_gamma,
+                                                           double *d_lambda, double *d_r, double *d_p, double tol,
+                                                           uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                                           double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res,
+                                                           gbdpcg_graph_t *out);
+
 /* The backward pass: gradients of a scalar through (G, C, g, c) -> (z, lambda), on the device.  Forward convention as above:
  * G z + g + C' lambda = 0, C z = c.  For a scalar l with upstream gradients gz = dl/dz (layout of d_g) and glam = dl/dlambda (layout
  * of d_c) let (a_z, a_lambda) solve the SAME KKT matrix with the right-hand side (-gz, -glam).  The matrix is symmetric, so this
