@@ -91,31 +91,22 @@ def _resolve_argtypes(lib):
         getattr(lib, f"gbdpcg_kkt_step_reg_{suf}").argtypes = head + [vp] + step + [vp]
         getattr(lib, f"gbdpcg_graph_create_kkt_step_reg_{suf}").argtypes = head + [vp] + step + [ctypes.POINTER(vp)]
         getattr(lib, f"gbdpcg_kkt_residual_reg_{suf}").argtypes = head + [vp] + [vp, vp, vp, vp]   # rho | z, lambda, res, stream
-        # box-constrained ADMM on a kept factorisation: h, nx, nu, N, batch | g, lo, hi, rho | ...
+        # ADMM on a kept factorisation, three families: box (lo <= z <= hi), stage-wise linear rows (lo <= E z <= hi), second-order
+        # cone rows next to them.  A family is the sizes it puts between nu and N and whether E stands in front of lo, hi:
+        #   init    h, nx, nu, [sizes], N, batch | g | [E], lo, hi, rho | w, y, gt | stream
+        #   update  ...                          | g | [E], lo, hi, rho | z, w, y, gt, res | stream
+        #   step    ...             | Ginv, C, g, c | [E], lo, hi, rho | the solve's arguments | w, y, gt, res | stream / graph out
         sizes = [vp, u32, u32, u32, u32]
-        getattr(lib, f"gbdpcg_admm_init_{suf}").argtypes = sizes + [vp, vp, vp, vp] + [vp, vp, vp, vp]           # w, y, gt, stream
-        getattr(lib, f"gbdpcg_admm_update_{suf}").argtypes = sizes + [vp, vp, vp, vp] + [vp, vp, vp, vp, vp, vp]   # z, w, y, gt, res, stream
-        # Ginv, C, g, c | lo, hi, rho | the solve's arguments | w, y, gt, res | stream / graph out
-        for name in ("admm_step", "admm_step_shared"):
-            getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = head + [vp, vp, vp] + solve + [vp, vp, vp, vp] + [vp]
-            getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = head + [vp, vp, vp] + solve + [vp, vp, vp, vp] + [ctypes.POINTER(vp)]
-        # stage-wise linear rows: h, nx, nu, mx, mu, N, batch | ... with E in front of lo
-        lsizes = [vp, u32, u32, u32, u32, u32, u32]
-        getattr(lib, f"gbdpcg_admm_lin_form_{suf}").argtypes = lsizes + [vp, vp, vp, vp, vp]                          # G, E, rho, Gt, stream
-        getattr(lib, f"gbdpcg_admm_lin_init_{suf}").argtypes = lsizes + [vp, vp, vp, vp, vp] + [vp, vp, vp, vp]       # g, E, lo, hi, rho | w, y, gt, stream
-        getattr(lib, f"gbdpcg_admm_lin_update_{suf}").argtypes = lsizes + [vp, vp, vp, vp, vp] + [vp, vp, vp, vp, vp, vp]
-        for name in ("admm_lin_step", "admm_lin_step_shared"):   # Ginv, C, g, c | E, lo, hi, rho | the solve | w, y, gt, res | last
-            getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = lsizes + [vp, vp, vp, vp] + [vp, vp, vp, vp] + solve + [vp, vp, vp, vp] + [vp]
-            getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = (lsizes + [vp, vp, vp, vp] + [vp, vp, vp, vp] + solve +
-                                                                          [vp, vp, vp, vp] + [ctypes.POINTER(vp)])
-        # second-order cone rows: h, nx, nu, mx, mu, lx, qx, lu, qu, N, batch | the lists of admm_lin
-        csizes = [vp] + [u32] * 10
-        getattr(lib, f"gbdpcg_admm_soc_init_{suf}").argtypes = csizes + [vp, vp, vp, vp, vp] + [vp, vp, vp, vp]
-        getattr(lib, f"gbdpcg_admm_soc_update_{suf}").argtypes = csizes + [vp, vp, vp, vp, vp] + [vp, vp, vp, vp, vp, vp]
-        for name in ("admm_soc_step", "admm_soc_step_shared"):
-            getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = csizes + [vp, vp, vp, vp] + [vp, vp, vp, vp] + solve + [vp, vp, vp, vp] + [vp]
-            getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = (csizes + [vp, vp, vp, vp] + [vp, vp, vp, vp] + solve +
-                                                                          [vp, vp, vp, vp] + [ctypes.POINTER(vp)])
+        for fam, extra in (("admm", []), ("admm_lin", [u32, u32]), ("admm_soc", [u32] * 6)):   # mx, mu | lx, qx, lu, qu
+            fsizes = [vp, u32, u32] + extra + [u32, u32]
+            fset = ([vp] if extra else []) + [vp, vp, vp]
+            getattr(lib, f"gbdpcg_{fam}_init_{suf}").argtypes = fsizes + [vp] + fset + [vp, vp, vp] + [vp]
+            getattr(lib, f"gbdpcg_{fam}_update_{suf}").argtypes = fsizes + [vp] + fset + [vp, vp, vp, vp, vp] + [vp]
+            for name in (f"{fam}_step", f"{fam}_step_shared"):
+                step_args = fsizes + [vp, vp, vp, vp] + fset + solve + [vp, vp, vp, vp]
+                getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = step_args + [vp]
+                getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = step_args + [ctypes.POINTER(vp)]
+        getattr(lib, f"gbdpcg_admm_lin_form_{suf}").argtypes = sizes + [u32, u32] + [vp, vp, vp, vp, vp]   # (mx, mu) G, E, rho, Gt, stream
         # the backward pass: z, lambda, az, alambda | gG, gC, stream
         for name in ("kkt_grad", "kkt_grad_shared"):
             getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = sizes + [vp, vp, vp, vp] + [vp, vp, vp]
@@ -623,16 +614,31 @@ class Solver:
                        _p(res), self._stream(stream)), "admm_update")
         return res.view(batch, 2)
 
-    def _admm_args(self, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters, mie, z, w, y,
-                   gt, res):
+    # One set of helpers for the three families.  rows = (mx, mu, E) for the calls with stage-wise rows (lo, hi, w, y then have the
+    # layout of the rows), cones = (lx, qx, lu, qu) next to rows for the calls with cone rows; `name` ends in "shared" for the twins.
+    def _admm_step_args(self, name, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters, mie,
+                        z, w, y, gt, res, rows=None, cones=None):
+        """(suffix, the argument tuple up to d_res, the tensors a graph has to keep alive)."""
         suf, _ = _suffix(g)
         assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == g.dtype
-        self._box(g, batch, lo, hi, z, w, y, gt)
-        return suf, (self.h, nx, nu, N, batch, _p(Ginv), _p(C), _p(g), _p(c), _p(lo), _p(hi), _p(self._rho(rho, batch, g)), _p(S),
-                     _p(Pinv), _p(gamma), _p(lam), _p(r), _p(p), tol, max_iter, _p(iters), _p(mie), _p(z), _p(w), _p(y), _p(gt), _p(res))
+        sizes, E = (), ()
+        if rows is None:
+            assert cones is None
+            self._box(g, batch, lo, hi, z, w, y, gt)
+        else:
+            mx, mu, E = rows
+            self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y), (g, z, gt), mats=1 if name.endswith("shared") else None)
+            sizes, E = (mx, mu), (E,)
+            if cones is not None:
+                assert len(cones) == 4
+                sizes += tuple(int(v) for v in cones)
+        args = ((self.h, nx, nu) + sizes + (N, batch, _p(Ginv), _p(C), _p(g), _p(c)) + tuple(_p(t) for t in E) +
+                (_p(lo), _p(hi), _p(self._rho(rho, batch, g)), _p(S), _p(Pinv), _p(gamma), _p(lam), _p(r), _p(p), tol, max_iter,
+                 _p(iters), _p(mie), _p(z), _p(w), _p(y), _p(gt), _p(res)))
+        return suf, args, (Ginv, C, g, c) + E + (lo, hi, rho, S, Pinv, gamma, lam, r, p, iters, mie, z, w, y, gt, res)
 
     def _admm_step(self, name, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, r, p, tol,
-                   max_iter, iters, max_iter_exit, stream):
+                   max_iter, iters, max_iter_exit, stream, rows=None, cones=None):
         import torch
         if iters is None:
             iters = torch.zeros(batch, dtype=torch.int32, device=g.device)
@@ -640,18 +646,18 @@ class Solver:
             max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=g.device)
         if res is None:
             res = torch.empty(batch, 2, dtype=g.dtype, device=g.device)
-        suf, args = self._admm_args(nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
-                                    max_iter_exit, z, w, y, gt, res)
+        suf, args, _ = self._admm_step_args(name, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter,
+                                            iters, max_iter_exit, z, w, y, gt, res, rows, cones)
         self._check(getattr(self.lib, f"gbdpcg_{name}_{suf}")(*args, self._stream(stream)), name)
         return iters, max_iter_exit, res.view(batch, 2)
 
     def _graph_admm_step(self, name, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
-                         max_iter_exit, z, w, y, gt, res):
-        suf, args = self._admm_args(nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
-                                    max_iter_exit, z, w, y, gt, res)
+                         max_iter_exit, z, w, y, gt, res, rows=None, cones=None):
+        suf, args, keep = self._admm_step_args(name, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                               max_iter, iters, max_iter_exit, z, w, y, gt, res, rows, cones)
         gr = ctypes.c_void_p()
         self._check(getattr(self.lib, f"gbdpcg_graph_create_{name}_{suf}")(*args, ctypes.byref(gr)), f"graph_create_{name}")
-        return Graph(self, gr, keep=(Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, iters, max_iter_exit, z, w, y, gt, res))
+        return Graph(self, gr, keep=keep)
 
     def admm_step(self, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=None, r=None, p=None,
                   tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
@@ -732,63 +738,32 @@ class Solver:
                        _p(y), _p(gt), _p(res), self._stream(stream)), "admm_lin_update")
         return res.view(batch, 2)
 
-    def _admm_lin_args(self, shared, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter,
-                       iters, mie, z, w, y, gt, res):
-        suf, _ = _suffix(g)
-        assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == g.dtype
-        self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y), (g, z, gt), mats=1 if shared else None)
-        return suf, (self.h, nx, nu, mx, mu, N, batch, _p(Ginv), _p(C), _p(g), _p(c), _p(E), _p(lo), _p(hi),
-                     _p(self._rho(rho, batch, g)), _p(S), _p(Pinv), _p(gamma), _p(lam), _p(r), _p(p), tol, max_iter, _p(iters), _p(mie),
-                     _p(z), _p(w), _p(y), _p(gt), _p(res))
-
-    def _admm_lin_step(self, name, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, r, p,
-                       tol, max_iter, iters, max_iter_exit, stream):
-        import torch
-        if iters is None:
-            iters = torch.zeros(batch, dtype=torch.int32, device=g.device)
-        if max_iter_exit is None:
-            max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=g.device)
-        if res is None:
-            res = torch.empty(batch, 2, dtype=g.dtype, device=g.device)
-        suf, args = self._admm_lin_args(name.endswith("shared"), nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
-                                        lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
-        self._check(getattr(self.lib, f"gbdpcg_{name}_{suf}")(*args, self._stream(stream)), name)
-        return iters, max_iter_exit, res.view(batch, 2)
-
-    def _graph_admm_lin_step(self, name, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter,
-                             iters, max_iter_exit, z, w, y, gt, res):
-        suf, args = self._admm_lin_args(name.endswith("shared"), nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
-                                        lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
-        gr = ctypes.c_void_p()
-        self._check(getattr(self.lib, f"gbdpcg_graph_create_{name}_{suf}")(*args, ctypes.byref(gr)), f"graph_create_{name}")
-        return Graph(self, gr, keep=(Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, iters, max_iter_exit, z, w, y, gt, res))
-
     def admm_lin_step(self, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=None, r=None,
                       p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
         """gbdpcg_admm_lin_step_*: kkt_resolve with gt in the place of g (warm start from lam), then admm_lin_update, one call.
         Returns (iters, flags, res [batch, 2])."""
-        return self._admm_lin_step("admm_lin_step", nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y,
-                                   gt, res, r, p, tol, max_iter, iters, max_iter_exit, stream)
+        return self._admm_step("admm_lin_step", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, r, p,
+                               tol, max_iter, iters, max_iter_exit, stream, rows=(mx, mu, E))
 
     def graph_admm_lin_step(self, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
                             max_iter_exit, z, w, y, gt, res):
         """Capture one iteration into a hipGraph (gbdpcg_graph_create_admm_lin_step_*): replay it once per iteration; the graph
         keeps rho's pointer."""
-        return self._graph_admm_lin_step("admm_lin_step", nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r,
-                                         p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
+        return self._graph_admm_step("admm_lin_step", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                     max_iter, iters, max_iter_exit, z, w, y, gt, res, rows=(mx, mu, E))
 
     def admm_lin_step_shared(self, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=None,
                              r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
         """gbdpcg_admm_lin_step_shared_*: ONE Ginv, C, S, Pinv and E for `batch` problems; bounds, rho and the state stay per
         problem."""
-        return self._admm_lin_step("admm_lin_step_shared", nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z,
-                                   w, y, gt, res, r, p, tol, max_iter, iters, max_iter_exit, stream)
+        return self._admm_step("admm_lin_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res,
+                               r, p, tol, max_iter, iters, max_iter_exit, stream, rows=(mx, mu, E))
 
     def graph_admm_lin_step_shared(self, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
                                    max_iter, iters, max_iter_exit, z, w, y, gt, res):
         """Capture the shared-matrix iteration into a hipGraph (gbdpcg_graph_create_admm_lin_step_shared_*)."""
-        return self._graph_admm_lin_step("admm_lin_step_shared", nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
-                                         lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
+        return self._graph_admm_step("admm_lin_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                     max_iter, iters, max_iter_exit, z, w, y, gt, res, rows=(mx, mu, E))
 
     # ---- second-order cone rows next to the linear ones (include/gbdpcg.h): cones = (lx, qx, lu, qu) -- the first lx rows of an x
     # block are linear, the rest cones of dimension qx, head row first; on a cone row lo holds the offset f and hi is not read.  The
@@ -819,59 +794,31 @@ class Solver:
                        _p(y), _p(gt), _p(res), self._stream(stream)), "admm_soc_update")
         return res.view(batch, 2)
 
-    def _admm_soc_args(self, cones, args):
-        """The argument tuple of the admm_lin step with the four cone sizes behind mx, mu."""
-        assert len(cones) == 4
-        return args[:5] + tuple(int(v) for v in cones) + args[5:]
-
-    def _admm_soc_step(self, name, nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res,
-                       r, p, tol, max_iter, iters, max_iter_exit, stream):
-        import torch
-        if iters is None:
-            iters = torch.zeros(batch, dtype=torch.int32, device=g.device)
-        if max_iter_exit is None:
-            max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=g.device)
-        if res is None:
-            res = torch.empty(batch, 2, dtype=g.dtype, device=g.device)
-        suf, args = self._admm_lin_args(name.endswith("shared"), nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
-                                        lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
-        self._check(getattr(self.lib, f"gbdpcg_{name}_{suf}")(*self._admm_soc_args(cones, args), self._stream(stream)), name)
-        return iters, max_iter_exit, res.view(batch, 2)
-
-    def _graph_admm_soc_step(self, name, nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
-                             max_iter, iters, max_iter_exit, z, w, y, gt, res):
-        suf, args = self._admm_lin_args(name.endswith("shared"), nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
-                                        lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
-        gr = ctypes.c_void_p()
-        self._check(getattr(self.lib, f"gbdpcg_graph_create_{name}_{suf}")(*self._admm_soc_args(cones, args), ctypes.byref(gr)),
-                    f"graph_create_{name}")
-        return Graph(self, gr, keep=(Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, iters, max_iter_exit, z, w, y, gt, res))
-
     def admm_soc_step(self, nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=None,
                       r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
         """gbdpcg_admm_soc_step_*: kkt_resolve with gt in the place of g (warm start from lam), then admm_soc_update, one call.
         Returns (iters, flags, res [batch, 2])."""
-        return self._admm_soc_step("admm_soc_step", nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z,
-                                   w, y, gt, res, r, p, tol, max_iter, iters, max_iter_exit, stream)
+        return self._admm_step("admm_soc_step", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, r, p,
+                               tol, max_iter, iters, max_iter_exit, stream, rows=(mx, mu, E), cones=cones)
 
     def graph_admm_soc_step(self, nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter,
                             iters, max_iter_exit, z, w, y, gt, res):
         """Capture one iteration into a hipGraph (gbdpcg_graph_create_admm_soc_step_*); the graph keeps rho's pointer."""
-        return self._graph_admm_soc_step("admm_soc_step", nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
-                                         lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
+        return self._graph_admm_step("admm_soc_step", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                     max_iter, iters, max_iter_exit, z, w, y, gt, res, rows=(mx, mu, E), cones=cones)
 
     def admm_soc_step_shared(self, nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt,
                              res=None, r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
         """gbdpcg_admm_soc_step_shared_*: ONE Ginv, C, S, Pinv and E for `batch` problems; bounds, offsets, rho and the state stay per
         problem."""
-        return self._admm_soc_step("admm_soc_step_shared", nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma,
-                                   lam, z, w, y, gt, res, r, p, tol, max_iter, iters, max_iter_exit, stream)
+        return self._admm_step("admm_soc_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res,
+                               r, p, tol, max_iter, iters, max_iter_exit, stream, rows=(mx, mu, E), cones=cones)
 
     def graph_admm_soc_step_shared(self, nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
                                    max_iter, iters, max_iter_exit, z, w, y, gt, res):
         """Capture the shared-matrix iteration into a hipGraph (gbdpcg_graph_create_admm_soc_step_shared_*)."""
-        return self._graph_admm_soc_step("admm_soc_step_shared", nx, nu, mx, mu, cones, N, batch, Ginv, C, g, c, E, lo, hi, rho, S, Pinv,
-                                         gamma, lam, r, p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res)
+        return self._graph_admm_step("admm_soc_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                     max_iter, iters, max_iter_exit, z, w, y, gt, res, rows=(mx, mu, E), cones=cones)
 
     # ---- the backward pass (include/gbdpcg.h): gradients of a scalar in G and C from the forward point (z, lam) and the adjoint pair
     # (az, alam), which is kkt_resolve with g := dl/dz, c := -dl/dlambda on the kept factorisation

@@ -20,6 +20,7 @@
 // workgroup peels a scalar head of (-b nz) mod (16 / sizeof T) elements, runs the body with 16-byte loads and stores and finishes
 // with a scalar tail; otherwise every element goes through the scalar form.  Same operations per element either way: same bits.
 // Default cache policy throughout: z was written by the recovery kernel just before, gt is read by the gamma kernel next.
+#include "ieee_once.hpp"
 #include "internal.hpp"
 #include "norm_fold.hpp"
 
@@ -36,11 +37,6 @@ template <> struct AdmmVec<double> {
     static constexpr uint32_t N = 2;
     typedef double type __attribute__((ext_vector_type(2)));
 };
-
-__device__ __forceinline__ float fma_once(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double fma_once(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
-template <typename T> __device__ __forceinline__ T clip(T v, T lo, T hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One element.  w, y: in / out (INIT leaves y alone); mp, md: the running maxima of the two norms (not INIT).
 template <typename T, bool INIT, typename U>

@@ -578,18 +578,17 @@ gbdpcg_status form_gamma_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint3
                               const T *d_g, const T *d_c, T *d_gamma, void *stream, bool shared = false);
 // (shared: d_Ginv and d_C are one problem's blocks, used by every problem of the batch)
 
-// The box and the splitting state of gbdpcg_admm_step_*: every array has the layout of g, rho [batch], res [2 batch].
-// lin (gbdpcg_admm_lin_step_*): the bounds are on E z -- lo, hi, w, y have the layout of the rows, E is one problem's in the
-// shared form.  soc (gbdpcg_admm_soc_step_*, with lin): the rows behind the first lx / lu of a block are cones of dimension qx /
-// qu, lo holds their offsets.
+// The set and the splitting state of the gbdpcg_admm*_step_* calls: rho [batch], res [2 batch].  Box (gbdpcg_admm_step_*): mx = mu = 0
+// and no E, every array has the layout of g.  rows (gbdpcg_admm_lin_step_*): the bounds are on E z -- lo, hi, w, y have the layout
+// of the rows, E is one problem's in the shared form.  cones (gbdpcg_admm_soc_step_*, with rows): the rows behind the first lx / lu
+// of a block are cones of dimension qx / qu, lo holds their offsets.
 template <typename T> struct AdmmOperands {
     const T *lo, *hi, *rho;
     T *w, *y, *gt, *res;
-    bool lin = false;
+    bool rows = false;
     const T *E = nullptr;
     uint32_t mx = 0, mu = 0;
-    bool soc = false;
-    uint32_t lx = 0, qx = 0, lu = 0, qu = 0;
+    const RowClasses *cones = nullptr;
 };
 
 // The forward point and the outputs of gbdpcg_kkt_backward_*: z has the layout of g, lambda that of c, gG / gC those of G / C (one
@@ -683,99 +682,82 @@ gbdpcg_status admm_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint
     return GBDPCG_OK;
 }
 
-// What the stage-wise rows of gbdpcg_admm_lin_* are refused for, before anything is written: no rows at all (mx = mu = 0, or
-// mx = 0 with N = 1) is INVALID, more than 64 rows per block or a knot that does not fit the update kernel's LDS UNSUPPORTED.
-template <typename T> gbdpcg_status admm_lin_rows(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N)
+// What the stage-wise rows of gbdpcg_admm_lin_* and gbdpcg_admm_soc_* are refused for, before anything is written.  INVALID: no
+// rows at all (mx = mu = 0, or mx = 0 with N = 1), row classes that do not fit the blocks (lx > mx, lu > mu, cone rows with q = 0
+// or not a whole number of cones).  UNSUPPORTED, behind every INVALID: more than 64 rows per block, a knot that does not fit the
+// update kernel's LDS.
+template <typename T> gbdpcg_status admm_rows_status(uint32_t nx, uint32_t nu, const AdmmOperands<T> &a, uint32_t N)
 {
-    if (((uint64_t)mx + mu) * N == mu) return GBDPCG_ERR_INVALID;
-    return admm_lin_shape_ok<T>(nx, nu, mx, mu) ? GBDPCG_OK : GBDPCG_ERR_UNSUPPORTED;
+    if (((uint64_t)a.mx + a.mu) * N == a.mu || (a.cones && !admm_rows_classes_ok(a.mx, a.mu, *a.cones))) return GBDPCG_ERR_INVALID;
+    return admm_rows_shape_ok<T>(nx, nu, a.mx, a.mu) ? GBDPCG_OK : GBDPCG_ERR_UNSUPPORTED;
 }
 
-// Gt = G + rho E'E (admm_lin.hip), one launch; d_Gt may be d_G.
+// Gt = G + rho E'E (admm_rows.hip), one launch; d_Gt may be d_G.
 template <typename T>
 gbdpcg_status admm_lin_form_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch,
                                  const T *d_G, const T *d_E, const T *d_rho, T *d_Gt, void *stream)
 {
     if (!h || !d_G || !d_E || !d_rho || !d_Gt || nx == 0 || nu == 0 || N == 0 || batch == 0) return GBDPCG_ERR_INVALID;
-    const gbdpcg_status st = admm_lin_rows<T>(nx, nu, mx, mu, N);
+    AdmmOperands<T> a{};
+    a.mx = mx, a.mu = mu;
+    const gbdpcg_status st = admm_rows_status<T>(nx, nu, a, N);
     if (st != GBDPCG_OK) return st;
     DEVICE_SCOPE(h);
     HIP_TRY(h, launch_admm_lin_form<T>(nx, nu, mx, mu, N, batch, d_G, d_E, d_rho, d_Gt, (hipStream_t)stream));
     return GBDPCG_OK;
 }
 
-// The splitting update for the rows (admm_lin.hip), one launch.  init: gbdpcg_admm_lin_init_* -- d_z and d_res are not arguments.
+// The splitting update for the rows of a (admm_rows.hip; with a.cones its CONES kernel), one launch.  init: gbdpcg_admm_lin_init_*,
+// gbdpcg_admm_soc_init_* -- d_z and a.res are not arguments.
 template <typename T>
-gbdpcg_status admm_lin_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch,
-                                   const T *d_g, const T *d_E, const T *d_lo, const T *d_hi, const T *d_rho, const T *d_z, T *d_w,
-                                   T *d_y, T *d_gt, T *d_res, void *stream, bool init, bool shared = false)
+gbdpcg_status admm_rows_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_g,
+                                    const AdmmOperands<T> &a, const T *d_z, void *stream, bool init, bool shared = false)
 {
-    if (!h || !d_g || !d_E || !d_lo || !d_hi || !d_rho || !d_w || !d_y || !d_gt || (!init && (!d_z || !d_res)) || nx == 0 ||
+    if (!h || !d_g || !a.E || !a.lo || !a.hi || !a.rho || !a.w || !a.y || !a.gt || (!init && (!d_z || !a.res)) || nx == 0 ||
         nu == 0 || N == 0 || batch == 0)
         return GBDPCG_ERR_INVALID;
-    const gbdpcg_status st = admm_lin_rows<T>(nx, nu, mx, mu, N);
+    const gbdpcg_status st = admm_rows_status<T>(nx, nu, a, N);
     if (st != GBDPCG_OK) return st;
     DEVICE_SCOPE(h);
-    HIP_TRY(h, launch_admm_lin_update<T>(nx, nu, mx, mu, N, batch, d_g, d_E, d_lo, d_hi, d_rho, d_z, d_w, d_y, d_gt, d_res,
-                                         (hipStream_t)stream, init, shared));
+    HIP_TRY(h, launch_admm_rows_update<T>(nx, nu, a.mx, a.mu, N, batch, d_g, a.E, a.lo, a.hi, a.rho, d_z, a.w, a.y, a.gt, a.res,
+                                          (hipStream_t)stream, init, shared, a.cones));
     return GBDPCG_OK;
 }
 
-// What the rows of gbdpcg_admm_soc_* are refused for, before anything is written: what admm_lin_rows refuses, and row classes that
-// do not fit the blocks (lx > mx, lu > mu, cone rows with q = 0 or not a whole number of cones) INVALID.  Every INVALID comes
-// before UNSUPPORTED.
+// What one ADMM iteration (admm_step_impl) is refused for, before anything is written, reserved or captured: whatever the solve or
+// the update would refuse for its arguments or the shape, every INVALID before every UNSUPPORTED.  solve_limits: with the limits of
+// the solve itself (mappable, fused_fits).  The graph-create entries pass false and leave those to graph_create_impl and the
+// capture, which answer them behind the reservation of the handle's workspaces: the entry points have always differed there.
 template <typename T>
-gbdpcg_status admm_soc_rows(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu,
-                            uint32_t N)
+gbdpcg_status admm_step_refusal(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv, const T *d_C,
+                                const T *d_g, const T *d_c, const AdmmOperands<T> &a, const T *d_S, const T *d_gamma,
+                                const T *d_lambda, const uint32_t *d_iters, const T *d_z, bool shared, bool solve_limits = true)
 {
-    if (((uint64_t)mx + mu) * N == mu || !admm_soc_classes_ok(mx, mu, lx, qx, lu, qu)) return GBDPCG_ERR_INVALID;
-    return admm_lin_rows<T>(nx, nu, mx, mu, N);
-}
-
-// The splitting update for linear and cone rows (admm_soc.hip), one launch.  init: gbdpcg_admm_soc_init_*.
-template <typename T>
-gbdpcg_status admm_soc_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx, uint32_t qx,
-                                   uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const T *d_g, const T *d_E, const T *d_lo,
-                                   const T *d_hi, const T *d_rho, const T *d_z, T *d_w, T *d_y, T *d_gt, T *d_res, void *stream,
-                                   bool init, bool shared = false)
-{
-    if (!h || !d_g || !d_E || !d_lo || !d_hi || !d_rho || !d_w || !d_y || !d_gt || (!init && (!d_z || !d_res)) || nx == 0 ||
-        nu == 0 || N == 0 || batch == 0)
+    if (!h || !d_Ginv || !d_g || !d_c || !a.lo || !a.hi || !a.rho || !d_S || !d_gamma || !d_lambda || !d_iters || !d_z || !a.w ||
+        !a.y || !a.gt || !a.res || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch) || (a.rows && !a.E))
         return GBDPCG_ERR_INVALID;
-    const gbdpcg_status st = admm_soc_rows<T>(nx, nu, mx, mu, lx, qx, lu, qu, N);
-    if (st != GBDPCG_OK) return st;
-    DEVICE_SCOPE(h);
-    HIP_TRY(h, launch_admm_soc_update<T>(nx, nu, mx, mu, lx, qx, lu, qu, N, batch, d_g, d_E, d_lo, d_hi, d_rho, d_z, d_w, d_y, d_gt,
-                                         d_res, (hipStream_t)stream, init, shared));
+    const gbdpcg_status rows = a.rows ? admm_rows_status<T>(nx, nu, a, N) : GBDPCG_OK;
+    if (rows == GBDPCG_ERR_INVALID) return rows;
+    if (!schur_shape_ok<T>(h->dev, nx, nu) || rows != GBDPCG_OK) return GBDPCG_ERR_UNSUPPORTED;
+    if (solve_limits && (!mappable<T>(nx) || (shared && !fused_fits<T>(h->dev, nx, N)))) return GBDPCG_ERR_UNSUPPORTED;
     return GBDPCG_OK;
 }
 
-// One iteration of box-constrained ADMM on a kept factorisation of G + rho I: kkt_resolve_impl with the shifted gradient a.gt in
-// the place of g (the gamma launch and the recovery launch read the same gt), then the update, which alone reads g, on the same
-// stream.  What either part would refuse for its arguments or the shape is refused here, before anything is written.
+// One iteration of ADMM on a kept factorisation of G + rho I (box) or G + rho E'E (rows): kkt_resolve_impl with the shifted
+// gradient a.gt in the place of g (the gamma launch and the recovery launch read the same gt), then the update, which alone reads
+// g, on the same stream.
 template <typename T>
 gbdpcg_status admm_step_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_Ginv, const T *d_C,
                              const T *d_g, const T *d_c, const AdmmOperands<T> &a, const T *d_S, const T *d_Pinv, T *d_gamma,
                              T *d_lambda, T *d_r, T *d_p, T tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_exit, T *d_z,
                              hipStream_t stream, bool shared = false)
 {
-    if (!h || !d_Ginv || !d_g || !d_c || !a.lo || !a.hi || !a.rho || !d_S || !d_gamma || !d_lambda || !d_iters || !d_z || !a.w ||
-        !a.y || !a.gt || !a.res || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))
-        return GBDPCG_ERR_INVALID;
-    gbdpcg_status rows = a.lin ? (a.E ? admm_lin_rows<T>(nx, nu, a.mx, a.mu, N) : GBDPCG_ERR_INVALID) : GBDPCG_OK;
-    if (a.lin && a.soc && a.E) rows = admm_soc_rows<T>(nx, nu, a.mx, a.mu, a.lx, a.qx, a.lu, a.qu, N);
-    if (rows == GBDPCG_ERR_INVALID) return rows;
-    if (!schur_shape_ok<T>(h->dev, nx, nu) || !mappable<T>(nx) || (shared && !fused_fits<T>(h->dev, nx, N)) || rows != GBDPCG_OK)
-        return GBDPCG_ERR_UNSUPPORTED;
-    const gbdpcg_status st = kkt_resolve_impl<T>(h, nx, nu, N, batch, d_Ginv, d_C, a.gt, d_c, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p,
-                                                 tol, max_iter, d_iters, d_exit, d_z, stream, shared);
+    gbdpcg_status st = admm_step_refusal<T>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, a, d_S, d_gamma, d_lambda, d_iters, d_z, shared);
     if (st != GBDPCG_OK) return st;
-    if (a.soc)   // (linear and cone rows: the update of admm_soc.hip)
-        return admm_soc_update_impl<T>(h, nx, nu, a.mx, a.mu, a.lx, a.qx, a.lu, a.qu, N, batch, d_g, a.E, a.lo, a.hi, a.rho, d_z, a.w, a.y,
-                                       a.gt, a.res, stream, false, shared);
-    if (a.lin)   // (with the rows and the kept matrices of G + rho E'E: the same two calls, the update of admm_lin.hip)
-        return admm_lin_update_impl<T>(h, nx, nu, a.mx, a.mu, N, batch, d_g, a.E, a.lo, a.hi, a.rho, d_z, a.w, a.y, a.gt, a.res, stream,
-                                       false, shared);
+    st = kkt_resolve_impl<T>(h, nx, nu, N, batch, d_Ginv, d_C, a.gt, d_c, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter,
+                             d_iters, d_exit, d_z, stream, shared);
+    if (st != GBDPCG_OK) return st;
+    if (a.rows) return admm_rows_update_impl<T>(h, nx, nu, N, batch, d_g, a, d_z, stream, false, shared);
     return admm_update_impl<T>(h, nx, nu, N, batch, d_g, a.lo, a.hi, a.rho, d_z, a.w, a.y, a.gt, a.res, stream, false);
 }
 
@@ -1537,189 +1519,134 @@ GBDPCG_REG(f32, float)
 GBDPCG_REG(f64, double)
 #undef GBDPCG_REG
 
-// ---- box constraints on a kept factorisation: ADMM iterations whose solve is gbdpcg_kkt_resolve_* on the matrices of G + rho I.
-// SHARED: the twin on one problem's Ginv, C, S, Pinv (the box, rho and the splitting state stay per problem).
+// ---- ADMM iterations on a kept factorisation, whose solve is gbdpcg_kkt_resolve_*.  Three families of one shape:
+//   admm       box lo <= z <= hi, the matrices of G + rho I
+//   admm_lin   stage-wise linear rows lo <= E z <= hi, the matrices of G + rho E'E (gbdpcg_admm_lin_form_*)
+//   admm_soc   second-order cone rows next to the linear ones, the same matrices
+// Each has init, update, step and graph_create_step, the last two with a _shared twin on one problem's Ginv, C, S, Pinv (and E);
+// the set, rho and the splitting state stay per problem.  A family is described by four macros, defined in front of its entries:
+//   ADMM_SIZES        the sizes between h and N
+//   ADMM_SET(TYPE)    the set, in front of d_rho
+//   ADMM_CONES        the declaration of `cones`, the RowClasses of the family, where it has any
+//   ADMM_OPERANDS     the initialiser of its AdmmOperands
 #define GBDPCG_ADMM_STEP(NAME, SUF, TYPE, SHARED)                                                                                   \
-    gbdpcg_status gbdpcg_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const TYPE *d_Ginv,  \
-                                        const TYPE *d_C, const TYPE *d_g, const TYPE *d_c, const TYPE *d_lo, const TYPE *d_hi,        \
-                                        const TYPE *d_rho, const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda,        \
-                                        TYPE *d_r, TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters,                        \
-                                        uint8_t *d_max_iter_exit, TYPE *d_z, TYPE *d_w, TYPE *d_y, TYPE *d_gt, TYPE *d_res,           \
-                                        void *stream)                                                                               \
+    gbdpcg_status gbdpcg_##NAME##_##SUF(gbdpcg_handle_t h, ADMM_SIZES, uint32_t N, uint32_t batch, const TYPE *d_Ginv,              \
+                                        const TYPE *d_C, const TYPE *d_g, const TYPE *d_c, ADMM_SET(TYPE), const TYPE *d_rho,       \
+                                        const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda, TYPE *d_r, TYPE *d_p,   \
+                                        TYPE tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, TYPE *d_z,        \
+                                        TYPE *d_w, TYPE *d_y, TYPE *d_gt, TYPE *d_res, void *stream)                                \
     {                                                                                                                               \
-        const AdmmOperands<TYPE> a{d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res};                                                       \
-        return admm_step_impl<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, a, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol,    \
+        ADMM_CONES                                                                                                                  \
+        const AdmmOperands<TYPE> a{ADMM_OPERANDS};                                                                                  \
+        return admm_step_impl<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, a, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol,   \
                                     max_iter, d_iters, d_max_iter_exit, d_z, (hipStream_t)stream, SHARED);                          \
     }                                                                                                                               \
-    gbdpcg_status gbdpcg_graph_create_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,         \
-                                                     const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c,           \
-                                                     const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho, const TYPE *d_S,          \
-                                                     const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda, TYPE *d_r, TYPE *d_p,         \
-                                                     TYPE tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,       \
-                                                     TYPE *d_z, TYPE *d_w, TYPE *d_y, TYPE *d_gt, TYPE *d_res, gbdpcg_graph_t *out)   \
+    gbdpcg_status gbdpcg_graph_create_##NAME##_##SUF(gbdpcg_handle_t h, ADMM_SIZES, uint32_t N, uint32_t batch, const TYPE *d_Ginv, \
+                                                     const TYPE *d_C, const TYPE *d_g, const TYPE *d_c, ADMM_SET(TYPE),             \
+                                                     const TYPE *d_rho, const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma,         \
+                                                     TYPE *d_lambda, TYPE *d_r, TYPE *d_p, TYPE tol, uint32_t max_iter,             \
+                                                     uint32_t *d_iters, uint8_t *d_max_iter_exit, TYPE *d_z, TYPE *d_w, TYPE *d_y,  \
+                                                     TYPE *d_gt, TYPE *d_res, gbdpcg_graph_t *out)                                  \
     {                                                                                                                               \
-        /* what the captured calls would refuse is refused before anything is reserved or captured */                                \
-        if (!h || !out || !d_Ginv || !d_g || !d_c || !d_lo || !d_hi || !d_rho || !d_S || !d_gamma || !d_lambda || !d_iters ||       \
-            !d_z || !d_w || !d_y || !d_gt || !d_res || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))                       \
-            return GBDPCG_ERR_INVALID;                                                                                              \
-        if (!schur_shape_ok<TYPE>(h->dev, nx, nu)) return GBDPCG_ERR_UNSUPPORTED;                                                   \
-        const AdmmOperands<TYPE> a{d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res};                                                       \
+        if (!out) return GBDPCG_ERR_INVALID;                                                                                        \
+        *out = nullptr;                                                                                                             \
+        ADMM_CONES                                                                                                                  \
+        const AdmmOperands<TYPE> a{ADMM_OPERANDS};                                                                                  \
+        /* what the captured calls would refuse for their arguments is refused before anything is reserved or captured */           \
+        const gbdpcg_status st = admm_step_refusal<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, a, d_S, d_gamma, d_lambda,     \
+                                                         d_iters, d_z, SHARED, false);                                              \
+        if (st != GBDPCG_OK) return st;                                                                                             \
         KktOperands<TYPE> k{nu, nullptr, d_C, d_g, d_c, const_cast<TYPE *>(d_Ginv), d_z};                                           \
         k.resolve = true;                                                                                                           \
         k.shared = SHARED;                                                                                                          \
         k.admm = &a;                                                                                                                \
-        return graph_create_impl<TYPE>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters,            \
+        return graph_create_impl<TYPE>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters,           \
                                        d_max_iter_exit, out, -1, &k);                                                               \
     }
+#define GBDPCG_ADMM_STEPS(NAME, SUF, TYPE)                                                                                          \
+    GBDPCG_ADMM_STEP(NAME, SUF, TYPE, false)                                                                                        \
+    GBDPCG_ADMM_STEP(NAME##_shared, SUF, TYPE, true)
+// init and update of a family with rows: thin forwards to admm_rows_update_impl (init has neither d_z nor d_res)
+#define GBDPCG_ADMM_ROWS(NAME, SUF, TYPE)                                                                                           \
+    gbdpcg_status gbdpcg_##NAME##_init_##SUF(gbdpcg_handle_t h, ADMM_SIZES, uint32_t N, uint32_t batch, const TYPE *d_g,            \
+                                             ADMM_SET(TYPE), const TYPE *d_rho, TYPE *d_w, TYPE *d_y, TYPE *d_gt, void *stream)     \
+    {                                                                                                                               \
+        TYPE *const d_res = nullptr;                                                                                                \
+        ADMM_CONES                                                                                                                  \
+        const AdmmOperands<TYPE> a{ADMM_OPERANDS};                                                                                  \
+        return admm_rows_update_impl<TYPE>(h, nx, nu, N, batch, d_g, a, nullptr, stream, true);                                     \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_##NAME##_update_##SUF(gbdpcg_handle_t h, ADMM_SIZES, uint32_t N, uint32_t batch, const TYPE *d_g,          \
+                                               ADMM_SET(TYPE), const TYPE *d_rho, const TYPE *d_z, TYPE *d_w, TYPE *d_y,            \
+                                               TYPE *d_gt, TYPE *d_res, void *stream)                                               \
+    {                                                                                                                               \
+        ADMM_CONES                                                                                                                  \
+        const AdmmOperands<TYPE> a{ADMM_OPERANDS};                                                                                  \
+        return admm_rows_update_impl<TYPE>(h, nx, nu, N, batch, d_g, a, d_z, stream, false);                                        \
+    }
+
+#define ADMM_SIZES uint32_t nx, uint32_t nu
+#define ADMM_SET(TYPE) const TYPE *d_lo, const TYPE *d_hi
+#define ADMM_CONES
+#define ADMM_OPERANDS d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res
 #define GBDPCG_ADMM(SUF, TYPE)                                                                                                      \
-    gbdpcg_status gbdpcg_admm_init_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const TYPE *d_g,    \
-                                         const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho, TYPE *d_w, TYPE *d_y, TYPE *d_gt,     \
+    gbdpcg_status gbdpcg_admm_init_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const TYPE *d_g,  \
+                                         const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho, TYPE *d_w, TYPE *d_y, TYPE *d_gt,   \
                                          void *stream)                                                                              \
     {                                                                                                                               \
-        return admm_update_impl<TYPE>(h, nx, nu, N, batch, d_g, d_lo, d_hi, d_rho, nullptr, d_w, d_y, d_gt, nullptr, stream, true);  \
+        return admm_update_impl<TYPE>(h, nx, nu, N, batch, d_g, d_lo, d_hi, d_rho, nullptr, d_w, d_y, d_gt, nullptr, stream, true); \
     }                                                                                                                               \
-    gbdpcg_status gbdpcg_admm_update_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const TYPE *d_g,  \
-                                           const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho, const TYPE *d_z, TYPE *d_w,         \
-                                           TYPE *d_y, TYPE *d_gt, TYPE *d_res, void *stream)                                         \
+    gbdpcg_status gbdpcg_admm_update_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const TYPE *d_g,\
+                                           const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho, const TYPE *d_z, TYPE *d_w,       \
+                                           TYPE *d_y, TYPE *d_gt, TYPE *d_res, void *stream)                                        \
     {                                                                                                                               \
-        return admm_update_impl<TYPE>(h, nx, nu, N, batch, d_g, d_lo, d_hi, d_rho, d_z, d_w, d_y, d_gt, d_res, stream, false);       \
+        return admm_update_impl<TYPE>(h, nx, nu, N, batch, d_g, d_lo, d_hi, d_rho, d_z, d_w, d_y, d_gt, d_res, stream, false);      \
     }                                                                                                                               \
-    GBDPCG_ADMM_STEP(admm_step, SUF, TYPE, false)                                                                                   \
-    GBDPCG_ADMM_STEP(admm_step_shared, SUF, TYPE, true)
+    GBDPCG_ADMM_STEPS(admm_step, SUF, TYPE)
 GBDPCG_ADMM(f32, float)
 GBDPCG_ADMM(f64, double)
 #undef GBDPCG_ADMM
-#undef GBDPCG_ADMM_STEP
+#undef ADMM_SIZES
+#undef ADMM_SET
+#undef ADMM_OPERANDS
 
-// ---- stage-wise linear inequality rows lo <= E z <= hi on a kept factorisation of G + rho E'E (admm_lin.hip): the formation of
-// Gt, init, update, and the iteration whose solve is gbdpcg_kkt_resolve_*.  SHARED: one problem's Ginv, C, S, Pinv and E.
-#define GBDPCG_ADMM_LIN_STEP(NAME, SUF, TYPE, SHARED)                                                                               \
-    gbdpcg_status gbdpcg_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,            \
-                                        uint32_t batch, const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c,        \
-                                        const TYPE *d_E, const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho, const TYPE *d_S,      \
-                                        const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda, TYPE *d_r, TYPE *d_p, TYPE tol,            \
-                                        uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, TYPE *d_z, TYPE *d_w,        \
-                                        TYPE *d_y, TYPE *d_gt, TYPE *d_res, void *stream)                                            \
-    {                                                                                                                               \
-        const AdmmOperands<TYPE> a{d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res, true, d_E, mx, mu};                                    \
-        return admm_step_impl<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, a, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol,    \
-                                    max_iter, d_iters, d_max_iter_exit, d_z, (hipStream_t)stream, SHARED);                          \
-    }                                                                                                                               \
-    gbdpcg_status gbdpcg_graph_create_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,           \
-                                                     uint32_t N, uint32_t batch, const TYPE *d_Ginv, const TYPE *d_C,               \
-                                                     const TYPE *d_g, const TYPE *d_c, const TYPE *d_E, const TYPE *d_lo,           \
-                                                     const TYPE *d_hi, const TYPE *d_rho, const TYPE *d_S, const TYPE *d_Pinv,       \
-                                                     TYPE *d_gamma, TYPE *d_lambda, TYPE *d_r, TYPE *d_p, TYPE tol,                  \
-                                                     uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, TYPE *d_z,      \
-                                                     TYPE *d_w, TYPE *d_y, TYPE *d_gt, TYPE *d_res, gbdpcg_graph_t *out)             \
-    {                                                                                                                               \
-        /* what the captured calls would refuse is refused before anything is reserved or captured */                                \
-        if (!h || !out || !d_Ginv || !d_g || !d_c || !d_E || !d_lo || !d_hi || !d_rho || !d_S || !d_gamma || !d_lambda ||           \
-            !d_iters || !d_z || !d_w || !d_y || !d_gt || !d_res || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))           \
-            return GBDPCG_ERR_INVALID;                                                                                              \
-        const gbdpcg_status rows = admm_lin_rows<TYPE>(nx, nu, mx, mu, N);                                                          \
-        if (rows == GBDPCG_ERR_INVALID) return rows;                                                                                \
-        if (!schur_shape_ok<TYPE>(h->dev, nx, nu) || rows != GBDPCG_OK) return GBDPCG_ERR_UNSUPPORTED;                              \
-        const AdmmOperands<TYPE> a{d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res, true, d_E, mx, mu};                                    \
-        KktOperands<TYPE> k{nu, nullptr, d_C, d_g, d_c, const_cast<TYPE *>(d_Ginv), d_z};                                           \
-        k.resolve = true;                                                                                                           \
-        k.shared = SHARED;                                                                                                          \
-        k.admm = &a;                                                                                                                \
-        return graph_create_impl<TYPE>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters,            \
-                                       d_max_iter_exit, out, -1, &k);                                                               \
-    }
+// (admm_lin: ADMM_CONES stays empty)
+#define ADMM_SIZES uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu
+#define ADMM_SET(TYPE) const TYPE *d_E, const TYPE *d_lo, const TYPE *d_hi
+#define ADMM_OPERANDS d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res, true, d_E, mx, mu
 #define GBDPCG_ADMM_LIN(SUF, TYPE)                                                                                                  \
-    gbdpcg_status gbdpcg_admm_lin_form_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,       \
-                                             uint32_t batch, const TYPE *d_G, const TYPE *d_E, const TYPE *d_rho, TYPE *d_Gt,        \
+    gbdpcg_status gbdpcg_admm_lin_form_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,     \
+                                             uint32_t batch, const TYPE *d_G, const TYPE *d_E, const TYPE *d_rho, TYPE *d_Gt,       \
                                              void *stream)                                                                          \
     {                                                                                                                               \
         return admm_lin_form_impl<TYPE>(h, nx, nu, mx, mu, N, batch, d_G, d_E, d_rho, d_Gt, stream);                                \
     }                                                                                                                               \
-    gbdpcg_status gbdpcg_admm_lin_init_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,       \
-                                             uint32_t batch, const TYPE *d_g, const TYPE *d_E, const TYPE *d_lo, const TYPE *d_hi,   \
-                                             const TYPE *d_rho, TYPE *d_w, TYPE *d_y, TYPE *d_gt, void *stream)                      \
-    {                                                                                                                               \
-        return admm_lin_update_impl<TYPE>(h, nx, nu, mx, mu, N, batch, d_g, d_E, d_lo, d_hi, d_rho, nullptr, d_w, d_y, d_gt, nullptr, \
-                                          stream, true);                                                                            \
-    }                                                                                                                               \
-    gbdpcg_status gbdpcg_admm_lin_update_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,     \
-                                               uint32_t batch, const TYPE *d_g, const TYPE *d_E, const TYPE *d_lo,                  \
-                                               const TYPE *d_hi, const TYPE *d_rho, const TYPE *d_z, TYPE *d_w, TYPE *d_y,           \
-                                               TYPE *d_gt, TYPE *d_res, void *stream)                                                \
-    {                                                                                                                               \
-        return admm_lin_update_impl<TYPE>(h, nx, nu, mx, mu, N, batch, d_g, d_E, d_lo, d_hi, d_rho, d_z, d_w, d_y, d_gt, d_res,      \
-                                          stream, false);                                                                           \
-    }                                                                                                                               \
-    GBDPCG_ADMM_LIN_STEP(admm_lin_step, SUF, TYPE, false)                                                                           \
-    GBDPCG_ADMM_LIN_STEP(admm_lin_step_shared, SUF, TYPE, true)
+    GBDPCG_ADMM_ROWS(admm_lin, SUF, TYPE)                                                                                           \
+    GBDPCG_ADMM_STEPS(admm_lin_step, SUF, TYPE)
 GBDPCG_ADMM_LIN(f32, float)
 GBDPCG_ADMM_LIN(f64, double)
 #undef GBDPCG_ADMM_LIN
-#undef GBDPCG_ADMM_LIN_STEP
+#undef ADMM_SIZES
+#undef ADMM_CONES
+#undef ADMM_OPERANDS
 
-// ---- second-order cone rows next to the linear ones (admm_soc.hip): init, update, and the iteration whose solve is
-// gbdpcg_kkt_resolve_* on the matrices of G + rho E'E (formed by gbdpcg_admm_lin_form_*).  SHARED: one problem's Ginv, C, S, Pinv, E.
-#define GBDPCG_ADMM_SOC_STEP(NAME, SUF, TYPE, SHARED)                                                                               \
-    gbdpcg_status gbdpcg_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,           \
-                                        uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const TYPE *d_Ginv,       \
-                                        const TYPE *d_C, const TYPE *d_g, const TYPE *d_c, const TYPE *d_E, const TYPE *d_lo,         \
-                                        const TYPE *d_hi, const TYPE *d_rho, const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma,      \
-                                        TYPE *d_lambda, TYPE *d_r, TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters,        \
-                                        uint8_t *d_max_iter_exit, TYPE *d_z, TYPE *d_w, TYPE *d_y, TYPE *d_gt, TYPE *d_res,           \
-                                        void *stream)                                                                               \
-    {                                                                                                                               \
-        const AdmmOperands<TYPE> a{d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res, true, d_E, mx, mu, true, lx, qx, lu, qu};              \
-        return admm_step_impl<TYPE>(h, nx, nu, N, batch, d_Ginv, d_C, d_g, d_c, a, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol,    \
-                                    max_iter, d_iters, d_max_iter_exit, d_z, (hipStream_t)stream, SHARED);                          \
-    }                                                                                                                               \
-    gbdpcg_status gbdpcg_graph_create_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,           \
-                                                     uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, \
-                                                     const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c,           \
-                                                     const TYPE *d_E, const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho,          \
-                                                     const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda, TYPE *d_r,   \
-                                                     TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters,                      \
-                                                     uint8_t *d_max_iter_exit, TYPE *d_z, TYPE *d_w, TYPE *d_y, TYPE *d_gt,           \
-                                                     TYPE *d_res, gbdpcg_graph_t *out)                                               \
-    {                                                                                                                               \
-        /* what the captured calls would refuse is refused before anything is reserved or captured */                                \
-        if (out) *out = nullptr;                                                                                                    \
-        if (!h || !out || !d_Ginv || !d_g || !d_c || !d_E || !d_lo || !d_hi || !d_rho || !d_S || !d_gamma || !d_lambda ||           \
-            !d_iters || !d_z || !d_w || !d_y || !d_gt || !d_res || (!d_C && N > 1) || nu == 0 || !shape_ok(nx, N, batch))           \
-            return GBDPCG_ERR_INVALID;                                                                                              \
-        const gbdpcg_status rows = admm_soc_rows<TYPE>(nx, nu, mx, mu, lx, qx, lu, qu, N);                                          \
-        if (rows == GBDPCG_ERR_INVALID) return rows;                                                                                \
-        if (!schur_shape_ok<TYPE>(h->dev, nx, nu) || rows != GBDPCG_OK) return GBDPCG_ERR_UNSUPPORTED;                              \
-        const AdmmOperands<TYPE> a{d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res, true, d_E, mx, mu, true, lx, qx, lu, qu};              \
-        KktOperands<TYPE> k{nu, nullptr, d_C, d_g, d_c, const_cast<TYPE *>(d_Ginv), d_z};                                           \
-        k.resolve = true;                                                                                                           \
-        k.shared = SHARED;                                                                                                          \
-        k.admm = &a;                                                                                                                \
-        return graph_create_impl<TYPE>(h, nx, N, batch, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, tol, max_iter, d_iters,            \
-                                       d_max_iter_exit, out, -1, &k);                                                               \
-    }
+// (admm_soc: ADMM_SET stays that of admm_lin)
+#define ADMM_SIZES uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu
+#define ADMM_CONES const RowClasses cones{lx, qx, lu, qu};
+#define ADMM_OPERANDS d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res, true, d_E, mx, mu, &cones
 #define GBDPCG_ADMM_SOC(SUF, TYPE)                                                                                                  \
-    gbdpcg_status gbdpcg_admm_soc_init_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,      \
-                                             uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const TYPE *d_g,     \
-                                             const TYPE *d_E, const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho, TYPE *d_w,      \
-                                             TYPE *d_y, TYPE *d_gt, void *stream)                                                    \
-    {                                                                                                                               \
-        return admm_soc_update_impl<TYPE>(h, nx, nu, mx, mu, lx, qx, lu, qu, N, batch, d_g, d_E, d_lo, d_hi, d_rho, nullptr, d_w,   \
-                                          d_y, d_gt, nullptr, stream, true);                                                        \
-    }                                                                                                                               \
-    gbdpcg_status gbdpcg_admm_soc_update_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,    \
-                                               uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const TYPE *d_g,   \
-                                               const TYPE *d_E, const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho,               \
-                                               const TYPE *d_z, TYPE *d_w, TYPE *d_y, TYPE *d_gt, TYPE *d_res, void *stream)          \
-    {                                                                                                                               \
-        return admm_soc_update_impl<TYPE>(h, nx, nu, mx, mu, lx, qx, lu, qu, N, batch, d_g, d_E, d_lo, d_hi, d_rho, d_z, d_w, d_y,  \
-                                          d_gt, d_res, stream, false);                                                              \
-    }                                                                                                                               \
-    GBDPCG_ADMM_SOC_STEP(admm_soc_step, SUF, TYPE, false)                                                                           \
-    GBDPCG_ADMM_SOC_STEP(admm_soc_step_shared, SUF, TYPE, true)
+    GBDPCG_ADMM_ROWS(admm_soc, SUF, TYPE)                                                                                           \
+    GBDPCG_ADMM_STEPS(admm_soc_step, SUF, TYPE)
 GBDPCG_ADMM_SOC(f32, float)
 GBDPCG_ADMM_SOC(f64, double)
 #undef GBDPCG_ADMM_SOC
-#undef GBDPCG_ADMM_SOC_STEP
+#undef ADMM_SIZES
+#undef ADMM_SET
+#undef ADMM_CONES
+#undef ADMM_OPERANDS
+#undef GBDPCG_ADMM_ROWS
+#undef GBDPCG_ADMM_STEPS
+#undef GBDPCG_ADMM_STEP
 
 // ---- the KKT backward pass: the gradients of a scalar in G and C from (z, lambda) and the adjoint pair, and the adjoint solve +
 // gradient launch as one call / one graph.  SHARED: one problem's Ginv, C, S, Pinv, and gG, gC summed over the batch.

@@ -257,33 +257,29 @@ template <typename T>
 hipError_t launch_admm_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *g, const T *lo, const T *hi, const T *rho,
                               const T *z, T *w, T *y, T *gt, T *res, hipStream_t s, bool init);
 
-// ---- admm_lin.hip : ADMM with stage-wise linear rows lo <= E z <= hi (layouts in include/gbdpcg.h), two kernels.
+// ---- admm_rows.hip : ADMM with stage-wise rows on E z, linear (lo <= E z <= hi) or in second-order cones; the layouts are in
+// include/gbdpcg.h, the lines that define every bit in the head of the file.  Two kernels:
 //     form:   Gt = G + rho_b E'E per diagonal block, one lane per entry (Gt may be G)
-//     update: w <- clip(E z + y), y <- (E z + y) - w, gt <- g - rho_b E'(w - y), res[2b] = ||E z - w||_inf,
-//             res[2b+1] = rho_b ||E'(w - w_old)||_inf; one workgroup per problem, the horizon in chunks of admm_lin_knot_chunk knots
-// init: w <- clip(w), gt <- g - rho_b E'(w - y); y is not written, z and res are not looked at (may be null).
+//     update: w <- projection of E z + y, y, gt, res; one workgroup per problem, the horizon in chunks of admm_rows_knot_chunk knots
+// init: the update without z (w is projected itself), y is not written, z and res are not looked at (may be null).
 // shared: E is one problem's blocks, used by every problem of the batch.
+// cones (the gbdpcg_admm_soc_* calls; null: every row is linear): the rows behind the first lx / lu of a block are cones of
+// dimension qx / qu, lo holds their offsets.  With cones the launch is the kernel's CONES instantiation, whatever the classes say.
+struct RowClasses {
+    uint32_t lx, qx, lu, qu;
+};
 template <typename T>
 hipError_t launch_admm_lin_form(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *G, const T *E,
                                 const T *rho, T *Gt, hipStream_t s);
 template <typename T>
-hipError_t launch_admm_lin_update(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *g, const T *E,
-                                  const T *lo, const T *hi, const T *rho, const T *z, T *w, T *y, T *gt, T *res, hipStream_t s,
-                                  bool init, bool shared = false);
+hipError_t launch_admm_rows_update(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *g,
+                                   const T *E, const T *lo, const T *hi, const T *rho, const T *z, T *w, T *y, T *gt, T *res,
+                                   hipStream_t s, bool init, bool shared = false, const RowClasses *cones = nullptr);
 // (mx, mu <= 64 and one knot's E blocks, z, t, d within the kernel's LDS)
-template <typename T> bool admm_lin_shape_ok(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu);
-uint32_t admm_lin_knot_chunk(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu);
-
-// ---- admm_soc.hip : the update of admm_lin.hip with second-order cone rows (layouts and lines in include/gbdpcg.h), one kernel.
-// In every x block the first lx rows are linear, the other mx - lx are consecutive cones of dimension qx, head row first (lu, qu:
-// the u blocks); on a cone row lo holds the offset f and hi is not read.  Same chunks, same LDS budget, same refusals as
-// launch_admm_lin_update, and the row classes must pass admm_soc_classes_ok.  The formation is launch_admm_lin_form.
-template <typename T>
-hipError_t launch_admm_soc_update(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu,
-                                  uint32_t N, uint32_t batch, const T *g, const T *E, const T *lo, const T *hi, const T *rho, const T *z,
-                                  T *w, T *y, T *gt, T *res, hipStream_t s, bool init, bool shared = false);
+template <typename T> bool admm_rows_shape_ok(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu);
+uint32_t admm_rows_knot_chunk(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu);
 // (lx <= mx, lu <= mu; where a block has cone rows its q is not 0 and divides their number; q is ignored where it has none)
-bool admm_soc_classes_ok(uint32_t mx, uint32_t mu, uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu);
+bool admm_rows_classes_ok(uint32_t mx, uint32_t mu, const RowClasses &c);
 
 // ---- kkt_grad.hip : the gradients of a scalar in the packed KKT blocks from the forward pair (z, lambda) and the adjoint pair
 // (az, alam), one launch.  gG has the layout of G, gC that of C; either may be null (not written):

@@ -1,16 +1,21 @@
 #!/usr/bin/env python3
-"""What the update with second-order cone rows costs next to the update with linear rows of the same row counts, in ONE process on
-one device:
-    python gbd-pcg_amd/tools/admm_soc_time.py [--warmup W] [--steps K] [--rounds R] > profiles/rNN_admm_soc.txt
+"""What the ADMM updates with stage-wise rows cost next to each other, next to the box update and next to the solve, in ONE process
+on one device:
+    python gbd-pcg_amd/tools/admm_rows_time.py [--warmup W] [--steps K] [--rounds R] > profiles/rNN_admm_rows.txt
 
 At 1024 x (nx 14, nu 7, N 128) with mx = 2 linear rows on x and mu = 5 rows on u (1 linear + one q = 4 cone: the norm of three
 inputs bounded by a fourth), random E, fp32 and fp64: the gbdpcg_admm_soc_update_* launch alone and the gbdpcg_admm_lin_update_*
-launch alone on the same E and row counts (K launches between two device events each), then windows of K graph replays,
-kkt_resolve / admm_lin_step / admm_soc_step alternating, R rounds; median and range over the rounds.  The factorisation is that of
-G + rho E'E (admm_lin_form, kkt_step; rho = 2); the linear bounds hold every row within half of the largest row of the solution
-without them, the cone rows have the offset 0 (admm_lin: the same bounds on all rows); every replay starts from lambda = 0.
-Algorithmic bytes, s = element size: (6 nw + 3 nz + ne) s + 3 s per problem for the lin update; a cone row reads no hi: one element
-less."""
+launch alone on the same E and row counts, the gbdpcg_admm_lin_form_* launch alone and the gbdpcg_admm_update_* (box) launch alone
+on buffers of its own (K launches between two device events each), then windows of K graph replays, kkt_resolve / admm_lin_step /
+admm_soc_step alternating, R rounds; median and range over the rounds.  The factorisation is that of G + rho E'E (admm_lin_form,
+kkt_step; rho = 2); the linear bounds hold every row within half of the largest row of the solution without them, the cone rows
+have the offset 0 (admm_lin: the same bounds on all rows); every replay starts from lambda = 0 (the zero fill is inside every
+window alike).  Algorithmic bytes, s = element size:
+    lin update  (6 nw + 3 nz + ne) s + 3 s per problem     w, y, lo, hi in, w, y out; z, g in, gt out; E once; rho and two norms
+                (a cone row reads no hi: one element less; the soc update is rated with the lin update's bytes)
+    lin form    (2 ng + ne) s + s per problem              G in, Gt out; E once (its re-reads are the caches'); rho
+    box update  9 nz s + 3 s per problem                   (tools/admm_time.py)
+each over its time, against the HBM rates: 8 TB/s peak, about 6.3 TB/s achievable."""
 import argparse
 import statistics
 import sys
@@ -21,6 +26,8 @@ import torch
 sys.path.insert(0, __file__.rsplit("/gbd-pcg_amd/", 1)[0])
 from gbd_pcg_amd import binding  # noqa: E402
 from oracle import schur_oracle as so  # noqa: E402
+
+HBM_PEAK, HBM_ACHIEVABLE = 8.0e12, 6.3e12   # bytes / s
 
 
 def window(fn, count):
@@ -37,6 +44,11 @@ def stat(v):
     return f"{statistics.median(v):.4f} ms (min {min(v):.4f}, max {max(v):.4f})"
 
 
+def rate(nbytes, ms):
+    r = nbytes / (ms * 1e-3)
+    return f"{nbytes / 1e6:.1f} MB -> {r / 1e12:.2f} TB/s, {100.0 * r / HBM_PEAK:.0f} % of peak, {100.0 * r / HBM_ACHIEVABLE:.0f} % of achievable"
+
+
 def one_shape(s, nx, nu, N, B, mx, mu, cones, dtype, a):
     td = torch.float32 if dtype == np.float32 else torch.float64
     base = so.gen(nx, nu, N, seed=77, batch=8, dtype=dtype)
@@ -44,7 +56,7 @@ def one_shape(s, nx, nu, N, B, mx, mu, cones, dtype, a):
     arr["g"] = arr["g"] * (1.0 + np.arange(B, dtype=dtype)[:, None] / B)
     G, C, g, c = (torch.from_numpy(np.ascontiguousarray(arr[k].reshape(-1))).cuda() for k in "GCgc")
     sv, sw = nx + nu, mx + mu
-    nz, nw, ne = sv * N - nu, sw * N - mu, (mx * nx + mu * nu) * N - mu * nu
+    nz, nw, ne, ng = sv * N - nu, sw * N - mu, (mx * nx + mu * nu) * N - mu * nu, (nx * nx + nu * nu) * N - nu * nu
     E = torch.from_numpy(np.tile((0.5 * np.random.default_rng(3).standard_normal(ne)).astype(dtype), B)).cuda()
     rho = torch.full((B,), 2.0, dtype=td, device="cuda")
     S = torch.empty(B * 3 * nx * nx * N, dtype=td, device="cuda")
@@ -83,6 +95,9 @@ def one_shape(s, nx, nu, N, B, mx, mu, cones, dtype, a):
                                   it, fl, z, L["w"], L["y"], L["gt"], L["res"])
     g_soc = s.graph_admm_soc_step(nx, nu, mx, mu, cones, N, B, Ginv, C, g, c, E, slo, hi, rho, S, Pinv, gamma, lam, None, None, a.tol,
                                   a.max_iter, it, fl, z, Q["w"], Q["y"], Q["gt"], Q["res"])
+    # the box update of the same run, on buffers of its own in the layout of z
+    blo, bhi = torch.full_like(g, -1.0), torch.full_like(g, 1.0)
+    bw, by, bgt, bres = torch.zeros_like(g), torch.zeros_like(g), torch.empty_like(g), torch.empty(B, 2, dtype=td, device="cuda")
 
     def replay(gr):
         lam.zero_()
@@ -90,6 +105,8 @@ def one_shape(s, nx, nu, N, B, mx, mu, cones, dtype, a):
 
     calls = {"soc update": lambda: s.admm_soc_update(nx, nu, mx, mu, cones, N, B, g, E, slo, hi, rho, z, Q["w"], Q["y"], Q["gt"], res=Q["res"]),
              "lin update": lambda: s.admm_lin_update(nx, nu, mx, mu, N, B, g, E, lo, hi, rho, z, L["w"], L["y"], L["gt"], res=L["res"]),
+             "lin form": lambda: s.admm_lin_form(nx, nu, mx, mu, N, B, G, E, rho, Gt=Gt),
+             "box update": lambda: s.admm_update(nx, nu, N, B, g, blo, bhi, rho, z, bw, by, bgt, res=bres),
              "resolve replay": lambda: replay(g_res), "lin step replay": lambda: replay(g_lin), "soc step replay": lambda: replay(g_soc)}
     for _ in range(30):      # a few iterations first: the loops do what they are for
         g_lin.launch()
@@ -107,14 +124,19 @@ def one_shape(s, nx, nu, N, B, mx, mu, cones, dtype, a):
             t[k].append(window(fn, a.steps))
     med = {k: statistics.median(v) for k, v in t.items()}
     es = np.dtype(dtype).itemsize
-    nbytes = ((6 * nw + 3 * nz + ne) * es + 3 * es) * B
-    for k in ("soc update", "lin update"):
-        print(f"  {k + ' launch alone':30s} {stat(t[k])}; {nbytes / 1e6:.1f} MB of the lin update -> {nbytes / (med[k] * 1e-3) / 1e12:.2f} TB/s")
+    must = {"soc update": ((6 * nw + 3 * nz + ne) * es + 3 * es) * B, "lin form": ((2 * ng + ne) * es + es) * B,
+            "box update": (9 * nz * es + 3 * es) * B}
+    must["lin update"] = must["soc update"]
+    for k in ("soc update", "lin update", "lin form", "box update"):
+        print(f"  {k + ' launch alone':30s} {stat(t[k])}; algorithmic bytes {rate(must[k], med[k])}")
     for k, name in (("resolve replay", "kkt_resolve"), ("lin step replay", "admm_lin_step"), ("soc step replay", "admm_soc_step")):
         print(f"  {name + ' graph replay':30s} {stat(t[k])}")
     print(f"  soc update / lin update: {med['soc update'] / med['lin update']:.2f} x ({1e3 * (med['soc update'] - med['lin update']):+.1f} us);  "
           f"soc step replay - resolve replay {1e3 * (med['soc step replay'] - med['resolve replay']):.1f} us, "
           f"lin step replay - resolve replay {1e3 * (med['lin step replay'] - med['resolve replay']):.1f} us")
+    bl, bb = must["lin update"] / med["lin update"], must["box update"] / med["box update"]
+    print(f"  lin update / box update: time {med['lin update'] / med['box update']:.2f} x, bytes {must['lin update'] / must['box update']:.2f} x, "
+          f"bytes over time {bl / bb:.2f} x;  lin update alone / resolve replay {100.0 * med['lin update'] / med['resolve replay']:.1f} %")
     for gr in (g_res, g_lin, g_soc):
         gr.close()
 
@@ -129,7 +151,7 @@ def main():
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X: there is no CPU path"
     s = binding.Solver(0)
-    print(f"# admm_soc_time.py --warmup {a.warmup} --steps {a.steps} --rounds {a.rounds} --tol {a.tol} --max-iter {a.max_iter}; "
+    print(f"# admm_rows_time.py --warmup {a.warmup} --steps {a.steps} --rounds {a.rounds} --tol {a.tol} --max-iter {a.max_iter}; "
           f"{torch.cuda.get_device_name(0)}; {s.lib.gbdpcg_version().decode()}")
     for dtype in (np.float32, np.float64):
         nx, nu, N, B, mx, mu, cones = 14, 7, 128, 1024, 2, 5, (2, 1, 1, 4)

@@ -607,7 +607,9 @@ gbdpcg_status gbdpcg_kkt_residual_reg_f64(gbdpcg_handle_t h, uint32_t nx, uint32
  *    own problem only.
  * Null handle or required pointer, nx, nu, N or batch == 0: GBDPCG_ERR_INVALID, nothing is written (d_r, d_p, d_max_iter_exit and
  * d_Pinv may be NULL as in gbdpcg_kkt_resolve_*, d_C when N == 1).  init and update are elementwise and refuse no shape; step
- * inherits every refusal of gbdpcg_kkt_resolve_* or its shared twin and refuses before anything is written. */
+ * inherits every refusal of gbdpcg_kkt_resolve_* or its shared twin and refuses before anything is written.  Every
+ * gbdpcg_graph_create_admm*_step_* (box, admm_lin and admm_soc alike) sets *out to NULL before its first refusal: a refused
+ * constructor never leaves a stale handle behind. */
 gbdpcg_status gbdpcg_admm_init_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_g,
                                    const float *d_lo, const float *d_hi, const float *d_rho, float *d_w, float *d_y, float *d_gt,
                                    void *stream);

@@ -24,6 +24,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import admm_ref  # noqa: E402
+from admm_util import bits, dev, np_same, same  # noqa: E402
 from gbd_pcg_amd import binding  # noqa: E402
 from oracle import schur_oracle as so  # noqa: E402
 
@@ -49,25 +50,8 @@ def solver():
     s.close()
 
 
-def dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()   # (a copy: the cached references are read-only)
-
-
 def tdt(dtype):
     return torch.float32 if np.dtype(dtype) == np.dtype(F32) else torch.float64
-
-
-def bits(t):
-    return t.contiguous().view(torch.uint8)
-
-
-def same(a, b):
-    return torch.equal(bits(a), bits(b))
-
-
-def np_same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def nz_of(nx, nu, N):

@@ -1,4 +1,4 @@
-"""ADMM with stage-wise linear inequality rows lo <= E z <= hi on a kept factorisation, on the device (csrc/admm_lin.hip and the
+"""ADMM with stage-wise linear inequality rows lo <= E z <= hi on a kept factorisation, on the device (csrc/admm_rows.hip and the
 composite calls of csrc/api.hip, through the C ABI): gbdpcg_admm_lin_form_*, _init_*, _update_*, _step_*, the shared twin and the two
 graphs.  PARITY UNPINNED: the reference tree has no code, fixture or output for these steps.
 
@@ -23,6 +23,7 @@ torch = pytest.importorskip("torch")
 
 import admm_lin_ref as ref  # noqa: E402
 import admm_ref  # noqa: E402
+from admm_util import bits, dev, host, knot_chunk, np_same, same  # noqa: E402
 from gbd_pcg_amd import binding  # noqa: E402
 from oracle import schur_oracle as so  # noqa: E402
 
@@ -36,12 +37,6 @@ PCG_TOL = {F32: 1e-10, F64: 1e-22}
 # reference (profiles/r11_admm_lin.txt): 2.781e-6 in fp32 (2.0e-6 / 2.2e-6 / 2.8e-6 per problem), 1.092e-12 in fp64 (1.1e-12 / 1.0e-12 /
 # 6.7e-13); times 4 for other boxes and PCG tolerances
 CLOSE = {F32: 1.12e-5, F64: 4.4e-12}
-
-
-def knot_chunk(nx, nu, mx, mu):
-    """The knots the update kernel stages at a time (admm_lin_knot_chunk in csrc/admm_lin.hip): what fits 4096 elements, 1 .. 64."""
-    per = mx * nx + mu * nu + nx + nu + 2 * (mx + mu)
-    return max(1, min(64, 4096 // per))
 
 
 NC = knot_chunk(14, 7, 4, 2)
@@ -62,27 +57,6 @@ def solver():
     s = binding.Solver(0)
     yield s
     s.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()   # (a copy: the cached references are read-only)
-
-
-def bits(t):
-    return t.contiguous().view(torch.uint8)
-
-
-def same(a, b):
-    return torch.equal(bits(a), bits(b))
-
-
-def np_same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def host(t, B):
-    return t.cpu().numpy().reshape(B, -1)
 
 
 INPUTS = ("G", "E", "g", "z", "w", "y", "lo", "hi", "rho")

@@ -1,4 +1,4 @@
-"""ADMM with stage-wise linear and second-order cone rows on a kept factorisation, on the device (csrc/admm_soc.hip and the composite
+"""ADMM with stage-wise linear and second-order cone rows on a kept factorisation, on the device (csrc/admm_rows.hip and the composite
 calls of csrc/api.hip, through the C ABI): gbdpcg_admm_soc_init_*, _update_*, _step_*, the shared twin and the two graphs.  PARITY
 UNPINNED: the reference tree has no code, fixture or output for these steps.
 
@@ -18,6 +18,7 @@ torch = pytest.importorskip("torch")
 
 import admm_lin_ref as lin  # noqa: E402
 import admm_soc_ref as ref  # noqa: E402
+from admm_util import bits, dev, host, knot_chunk, np_same, np_same_or_nan, same  # noqa: E402
 from gbd_pcg_amd import binding  # noqa: E402
 from oracle import schur_oracle as so  # noqa: E402
 
@@ -51,10 +52,6 @@ SHAPES = [(4, 3, 5, 3, 4, (0, 3, 1, 3)),        # x one cone q = 3; u one linear
           (5, 3, 9, 6, 4, (0, 3, 0, 4))]        # 86 rows, 69 entries: the 64-thread launch, two passes, a cone across them
 
 
-def knot_chunk(nx, nu, mx, mu):
-    return max(1, min(64, 4096 // (mx * nx + mu * nu + nx + nu + 2 * (mx + mu))))
-
-
 assert knot_chunk(14, 7, 5, 4) == 29 and 29 * 9 > 256 and (256 - 28 * 9) == 4      # row 256 is the last row of a q = 3 cone
 assert knot_chunk(5, 3, 6, 4) >= 9 and 64 - 6 * 10 == 4                           # row 64 is the middle row of a q = 3 cone
 
@@ -65,34 +62,6 @@ def solver():
     s = binding.Solver(0)
     yield s
     s.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()
-
-
-def bits(t):
-    return t.contiguous().view(torch.uint8)
-
-
-def same(a, b):
-    return torch.equal(bits(a), bits(b))
-
-
-def np_same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def np_same_or_nan(a, b):
-    """The same bits, except that a NaN need only meet a NaN: the sign and payload of a NaN that an operation makes (Inf - Inf) are
-    the platform's, and the host's differ from the device's."""
-    na, nb = np.isnan(a), np.isnan(b)
-    return np.array_equal(na, nb) and np_same(np.where(na, 0, a).astype(a.dtype), np.where(nb, 0, b).astype(b.dtype))
-
-
-def host(t, batch=B):
-    return t.cpu().numpy().reshape(batch, -1)
 
 
 def ids(shape):
@@ -183,7 +152,7 @@ def test_update_and_init_vs_reference(solver, shape, dtype, init):
     before = {k: b.clone() for k, b in t["_bufs"].items()}
     res = run_update(solver, shape, t, init)
     torch.cuda.synchronize()
-    w, y, gt = (host(t[k]) for k in ("w", "y", "gt"))
+    w, y, gt = (host(t[k], B) for k in ("w", "y", "gt"))
     clean = [b for b in range(B) if b not in (NAN_PROBLEM, INF_PROBLEM)]
     for name, got, want in (("w", w, wr), ("y", y, yr), ("gt", gt, gr)):
         assert np_same(got[clean], want[clean]), name
@@ -199,7 +168,7 @@ def test_update_and_init_vs_reference(solver, shape, dtype, init):
     for b in clean:
         assert np.isfinite(w[b]).all() and np.isfinite(gt[b]).all()
     if not init:
-        assert np_same_or_nan(host(res), rr) and np_same(host(res)[clean], rr[clean]), "res"
+        assert np_same_or_nan(host(res, B), rr) and np_same(host(res, B)[clean], rr[clean]), "res"
         assert np.isnan(rr[NAN_PROBLEM]).any() and np.isfinite(rr[clean]).all()
         assert not np.isfinite(w[INF_PROBLEM]).all()
 
@@ -246,7 +215,7 @@ def test_half_lines_give_the_bits_of_admm_lin_with_zero_and_infinity(solver, dty
     torch.cuda.synchronize()
     for k in ("w", "y", "gt", "res"):
         assert same(a[k], b[k]), k
-    w = host(b["w"])
+    w = host(b["w"], B)
     assert (w >= 0).all() and (w == 0).mean() > 0.2 and (w > 0).mean() > 0.2
 
 
