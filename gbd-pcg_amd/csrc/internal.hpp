@@ -227,12 +227,15 @@ hipError_t launch_form_pinv(const DeviceInfo &dev, uint32_t n, uint32_t N, uint3
 // (s_symmetric: the caller KNOWS L_{k+1} == R_k^T in S bit for bit -- the one-launch stair kernel then never reads L)
 template <typename T> uint32_t pinv_verdict_chunks(uint32_t n, uint32_t N, int kind);
 
-// ---- schur.hip: KKT blocks -> S, gamma, G^-1;  lambda -> primal step.  Layouts in include/gbdpcg.h.
+// ---- schur.hip: KKT blocks -> S, gamma, G^-1.  Layouts in include/gbdpcg.h.
 // rho (device, [batch]; gbdpcg_form_schur_reg_*): problem b is formed from G_b + rho_b I -- the REG instantiations of the same
 // kernels; nullptr: the kernels without the switch.
 template <typename T>
 hipError_t launch_form_schur(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *G, const T *C,
                              const T *g, const T *c, T *S, T *gamma, T *Ginv, hipStream_t s, const T *rho = nullptr);
+template <typename T> bool schur_shape_ok(const DeviceInfo &dev, uint32_t nx, uint32_t nu);
+
+// ---- schur_ginv.hip : the two steps that apply the stored G^-1.  lambda -> primal step z = -G^-1 (g + C' lambda)
 template <typename T>
 hipError_t launch_recover_primal(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *Ginv,
                                  const T *C, const T *g, const T *lambda, T *z, hipStream_t s, bool shared = false);
@@ -240,14 +243,16 @@ hipError_t launch_recover_primal(const DeviceInfo &dev, uint32_t nx, uint32_t nu
 template <typename T>
 hipError_t launch_form_gamma(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *Ginv, const T *C,
                              const T *g, const T *c, T *gamma, hipStream_t s, bool shared = false);
+// (shared, the two launchers: Ginv and C are one problem's blocks, used by every problem of the batch)
+
+// ---- schur_residual.hip
 // res[2b] = ||G z + g + C' lambda||_inf, res[2b+1] = ||C z - c||_inf of problem b (G: the Hessians, not their inverses)
 // rho (gbdpcg_kkt_residual_reg_*, not with shared): the stationarity of G_b + rho_b I
 template <typename T>
 hipError_t launch_kkt_residual(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *G, const T *C,
                                const T *g, const T *c, const T *z, const T *lambda, T *res, hipStream_t s, bool shared = false,
                                const T *rho = nullptr);
-// (shared, the three launchers: Ginv / G and C are one problem's blocks, used by every problem of the batch)
-template <typename T> bool schur_shape_ok(const DeviceInfo &dev, uint32_t nx, uint32_t nu);
+// (shared: G and C are one problem's blocks, used by every problem of the batch)
 
 // ---- admm.hip : the splitting update of box-constrained ADMM on a kept factorisation, one launch, one workgroup per problem.
 // Every array has the layout of g ((nx + nu) N - nu elements per problem), rho [batch], res [2 batch]:

@@ -1,4 +1,4 @@
-// norm_fold.hpp -- the NaN-propagating maximum of magnitudes that the per-problem norms are taken with (schur.hip: the KKT
+// norm_fold.hpp -- the NaN-propagating maximum of magnitudes that the per-problem norms are taken with (schur_residual.hip: the KKT
 // residual kernels; admm.hip: the splitting update).  The maximum runs over the BIT PATTERN of |entry| as an unsigned integer:
 // that orders the non-negative numbers as they are ordered, puts Inf above them and every NaN above Inf, and is exact in any fold
 // order.  Every lane keeps its running maxima in registers, a wave folds them through DPP, the workgroup through one LDS slot per

@@ -19,15 +19,10 @@
 // data, once per control step; not the bandwidth-bound hot loop, but on the MPC critical path.
 #include "bt_device.hpp"
 #include "internal.hpp"
+#include "row16.hpp"
 
 #ifndef GBDPCG_PINV_SKIP
 #define GBDPCG_PINV_SKIP 0     // timing builds of pinv_stair_mfma_kernel (WRONG results): 1 no elimination, 2 no products, 4 no stores
-#endif
-#ifndef GBDPCG_PINV_PACKED
-#define GBDPCG_PINV_PACKED 1   // 0: one row per instruction in the DPP elimination (A/B runs)
-#endif
-#ifndef GBDPCG_PINV_DPP
-#define GBDPCG_PINV_DPP 1   // 0: pivot columns of the one-launch stair kernel broadcast through LDS (A/B runs)
 #endif
 
 namespace gbdpcg {
@@ -283,55 +278,12 @@ __global__ __launch_bounds__(kPinvThreads) void pinv_diag_pair_kernel(uint32_t N
     }
 }
 
-// The value lane J of every 16-lane row holds, in all lanes of that row (DPP row_newbcast: a VALU move, no LDS round trip), and the
-// in-place Gauss-Jordan elimination of an M x M block held one column per lane on top of it -- the arithmetic of
-// pinv_diag_quad_kernel, element for element (the broadcast values are the same numbers that kernel passes through LDS).
-#if GBDPCG_PINV_DPP
-template <int J> __device__ __forceinline__ float stair_bcast(float v)
+// The in-place Gauss-Jordan elimination of an n x n block held one column per lane of a 16-lane row (row16.hpp), as the kernels
+// below take it: the pivot's reciprocal is the division, and an odd n in fp32 takes the one-row-per-instruction loop.
+template <int M, typename T> __device__ __forceinline__ void stair_invert(T (&col)[M], uint32_t l)
 {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x150 + J, 0xf, 0xf, true));
+    row_eliminate<0, M, RcpDivide, false>(col, l);
 }
-template <int J> __device__ __forceinline__ double stair_bcast(double v)
-{
-    const long long b = __builtin_bit_cast(long long, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), 0x150 + J, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x150 + J, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
-template <int J, int M, typename T> __device__ __forceinline__ void stair_eliminate(T (&col)[M], uint32_t l)
-{
-    if constexpr (J < M) {
-        T cj[M];
-#pragma unroll
-        for (int r = 0; r < M; ++r) cj[r] = stair_bcast<J>(col[r]);
-        const T piv = T(1) / cj[J];
-        const bool is_j = l == (uint32_t)J;
-        const T pr = is_j ? piv : col[J] * piv;
-#if GBDPCG_PINV_PACKED
-        if constexpr (sizeof(T) == 4 && M % 2 == 0) {
-            // two rows per instruction (schur.hip, quad_pivot): the pivot lane's "start from zero" is an exact packed multiply by
-            // 0 or 1 instead of a select per row, the update a packed fma -- the same fma on the same numbers, element for element
-            typedef float f2 __attribute__((ext_vector_type(2)));
-            const float keep = is_j ? 0.0f : 1.0f;
-            const f2 kk = {keep, keep}, npr = {-pr, -pr};
-#pragma unroll
-            for (int r = 0; r + 1 < M; r += 2) {
-                const f2 c = {col[r], col[r + 1]}, b = {cj[r], cj[r + 1]};
-                const f2 v = __builtin_elementwise_fma(b, npr, c * kk);
-                col[r] = v.x;
-                col[r + 1] = v.y;
-            }
-            col[J] = pr;
-        } else
-#endif
-        {
-#pragma unroll
-            for (int r = 0; r < M; ++r) col[r] = (r == J) ? pr : fma_t(-cj[r], pr, is_j ? T(0) : col[r]);
-        }
-        stair_eliminate<J + 1, M>(col, l);
-    }
-}
-#endif
 
 // n <= 16: FOUR knots per wavefront, one per 16-lane quarter, with the IN-PLACE form of the same
 // elimination: lane c < n of a quarter owns column c of the n x n block only.  The identity half of the
@@ -344,15 +296,13 @@ template <typename T, int NCT>
 __global__ __launch_bounds__(kPinvThreads) void pinv_diag_quad_kernel(uint32_t N, uint64_t knots, const T *__restrict__ S,
                                                                      T *__restrict__ Pinv, int kind)
 {
-    constexpr uint32_t n = NCT, nn = n * n, NP = (n + 3) / 4 * 4;
+    constexpr uint32_t n = NCT, nn = n * n;
     static_assert(n <= 16, "four knots per wave need n lanes per quarter");
     __shared__ __attribute__((aligned(16))) T stage_all[4][4][nn];  // D_k^-1 of each quarter's knot, for the mirrored write-out
-    __shared__ __attribute__((aligned(16))) T bcast_all[4][4][NP];  // the pivot column of the current step
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, quarter = lane >> 4, l = lane & 15u;
     const uint64_t knot = ((uint64_t)blockIdx.x * 4 + wave) * 4 + quarter;
     const bool alive = knot < knots;
     T *stage = stage_all[wave][quarter];
-    T *bc = bcast_all[wave][quarter];
     const size_t blk = (size_t)(alive ? knot : 0) * 3 * nn;
     const T *D = S + blk + nn;
     const bool owner = l < n;
@@ -360,31 +310,7 @@ __global__ __launch_bounds__(kPinvThreads) void pinv_diag_quad_kernel(uint32_t N
     T col[n];
 #pragma unroll
     for (uint32_t r = 0; r < n; ++r) col[r] = (kind == 0 || !alive || !owner) ? (r == l ? T(1) : T(0)) : D[l * n + r];
-#if GBDPCG_PINV_DPP
-    (void)bc;
-    if (kind != 0) stair_eliminate<0, (int)n>(col, l);
-    if (false) {
-#else
-    if (kind != 0) {
-#endif
-#pragma unroll
-        for (uint32_t j = 0; j < n; ++j) {
-            if (l == j) {
-#pragma unroll
-                for (uint32_t r = 0; r < n; ++r) bc[r] = col[r];
-            }
-            group_sync<64>();
-            T cj[n];
-#pragma unroll
-            for (uint32_t r = 0; r < n; ++r) cj[r] = bc[r];
-            group_sync<64>();  // everyone has the column before step j+1 overwrites it
-            const T piv = T(1) / cj[j];
-            const bool is_j = l == j;
-            const T pr = is_j ? piv : col[j] * piv;  // scaled pivot-row entry of this lane's column
-#pragma unroll
-            for (uint32_t r = 0; r < n; ++r) col[r] = (r == j) ? pr : fma_t(-cj[r], pr, is_j ? T(0) : col[r]);
-        }
-    }
+    if (kind != 0) stair_invert<(int)n>(col, l);   // (the pivot column reaches the quarter as a DPP row broadcast)
     if (owner) {
 #pragma unroll
         for (uint32_t r = 0; r < n; ++r) stage[l * n + r] = col[r];
@@ -618,11 +544,10 @@ __global__ __launch_bounds__(kPinvThreads) void pinv_stair_fused_kernel(uint32_t
                                                                        T *__restrict__ Pinv, uint8_t *__restrict__ verdicts)
 {
     constexpr bool s_symmetric = S_SYM;
-    constexpr uint32_t n = NCT, nn = n * n, NP = (n + 3) / 4 * 4, H = n / 2, PAIRS = 15;
+    constexpr uint32_t n = NCT, nn = n * n, H = n / 2, PAIRS = 15;
     static_assert(n <= 16 && n % 2 == 0, "quarter-wave elimination and 2 x 2 tiles");
     using P2 = typename VecOf<T, 2>::type;
     __shared__ __attribute__((aligned(16))) T inv[16][nn];      // mirrored D^-1 of knots k0 .. k0+15
-    __shared__ __attribute__((aligned(16))) T bcast_all[16][NP];
     __shared__ __attribute__((aligned(16))) T work[4][2][nn];   // per wave: B (R_k or L_{k+1}^T) and W^T
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, quarter = lane >> 4, l = lane & 15u;
     const uint32_t prob = blockIdx.x / chunks, chunk = blockIdx.x - prob * chunks;
@@ -633,32 +558,10 @@ __global__ __launch_bounds__(kPinvThreads) void pinv_stair_fused_kernel(uint32_t
         const uint32_t slot = wave * 4 + quarter, k = k0 + slot;
         const bool alive = k < N, owner = l < n;
         const T *D = S + pbase + (size_t)(alive ? k : 0) * 3 * nn + nn;
-        T *bc = bcast_all[slot];
         T col[n];
 #pragma unroll
         for (uint32_t r = 0; r < n; ++r) col[r] = (!alive || !owner) ? (r == l ? T(1) : T(0)) : D[l * n + r];
-#if GBDPCG_PINV_DPP
-        (void)bc;
-        stair_eliminate<0, (int)n>(col, l);
-#else
-#pragma unroll
-        for (uint32_t j = 0; j < n; ++j) {
-            if (l == j) {
-#pragma unroll
-                for (uint32_t r = 0; r < n; ++r) bc[r] = col[r];
-            }
-            group_sync<64>();
-            T cj[n];
-#pragma unroll
-            for (uint32_t r = 0; r < n; ++r) cj[r] = bc[r];
-            group_sync<64>();
-            const T piv = T(1) / cj[j];
-            const bool is_j = l == j;
-            const T pr = is_j ? piv : col[j] * piv;
-#pragma unroll
-            for (uint32_t r = 0; r < n; ++r) col[r] = (r == j) ? pr : fma_t(-cj[r], pr, is_j ? T(0) : col[r]);
-        }
-#endif
+        stair_invert<(int)n>(col, l);
         if (owner) {  // mirrored on the way into LDS: element (r, c) with r > c takes the value of (c, r)
 #pragma unroll
             for (uint32_t r = 0; r < n; ++r)
@@ -860,7 +763,7 @@ __global__ __launch_bounds__(kPinvThreads) void pinv_stair_mfma_kernel(uint32_t 
 #pragma unroll
         for (uint32_t r = 0; r < n; ++r) col[r] = (!alive || !owner) ? (r == l ? 1.f : 0.f) : D[l * n + r];
 #if !(GBDPCG_PINV_SKIP & 1)
-        stair_eliminate<0, (int)n>(col, l);
+        stair_invert<(int)n>(col, l);
 #endif
         if (owner) {  // mirrored on the way into LDS: element (r, c) with r > c takes the value of (c, r)
 #pragma unroll

@@ -66,7 +66,7 @@ def main():
     subprocess.check_call([sys.executable, os.path.join(ROOT, "gbd-pcg_amd", "tools", "pmc_traffic.py"),
                            os.path.join(src, "fetch"), os.path.join(src, "write"), os.path.join(src, "cal"),
                            os.path.join(dst, f"{rnd}_pmc_traffic.json")], stdout=subprocess.DEVNULL)
-    # the steps either side of the solve (schur.hip): stage times + kernel stats + traffic of tools/schur_run.py
+    # the steps either side of the solve (schur.hip, schur_ginv.hip): stage times + kernel stats + traffic of tools/schur_run.py
     st = os.path.join(src, "schur.txt")
     if os.path.exists(st):
         nx, nu, N, B = 14, 7, 128, 1024

@@ -47,7 +47,7 @@ echo "[10] the cluster kernel (general storage): time per iteration and fixed co
     GBDPCG_LIB=$ROOT/gbd-pcg_amd/csrc/variants/libgbdpcg_clstamps.so python3 $ROOT/gbd-pcg_amd/tools/cluster_stamps.py 128 1024 | tail -8
   fi
 } > $OUT/cluster.txt 2>/dev/null || true
-echo "[11] the steps either side of the solve (schur.hip): stage times, kernel stats, traffic, phase stamps"
+echo "[11] the steps either side of the solve (schur.hip, schur_ginv.hip): stage times, kernel stats, traffic, phase stamps"
 {
   python3 $ROOT/gbd-pcg_amd/tools/schur_run.py --reps 40
   python3 $ROOT/gbd-pcg_amd/tools/schur_run.py --reps 40 --N 50 --batch 2048

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the two steps either side of the solve (csrc/schur.hip) next to Pinv formation and the solve itself, on
+"""Times the two steps either side of the solve (csrc/schur.hip, csrc/schur_ginv.hip) next to Pinv formation and the solve itself, on
 synthetic KKT blocks of the BASELINE batch shape:   python gbd-pcg_amd/tools/schur_run.py [--nx 14 --nu 7 --N 128 --batch 1024]
 Algorithmic bytes = every input once + every output once (form: G, C, g, c -> S, gamma, G^-1; recover: G^-1, C, g, lambda -> z).
 Inputs are drawn on the device (SPD cost blocks M M' + I, dynamics I + noise); event-timed, median of --reps."""
@@ -78,10 +78,10 @@ def main():
         s.form_schur(nx, nu, N, B, G, C, g, c, S=S, gamma=gam2, Ginv=Ginv)
         torch.cuda.synchronize()
         st = gam2[-24:].view(torch.int64).cpu().tolist()[:10]
-        # fp32 (one input buffer): the requests for the next step go out at the END of a step, behind its stores, and the S rows are
-        # stored there too; fp64 (two buffers): requests at the top, S rows of the previous step stored during the elimination
-        names = ["wait for the requests", "(fp64: issue next requests)", "fix-ups + columns into registers", "elimination (fp64: + previous S stores)",
-                 "carry", "G^-1 in place, A / B from LDS, W, V products", "T product", "D, gamma", "G^-1 stores (fp32: + S, gamma stores, next requests)"]
+        # one input buffer: the requests for the next step go out at the END of a step, behind its stores, and the S rows are stored
+        # there too
+        names = ["wait for the requests", "(nothing: the requests go out at the end of a step)", "fix-ups + columns into registers", "elimination",
+                 "carry", "G^-1 in place, A / B from LDS, W, V products", "T product", "D, gamma", "G^-1, S, gamma stores, next requests"]
         out["stamps_shader_cycles"] = {names[i]: st[i + 1] - st[i] for i in range(9)}
         out["stamps_step_total"] = st[9] - st[0]
     print(json.dumps(out))

@@ -1,4 +1,4 @@
-"""KKT residual norms on the device (csrc/schur.hip schur_residual_kernel / schur_residual_quad_kernel, through the C ABI):
+"""KKT residual norms on the device (csrc/schur_residual.hip schur_residual_kernel / schur_residual_quad_kernel, through the C ABI):
 res[b] = (||G z + g + C' lambda||_inf, ||C z - c||_inf) per problem.  PARITY UNPINNED: the reference tree has no code, fixture or
 output for this step.
 
@@ -30,7 +30,7 @@ F32, F64 = np.float32, np.float64
 SHAPES = [(14, 7, 128, 3), (14, 7, 1, 2), (14, 7, 2, 1), (2, 1, 5, 4), (3, 3, 2, 1), (5, 2, 9, 2), (12, 4, 33, 2), (4, 6, 3, 2),
           (36, 18, 6, 1), (1, 1, 4, 1), (44, 3, 3, 1)]   # SHAPES of tests/test_gpu_resolve.py
 QUAD_SHAPES = [(2, 1), (4, 1), (4, 2), (6, 3), (8, 4), (10, 5), (12, 4), (12, 6), (13, 4), (3, 1), (5, 2), (6, 1), (6, 2), (7, 3), (8, 2), (9, 3),
-               (10, 4), (11, 4), (12, 3), (14, 7)]   # GBDPCG_QUAD_SHAPES of csrc/schur.hip
+               (10, 4), (11, 4), (12, 3), (14, 7)]   # GBDPCG_QUAD_SHAPES of csrc/schur_common.hpp
 QUAD_NB = [(1, 2), (2, 3), (3, 1), (5, 3), (7, 11), (16, 5)]   # rows, waves and workgroups partly empty, problems that straddle waves
 POINTS = ("solution", "solution + 1e-3 noise", "random")
 

@@ -1,4 +1,4 @@
-"""Per-problem regularisation on the device (the REG instantiations of csrc/schur.hip, through the C ABI): problem b is formed,
+"""Per-problem regularisation on the device (the REG instantiations of csrc/schur.hip and csrc/schur_residual.hip, through the C ABI): problem b is formed,
 solved and judged with G_b + rho_b I in place of G_b -- gbdpcg_form_schur_reg_*, gbdpcg_kkt_step_reg_* and its graph,
 gbdpcg_kkt_residual_reg_*.  PARITY UNPINNED: the reference tree has no code, fixture or output for these steps.
 

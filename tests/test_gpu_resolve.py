@@ -1,4 +1,4 @@
-"""The frozen-linearisation step on the device (csrc/schur.hip schur_gamma_kernel / schur_gamma_quad_kernel, through the C ABI):
+"""The frozen-linearisation step on the device (csrc/schur_ginv.hip schur_gamma_kernel / schur_gamma_quad_kernel, through the C ABI):
 G and C are kept, g and c are new, so S, Phi^-1 and G^-1 stand and only gamma = -(c + C G^-1 g) is formed before the solve.
 gamma against oracle/schur_oracle.py::form_schur (fp64 block formulas), the whole step against a dense fp64 solve of the KKT
 system.  PARITY UNPINNED: the reference tree has no code, fixture or output for these steps.  Tolerances are those
@@ -42,7 +42,7 @@ def relerr(a, b):
 SHAPES = [(14, 7, 128, 3), (14, 7, 1, 2), (14, 7, 2, 1), (2, 1, 5, 4), (3, 3, 2, 1), (5, 2, 9, 2), (12, 4, 33, 2), (4, 6, 3, 2),
           (36, 18, 6, 1), (1, 1, 4, 1), (44, 3, 3, 1)]   # tests/test_gpu_schur.py
 QUAD_SHAPES = [(2, 1), (4, 1), (4, 2), (6, 3), (8, 4), (10, 5), (12, 4), (12, 6), (13, 4), (3, 1), (5, 2), (6, 1), (6, 2), (7, 3), (8, 2), (9, 3),
-               (10, 4), (11, 4), (12, 3), (14, 7)]   # GBDPCG_QUAD_SHAPES of csrc/schur.hip
+               (10, 4), (11, 4), (12, 3), (14, 7)]   # GBDPCG_QUAD_SHAPES of csrc/schur_common.hpp
 # rows = N * B of 2, 6, 3, 15, 77 and 80: quarters, waves and workgroups (16 rows) partly empty, problems that straddle waves
 QUAD_NB = [(1, 2), (2, 3), (3, 1), (5, 3), (7, 11), (16, 5)]
 GAMMA_CASES = SHAPES + [(nx, nu, N, B) for nx, nu in QUAD_SHAPES for N, B in QUAD_NB] + [(36, 12, 7, 3)]

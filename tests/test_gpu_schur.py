@@ -1,4 +1,4 @@
-"""SURVEY 8f-4 on the device (csrc/schur.hip, through the C ABI): KKT blocks -> S, gamma, G^-1 and lambda -> primal step,
+"""SURVEY 8f-4 on the device (csrc/schur.hip and csrc/schur_ginv.hip, through the C ABI): KKT blocks -> S, gamma, G^-1 and lambda -> primal step,
 against oracle/schur_oracle.py (fp64 block formulas, themselves pinned to a dense KKT solve in test_oracle_schur.py).
 PARITY UNPINNED: the reference tree has no code, fixture or output for these steps.  Tolerances: the device inverts the
 cost blocks by Gauss-Jordan in working precision, so entries agree with the fp64 formulas to cond(Q) * eps -- 2e-4 of the
@@ -103,7 +103,7 @@ def test_four_knot_form_runs_of_every_length(solver, N, B):
 
 
 QUAD_SHAPES = [(2, 1), (4, 1), (4, 2), (6, 3), (8, 4), (10, 5), (12, 4), (12, 6), (13, 4), (3, 1), (5, 2), (6, 1), (6, 2), (7, 3), (8, 2), (9, 3),
-               (10, 4), (11, 4), (12, 3), (14, 7)]   # GBDPCG_QUAD_SHAPES of csrc/schur.hip (14 / 7 last: it has tests of its own)
+               (10, 4), (11, 4), (12, 3), (14, 7)]   # GBDPCG_QUAD_SHAPES of csrc/schur_common.hpp (14 / 7 last: it has tests of its own)
 
 
 @pytest.mark.parametrize("nx,nu", QUAD_SHAPES[:-1])
