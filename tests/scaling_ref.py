@@ -154,7 +154,7 @@ RUNS = [("tol", 1e-6, 200), ("fixed", 0.0, 6)]            # the two runs of ever
 # (family, n, N, dtype, symmetric mode, B, distinct base problems, warm start); the GPU half forces the dispatch and asserts what
 # the C ABI lets it see of it (path, workgroups per cluster, batch against the number of compute units).
 # "sym": B = 132 = 44 x 3 copies, more than one round of two-workgroup clusters on 256 compute units: below that, mode 2 hands
-# the batch to the cluster kernel in general storage (csrc/api.hip, one_cluster_round) and never runs the verifying kernel.
+# the batch to the cluster kernel in general storage (csrc/api_solve.hip, one_cluster_round) and never runs the verifying kernel.
 # "symstream": symmetric streaming exists for even n in 8 ... 16 beyond the horizons of the resident and cluster kernels and for
 # batches of at least one problem per compute unit: fp64 12 x 161 (resident up to 40 knots, clusters up to 160).  In fp32 the
 # cluster kernel holds n = 12 up to 640 knots (n = 16: 512, n = 8: 1024), so the smallest fp32 case is 256 x (12, 641): 284 MB

@@ -1,4 +1,4 @@
-"""Box-constrained ADMM on a kept factorisation, on the device (csrc/admm.hip and the composite calls of csrc/api.hip, through the C
+"""Box-constrained ADMM on a kept factorisation, on the device (csrc/admm.hip and the composite calls of csrc/api_kkt.hip, through the C
 ABI): gbdpcg_admm_init_*, gbdpcg_admm_update_*, gbdpcg_admm_step_*, the shared twin and the two graphs.  PARITY UNPINNED: the
 reference tree has no code, fixture or output for these steps.
 

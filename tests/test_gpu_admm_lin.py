@@ -1,5 +1,5 @@
 """ADMM with stage-wise linear inequality rows lo <= E z <= hi on a kept factorisation, on the device (csrc/admm_rows.hip and the
-composite calls of csrc/api.hip, through the C ABI): gbdpcg_admm_lin_form_*, _init_*, _update_*, _step_*, the shared twin and the two
+composite calls of csrc/api_kkt.hip, through the C ABI): gbdpcg_admm_lin_form_*, _init_*, _update_*, _step_*, the shared twin and the two
 graphs.  PARITY UNPINNED: the reference tree has no code, fixture or output for these steps.
 
 Reference: tests/admm_lin_ref.py.  Formation, initialisation and update are defined to the bit (every line one IEEE operation, the

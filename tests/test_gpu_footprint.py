@@ -138,7 +138,7 @@ def cus():
 
 
 def slices(solver, c):
-    """Problems per persistent launch when AUTO cuts a batch into several (api.hip, persist_slices); 0: it does not."""
+    """Problems per persistent launch when AUTO cuts a batch into several (api_solve.hip, persist_slices); 0: it does not."""
     if c.path != AUTO or solver.choose_path(c.es, c.n, c.N, c.B) != SPLIT:
         return 0
     cap = 0

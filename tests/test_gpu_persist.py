@@ -224,7 +224,7 @@ def test_persistent_other_state_sizes(solver, orc, path, n, dtype, N, B):
                                                   (24, np.float32, 128, 11, 60), (20, np.float64, 200, 5, 100), (32, np.float32, 100, 9, 200),
                                                   (24, np.float32, 128, 8, 12)])
 def test_small_batches_of_large_problems_go_persistent_in_slices(solver, orc, n, dtype, N, B, max_iter):
-    """A few problems more than one persistent launch holds: AUTO cuts the batch into persistent launches in a row (api.hip,
+    """A few problems more than one persistent launch holds: AUTO cuts the batch into persistent launches in a row (api_solve.hip,
     persist_slices) instead of the split path's 2 max_iter + 4 launches -- unless max_iter is so small that the split graph is the
     shorter one (last case).  Every problem against the oracle, warm start, r and p included; then the same as a hipGraph."""
     es = np.dtype(dtype).itemsize

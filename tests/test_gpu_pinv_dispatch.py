@@ -230,7 +230,7 @@ def relerr(a, b):
 @pytest.mark.parametrize("dtype,n", [(F32, 2), (F32, 4), (F32, 8), (F32, 10), (F32, 16), (F64, 8), (F64, 14), (F64, 16)])
 def test_form_pinv_solve_with_some_asymmetric_problems(solver, dtype, n):
     """tests/test_gpu_robustness.py::test_form_pinv_solve_with_some_asymmetric_problems at the other block sizes, N = 20.  The stair
-    kernel reports verdicts only where the solve would pick a symmetric kernel (api.hip: FUSED path, fused_has_symmetric): at N = 20
+    kernel reports verdicts only where the solve would pick a symmetric kernel (api_solve.hip: FUSED path, fused_has_symmetric): at N = 20
     that needs a block size the register-resident kernel does not take (16; 14 in fp64) and a batch of at least the device's 256
     compute units, so those sizes run 258 problems; the solve then takes them as clusters of one and ignores the bytes, so no size of
     this list has the two-kernel dispatch, and the others run 6 problems."""

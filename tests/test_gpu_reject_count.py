@@ -13,7 +13,7 @@ replay on), for N = 2 (one pair of block-rows), 5 (an odd count, one dead slot) 
   * the cluster path's hand-off state: a launch that leaves early takes no launch number, and a mode-0 cluster solve right
     after it on the same handle matches the oracle.
 
-Which launches a case reaches follows from the shape alone (api.hip): the verifying launch exists where the general kernel is
+Which launches a case reaches follows from the shape alone (api_solve.hip): the verifying launch exists where the general kernel is
 the cluster kernel (N > 72 at this block size) and the batch is more than one round of clusters (2 CUs per problem at N = 128).
 The other cases (N = 2, 5; three problems at N = 128) are solved by one general launch in mode 2: no verdict byte is written for
 them, which is asserted as such, and everything else is checked all the same.

@@ -214,24 +214,50 @@ def test_solve_inside_a_caller_owned_capture(solver, orc):
         assert np.linalg.norm(lam_h[b] - ob["lambda_"][b]) / np.linalg.norm(ob["lambda_"][b]) < 1e-6
 
 
-def test_sliced_persistent_solve_inside_a_caller_owned_capture(orc):
-    """The same for a small batch of large problems, which AUTO cuts into persistent launches in a row (api.hip, persist_slices):
+@pytest.mark.parametrize("B", [8, 11])
+def test_sliced_persistent_solve_inside_a_caller_owned_capture(orc, B):
+    """The same for a small batch of large problems, which AUTO cuts into persistent launches in a row (api_solve.hip, persist_slices;
+    the shape is that of the graph case of tests/test_gpu_persist.py, 11 problems leave a last slice that is shorter than the
+    others): a capture on a handle that has seen nothing is refused, there is nowhere to take the hand-off words from;
     gbdpcg_reserve prepares the hand-off words of the slices (and the split path's workspace -- which of the two a solve takes
-    depends on its max_iter), so both captures below are legal; a fresh handle, so that nothing is there by accident."""
-    n, N, B = 24, 100, 7
-    s = binding.Solver(0)
+    depends on its max_iter), so both captures behind it are legal.  Fresh handles, so that nothing is there by accident."""
+    n, N = 24, 128
+    d = synth.gen_numpy(n, N, seed=405, batch=B, dtype=np.float32)
+    S, P, g = dev(d["S"]), dev(d["Pinv"]), dev(d["gamma"])
+    iters = torch.zeros(B, dtype=torch.int32, device="cuda")
+    flags = torch.zeros(B, dtype=torch.uint8, device="cuda")
+
+    def captured_solve(s, lam, max_iter):
+        """The solve inside a capture of the caller's: (the graph, the status of the call)."""
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            iters.zero_()   # (a node of the caller's own: the graph is not empty where the solve is refused)
+            _, args = s.solve_args(n, N, B, S, P, g, lam, None, None, 1e-6, max_iter, iters, flags)
+            st = s.lib.gbdpcg_solve_f32(*args, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        return graph, st
+
+    # which launches a case reaches: the rule of persist_slices, as slices() of tests/test_gpu_footprint.py restates it
+    probe = binding.Solver(0)
     try:
-        d = synth.gen_numpy(n, N, seed=405, batch=B, dtype=np.float32)
-        S, P, g = dev(d["S"]), dev(d["Pinv"]), dev(d["gamma"])
-        iters = torch.zeros(B, dtype=torch.int32, device="cuda")
-        flags = torch.zeros(B, dtype=torch.uint8, device="cuda")
-        s.reserve(4, n, N, B)
-        torch.cuda.synchronize()
-        for max_iter in (60, 8):   # 60: persistent launches in a row; 8: the split graph is the shorter one
+        assert probe.choose_path(4, n, N, B) == binding.PATH_SPLIT
+        per = max(b for b in range(1, B) if probe.choose_path(4, n, N, b) == binding.PATH_PERSISTENT)
+    finally:
+        probe.close()
+    launches = -(-B // per)
+    sliced = {mi: launches <= 16 and 25.0 * launches < 1.8 * (2.0 * mi + 4.0) for mi in (60, 8)}
+    assert sliced == {60: True, 8: False} and (B == 8 or B % per != 0), (per, launches)
+    for max_iter in (60, 8):   # 60: persistent launches in a row; 8: the split graph is the shorter one
+        s = binding.Solver(0)
+        try:
+            assert s.choose_path(4, n, N, B) == binding.PATH_SPLIT
             lam = torch.zeros_like(g)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                s.solve(n, N, B, S, P, g, lam, tol=1e-6, max_iter=max_iter, iters=iters, max_iter_exit=flags)
+            graph, st = captured_solve(s, lam, max_iter)
+            assert st == 6, (max_iter, st)   # GBDPCG_ERR_ALLOC
+            del graph
+            s.reserve(4, n, N, B)
+            torch.cuda.synchronize()
+            graph, st = captured_solve(s, lam, max_iter)
+            assert st == binding.OK, (max_iter, st)
             for _ in range(2):
                 lam.zero_()
                 graph.replay()
@@ -243,8 +269,8 @@ def test_sliced_persistent_solve_inside_a_caller_owned_capture(orc):
             for b in range(B):
                 assert np.linalg.norm(lam_h[b] - ob["lambda_"][b]) / np.linalg.norm(ob["lambda_"][b]) < 2e-6, (max_iter, b)
             del graph
-    finally:
-        s.close()
+        finally:
+            s.close()
 
 
 @pytest.mark.parametrize("shape", [(14, 40, 3, 400, np.float32), (36, 256, 1, 4, np.float64)])
@@ -324,7 +350,7 @@ def test_form_pinv_solve_with_some_asymmetric_problems(solver, orc):
     both sides); the others by the resident symmetric one; all must match the oracle run on the same S and Pinv."""
     n, N, base = 14, 100, 6
     # 132 problems: more than one round of two-workgroup clusters holds (128), so that mode 2 does run its two-kernel
-    # dispatch (smaller batches go to the cluster kernel as a whole: api.hip, one_cluster_round)
+    # dispatch (smaller batches go to the cluster kernel as a whole: api_solve.hip, one_cluster_round)
     B = 132
     d0 = synth.gen_numpy(n, N, seed=31337, batch=base, dtype=np.float32)
     idx = np.arange(B) % base

@@ -68,7 +68,7 @@ class Case:
 
 
 # reach: the families the case must reach over the batches below (a batch that one round of clusters holds goes to the cluster
-# kernel in mode 2, api.hip one_cluster_round)
+# kernel in mode 2, api_solve.hip one_cluster_round)
 CASES = [
     Case("14x128-m2", {"resident_sym", "cluster"}, 14, 128, F32, mode=2),
     Case("14x128-m1", {"resident_sym"}, 14, 128, F32, mode=1),
@@ -101,7 +101,7 @@ def resident_horizon(solver, es, n):
 
 
 def family(solver, c, B):
-    """The kernel family solve_impl's fused branch reaches for this case and batch (csrc/api.hip, csrc/pcg_fused.hip)."""
+    """The kernel family the fused branch of solve reaches for this case and batch (csrc/api_solve.hip, csrc/pcg_fused.hip)."""
     assert solver.choose_path(c.es, c.n, c.N, B) == binding.PATH_FUSED
     members = solver.cluster_members(c.es, c.n, c.N)
     al8 = c.shift % 8 == 0
