@@ -31,6 +31,13 @@ namespace gbdpcg {
 
 constexpr uint32_t kWave = 64;
 
+// LDS operations of one wave execute in program order: the synchronisation inside a wave is a compiler fence.
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
 // One correctly-rounded fused multiply-add in T's own precision.  (__builtin_fma is the DOUBLE
 // builtin: given floats it converts, does an fp64 FMA and rounds back -- slow and not fp32 math.)
 __device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }

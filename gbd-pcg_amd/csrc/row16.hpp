@@ -1,6 +1,6 @@
 // row16.hpp -- what the kernels that put one small block (or one knot) into each 16-lane row of a wavefront share: the DPP row
 // broadcast, the products that ride on it, and one pivot step of the in-place Gauss-Jordan elimination of a block held one
-// column per lane.  Used by schur.hip, schur_ginv.hip, schur_residual.hip (the four-knots-per-wave kernels) and pinv.hip (the
+// column per lane.  Used by schur.hip, schur_ginv.hip, schur_residual.hip (the four-knots-per-wave kernels) and pinv_regs.hip / pinv_fused.hip (the
 // quarter-wave and one-launch stair kernels).  Everything here is forced inline: no symbols, the same code in every unit.
 #pragma once
 #include <cstdint>

@@ -30,7 +30,7 @@
 // are then the same fma chains over the same numbers, so S comes out EXACTLY symmetric in storage (L_{k+1} == R_k'
 // bit for bit) and the solve takes its symmetric-storage kernels (gbdpcg_set_symmetric, mode 2 test passes).
 // LDS operations of one wave execute in program order, so the synchronisation inside a wave is a compiler fence
-// (group_sync<64> of pinv.hip restated).  A row's working set is 7 nx^2 + 3 nu^2 + ... elements of LDS (7.5 KB at
+// (wave_sync of bt_device.hpp, which the Phi^-1 kernels share).  A row's working set is 7 nx^2 + 3 nu^2 + ... elements of LDS (7.5 KB at
 // nx = 14, nu = 7, fp32): four waves per workgroup while they fit 64 KB, one otherwise.
 #include "row16.hpp"
 #include "schur_common.hpp"

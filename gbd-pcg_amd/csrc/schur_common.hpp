@@ -11,13 +11,6 @@
 
 namespace gbdpcg {
 
-// LDS operations of one wave execute in program order: the synchronisation inside a wave is a compiler fence.
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 struct KktDims {
     uint32_t nx, nu, N;
     uint32_t sg, sc, sv;  // strides of one knot in G / C / g

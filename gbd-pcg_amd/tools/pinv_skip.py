@@ -1,4 +1,4 @@
-"""Timing builds of pinv_stair_mfma_kernel with parts switched off (make fvariant NAME=pskipK EXTRA=-DGBDPCG_PINV_SKIP=K UNITS=pinv;
+"""Timing builds of pinv_stair_mfma_kernel with parts switched off (make fvariant NAME=pskipK EXTRA=-DGBDPCG_PINV_SKIP=K UNITS=pinv_fused;
 1 no elimination, 2 no products, 4 no result stores; results are WRONG): where the time of the stair kernel goes."""
 import os, subprocess, sys
 ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")

@@ -1,4 +1,4 @@
-"""Reference, case table and route prediction for the tests of Phi^-1 formation (csrc/pinv.hip); not a test module.
+"""Reference, case table and route prediction for the tests of Phi^-1 formation (csrc/pinv*.hip); not a test module.
 
 reference()       plain fp64 numpy on S already rounded to the case's precision: D slot inv(D_k), R slot -D_k^-1 R_k D_{k+1}^-1,
                   L slot -D_k^-1 L_k D_{k-1}^-1; Jacobi the D slots only; identity D slot = I.  The two never-read corner slots (L of
@@ -11,8 +11,8 @@ same_precision()  the formulas in the case's OWN precision with plain numpy (np.
                   block's bound is max(TOL[dtype], 8 e_np(block)), e_np = the error of this evaluation against the reference, both
                   relative to the largest entry of the reference block: the project's tolerance, or a factor 8 for Gauss-Jordan
                   without pivoting over LAPACK's pivoted inverse at the same precision.
-CASES             one table, each case naming the kernel family it is meant to reach; route() restates the conditions of
-                  launch_form_pinv, and tests/test_pinv_reference.py holds every case to it.
+CASES             one table, each case naming the kernel family it is meant to reach; pinv_route() restates pinv_route of
+                  csrc/pinv.hip line for line, route() names the kernels of its family, and tests/test_pinv_reference.py holds every case to it.
 Everything is in the device layout: [B, N, 3, n * n], slot order L, D, R, element (r, c) of a block at c * n + r."""
 import collections
 import functools
@@ -29,11 +29,11 @@ MARGIN = 8.0
 IDENTITY, JACOBI, STAIR = 0, 1, 2
 LDS_PER_WG = 160 * 1024          # DeviceInfo::lds_per_wg_max
 
-# internal.hpp GBDPCG_SPECIALIZED_N and pinv.hip GBDPCG_PINV_N, restated: a change of either list must show up in route()
+# internal.hpp GBDPCG_SPECIALIZED_N and pinv_common.hpp GBDPCG_PINV_N, restated: a change of either list must show up in route()
 SPECIALIZED_N = (2, 4, 6, 8, 10, 12, 13, 14, 16, 18, 20, 24, 36)
 PINV_N = SPECIALIZED_N + (3, 5, 7, 9, 11, 15, 22)
 
-# every kernel template of pinv.hip (tests/test_pinv_reference.py compares with a list of its own)
+# every kernel template of the pinv units (tests/test_pinv_reference.py compares with a list of its own)
 FUSED = ("pinv_stair_fused_kernel",)
 MFMA = ("pinv_stair_mfma_kernel",)
 QUAD = ("pinv_diag_quad_kernel", "pinv_stair_reg_kernel")
@@ -47,12 +47,13 @@ G64 = ("pinv_diag_kernel<64,16>", "pinv_stair_kernel<64>")
 G256 = ("pinv_diag_kernel<256,16>", "pinv_stair_kernel<256>")
 G256L = ("pinv_diag_kernel<256,64>", "pinv_stair_kernel<256>")
 REFUSED = ("refused",)
-# launch_stair_only (pinv_diag_wide_kernel followed by pinv_stair_kernel<256>) serves a listed n in 33 .. 64 that is odd or whose
-# four factors exceed 64 KiB of static LDS.  The only listed n in that range is 36, which takes pinv_stair_wide_kernel in both
-# precisions: UNREACHABLE with today's size list, no case.
-STAIR_ONLY = ("pinv_diag_wide_kernel", "pinv_stair_kernel<256>")
+# PinvFamily of csrc/pinv_common.hpp, by name: the kernels of each family (the second one runs for the stair kind only)
+FAMILY_KERNELS = {"mfma": MFMA, "fused": FUSED, "quad": QUAD, "pair": PAIR_STAIR, "reg": REG_STAIR, "wide": WIDE,
+                  "lds64": G64, "lds256": G256, "lds256_long": G256L, "refused": REFUSED}
+LDS_TIER = {"lds64": 64, "lds256": 256, "lds256_long": 256}   # threads per knot: launch_form_pinv_g<T, GT, .>
 
 Case = collections.namedtuple("Case", "family dtype n N B kind perturbed s_off env")
+PinvSwitches = collections.namedtuple("PinvSwitches", "two_pass no_mfma pair no_wide mfma_from")
 
 
 def _align16(count, es):
@@ -60,34 +61,50 @@ def _align16(count, es):
     return (count + per - 1) // per * per
 
 
+def pinv_switches(env):
+    env = dict(env)
+    return PinvSwitches("GBDPCG_PINV_TWO_PASS" in env, "GBDPCG_PINV_NO_MFMA" in env, "GBDPCG_PINV_PAIR" in env,
+                        "GBDPCG_PINV_NO_WIDE" in env, int(env.get("GBDPCG_PINV_MFMA_FROM", 16)))
+
+
+def pinv_route(elem_size, n, N, kind, s_aligned16, verdicts_wanted, sw):
+    """pinv_route of csrc/pinv.hip, line for line: (family, chunks)."""
+    listed = n in PINV_N
+    specialised = n in SPECIALIZED_N
+    family, chunks = "refused", 0
+    if listed and 2 * n <= 64:
+        if n <= 16 and n % 2 == 0 and kind == 2 and N >= 2 and not sw.two_pass and specialised:
+            chunks = (N - 1 + 14) // 15
+            mfma = elem_size == 4 and n >= 12 and not sw.no_mfma and n >= sw.mfma_from and s_aligned16
+            family = "mfma" if mfma else "fused"
+        elif 2 * n <= 32:
+            family = "quad" if kind == 2 and not sw.pair else "pair"
+        else:
+            family = "reg"
+    elif listed and 32 < n <= 64 and not sw.no_wide:
+        family = "wide"
+    elif 2 * n * n <= 16 * 64:
+        family = "lds64"
+    elif 2 * n * n <= 16 * 256:
+        family = "lds256"
+    elif 2 * n * n <= 64 * 256:
+        family = "lds256_long"
+    if verdicts_wanted and chunks == 0:
+        family = "refused"
+    return family, chunks
+
+
 def route(dtype, n, N, kind, s_aligned=True, env=()):
-    """The kernels launch_form_pinv (verdicts == nullptr) starts for a shape, as names; kinds 0 and 1 return after the diagonal
-    pass, so only the first name runs then."""
-    es, env = np.dtype(dtype).itemsize, dict(env)
-    two_pass, pair = "GBDPCG_PINV_TWO_PASS" in env, "GBDPCG_PINV_PAIR" in env
-
-    def diag_only(names):
-        return names if kind == STAIR else names[:1]
-
-    if n in PINV_N and 2 * n <= 64:
-        if n <= 16 and n % 2 == 0 and kind == STAIR and N >= 2 and not two_pass and n in SPECIALIZED_N:
-            if es == 4 and n >= 12 and "GBDPCG_PINV_NO_MFMA" not in env and n >= int(env.get("GBDPCG_PINV_MFMA_FROM", 16)) and s_aligned:
-                return MFMA
-            return FUSED
-        if 2 * n <= 32:
-            return QUAD if kind == STAIR and not pair else diag_only(PAIR_STAIR)
-        return diag_only(REG_STAIR)
-    if n in PINV_N and 32 < n <= 64 and "GBDPCG_PINV_NO_WIDE" not in env:
-        if kind != STAIR or N < 2:
-            return WIDE[:1]
-        return WIDE if n % 2 == 0 and 4 * n * n * es <= 64 * 1024 else STAIR_ONLY
-    for tier, gt, ept in ((G64, 64, 16), (G256, 256, 16), (G256L, 256, 64)):
-        if 2 * n * n <= ept * gt:
-            groups = 256 // gt
-            if groups * _align16(4 * n * n, es) * es > LDS_PER_WG:
-                return REFUSED
-            return diag_only(tier)
-    return REFUSED
+    """The kernels launch_form_pinv (verdicts == nullptr) starts for a shape, as names: the family pinv_route picks, refused where
+    launch_form_pinv_g finds the four factors of a workgroup's knots over the LDS of a compute unit; kinds 0 and 1 return after
+    the diagonal pass (and so does pinv_diag_wide_kernel at N = 1), so only the first name runs then."""
+    es = np.dtype(dtype).itemsize
+    family, _ = pinv_route(es, n, N, kind, s_aligned, False, pinv_switches(env))
+    if family in LDS_TIER and 256 // LDS_TIER[family] * _align16(4 * n * n, es) * es > LDS_PER_WG:
+        family = "refused"
+    names = FAMILY_KERNELS[family]
+    stair_pass = kind == STAIR and (family != "wide" or N >= 2)
+    return names if stair_pass else names[:1]
 
 
 def _cases():

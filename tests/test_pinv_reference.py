@@ -1,6 +1,9 @@
 """CPU half of tests/test_gpu_pinv_dispatch.py: the reference of tests/pinv_ref.py against the product-side host formula and
 against exact rationals, the conditioning of the inputs, the yardstick against the project's tolerance, and the case table against
 a restatement of launch_form_pinv's conditions."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -9,7 +12,7 @@ from gbd_pcg_amd import synth
 
 F32, F64 = pr.F32, pr.F64
 
-# every kernel template of csrc/pinv.hip, written here (not read from the binary or from pinv_ref.py)
+# every kernel template of csrc/pinv.hip, pinv_regs.hip and pinv_fused.hip, written here (not read from the binary or from pinv_ref.py)
 KERNEL_TEMPLATES = ["pinv_diag_kernel", "pinv_stair_kernel", "pinv_diag_reg_kernel", "pinv_diag_pair_kernel", "pinv_diag_quad_kernel",
                     "pinv_diag_wide_kernel", "pinv_stair_reg_kernel", "pinv_stair_fused_kernel", "pinv_stair_mfma_kernel",
                     "pinv_stair_wide_kernel"]
@@ -84,8 +87,6 @@ def test_table_names_every_kernel_template():
         assert t in named, t
     for k in named:
         assert k.split("<")[0] in KERNEL_TEMPLATES, k
-    # the one launcher without a case: see pinv_ref.STAIR_ONLY
-    assert not any(pr.route(dt, n, 5, pr.STAIR) == pr.STAIR_ONLY for dt in (F32, F64) for n in range(1, 100))
 
 
 def test_every_case_takes_the_route_the_table_claims():
@@ -105,6 +106,26 @@ def test_every_case_takes_the_route_the_table_claims():
     for dt in (F32, F64):
         assert pr.route(dt, pr.FIRST_REFUSED[dt], 2, pr.STAIR) == pr.REFUSED
         assert pr.route(dt, pr.LARGEST[dt], 2, pr.STAIR) == pr.G256L and pr.LARGEST[dt] + 1 == pr.FIRST_REFUSED[dt]
+
+
+def test_route_agrees_with_the_table_recorded_before_the_rewrite():
+    """tests/golden/pinv_routes.json: what route() returned for every (dtype, n <= 91, N in {1, 2}, kind, S aligned) when it still
+    restated the launcher's macro bodies, before it and the launcher were rewritten around one pinv_route: kernel names only."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pinv_routes.json")) as fh:
+        recorded = json.load(fh)
+    seen = 0
+    for dt in (F32, F64):
+        for n in range(1, 92):
+            for N in (1, 2):
+                for kind in (0, 1, 2):
+                    for aligned in (True, False):
+                        key = "%s,%d,%d,%d,%d" % (np.dtype(dt).name, n, N, kind, aligned)
+                        assert "+".join(pr.route(dt, n, N, kind, aligned)) == recorded[key], key
+                        seen += 1
+    assert seen == len(recorded)
+    # every family name of the route is one of the documented ones, and each names kernels of the template list
+    for family, names in pr.FAMILY_KERNELS.items():
+        assert family == "refused" or all(k.split("<")[0] in KERNEL_TEMPLATES for k in names), family
 
 
 def test_cases_are_unique():
