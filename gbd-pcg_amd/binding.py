@@ -61,6 +61,8 @@ SYMBOLS = [
     "gbdpcg_kkt_backward_f32", "gbdpcg_kkt_backward_f64", "gbdpcg_kkt_backward_shared_f32", "gbdpcg_kkt_backward_shared_f64",
     "gbdpcg_graph_create_kkt_backward_f32", "gbdpcg_graph_create_kkt_backward_f64",
     "gbdpcg_graph_create_kkt_backward_shared_f32", "gbdpcg_graph_create_kkt_backward_shared_f64",
+    "gbdpcg_demote_f32", "gbdpcg_kkt_defect_mixed", "gbdpcg_kkt_refine_apply", "gbdpcg_kkt_refine_step",
+    "gbdpcg_graph_create_kkt_refine_step",
     "gbdpcg_csr_to_bt_f32", "gbdpcg_csr_to_bt_f64", "gbdpcg_version",
 ]
 
@@ -115,6 +117,17 @@ def _resolve_argtypes(lib):
         for name in ("kkt_backward", "kkt_backward_shared"):
             getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = back + [vp]
             getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = back + [ctypes.POINTER(vp)]
+
+    # mixed-precision refinement (no suffix: fp64 data and point, fp32 solve)
+    head = [vp, u32, u32, u32, u32, vp, vp, vp, vp]                # h, nx, nu, N, batch, G, C, g, c (fp64)
+    lib.gbdpcg_demote_f32.argtypes = [vp, ctypes.c_uint64, vp, vp, vp]                    # h, count, src, dst, stream
+    lib.gbdpcg_kkt_defect_mixed.argtypes = head + [vp, vp, vp, vp, vp, vp, vp, vp]        # z, lambda | rg, rc, dlambda, expo, res | stream
+    lib.gbdpcg_kkt_refine_apply.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp]   # dz, dlambda, expo | z, lambda | stream
+    # Ginv32, C32, S32, Pinv32 | rg, rc, gamma, dlambda, r, p, dz | tol, max_iter, iters, flags | expo, z, lambda, res
+    step = head + [vp] * 4 + [vp] * 7 + [ctypes.c_float, u32, vp, vp] + [vp] * 4
+    lib.gbdpcg_kkt_refine_step.argtypes = step + [vp]
+    lib.gbdpcg_graph_create_kkt_refine_step.argtypes = step + [ctypes.POINTER(vp)]
+
 
 _lib = None
 
@@ -907,6 +920,121 @@ class Solver:
         """Capture the shared-matrix backward pass into one hipGraph (gbdpcg_graph_create_kkt_backward_shared_*)."""
         return self._graph_kkt_backward("kkt_backward_shared", nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam,
                                         r, p, tol, max_iter, iters, max_iter_exit, gG, gC)
+
+
+    # ---- mixed-precision refinement: fp64 problem data and point, fp32 solves on a kept fp32 factorisation (include/gbdpcg.h)
+    def demote(self, src, dst=None, stream=None):
+        """gbdpcg_demote_f32: the fp64 tensor rounded to fp32 (to nearest), on the device."""
+        import torch
+        assert src.is_cuda and src.is_contiguous() and src.dtype == torch.float64
+        if dst is None:
+            dst = torch.empty(src.shape, dtype=torch.float32, device=src.device)
+        assert dst.is_cuda and dst.is_contiguous() and dst.dtype == torch.float32 and dst.numel() == src.numel()
+        self._check(self.lib.gbdpcg_demote_f32(self.h, src.numel(), _p(src), _p(dst), self._stream(stream)), "demote")
+        return dst
+
+    @staticmethod
+    def _refine_check(nx, nu, N, batch, f64=(), f32_g=(), f32_c=(), expo=None, res=None):
+        import torch
+        nz, nl = (nx + nu) * N - nu, nx * N
+        for t in f64:
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64)
+        for ts, cnt in ((f32_g, nz), (f32_c, nl)):
+            for t in ts:
+                assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == batch * cnt)
+        assert expo is None or (expo.is_cuda and expo.is_contiguous() and expo.dtype == torch.int32 and expo.numel() == batch)
+        assert res is None or (res.is_cuda and res.is_contiguous() and res.dtype == torch.float64 and res.numel() == 2 * batch)
+
+    def kkt_defect_mixed(self, nx, nu, N, batch, G, C, g, c, z, lam, rg=None, rc=None, dlam=None, expo=None, res=None, stream=None,
+                         zero_dlam=True):
+        """gbdpcg_kkt_defect_mixed: the fp64 defect of (z, lam) as the scaled fp32 right-hand side of the correction system.
+        Returns (rg, rc, dlam, expo, res [batch, 2]); zero_dlam=False passes NULL for dlam."""
+        import torch
+        if rg is None:
+            rg = torch.empty(batch * ((nx + nu) * N - nu), dtype=torch.float32, device=G.device)
+        if rc is None:
+            rc = torch.empty(batch * nx * N, dtype=torch.float32, device=G.device)
+        if dlam is None and zero_dlam:
+            dlam = torch.empty(batch * nx * N, dtype=torch.float32, device=G.device)
+        if expo is None:
+            expo = torch.empty(batch, dtype=torch.int32, device=G.device)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=torch.float64, device=G.device)
+        self._refine_check(nx, nu, N, batch, (G, C, g, c, z, lam), (rg,), (rc, dlam), expo, res)
+        self._check(self.lib.gbdpcg_kkt_defect_mixed(self.h, nx, nu, N, batch, _p(G), _p(C), _p(g), _p(c), _p(z), _p(lam), _p(rg),
+                                                     _p(rc), _p(dlam), _p(expo), _p(res), self._stream(stream)), "kkt_defect_mixed")
+        return rg, rc, dlam, expo, res.view(batch, 2)
+
+    def kkt_refine_apply(self, nx, nu, N, batch, dz, dlam, expo, z, lam, stream=None):
+        """gbdpcg_kkt_refine_apply: z += ldexp(dz, -e_b), lam += ldexp(dlam, -e_b) in fp64, in place."""
+        self._refine_check(nx, nu, N, batch, (z, lam), (dz,), (dlam,), expo)
+        self._check(self.lib.gbdpcg_kkt_refine_apply(self.h, nx, nu, N, batch, _p(dz), _p(dlam), _p(expo), _p(z), _p(lam),
+                                                     self._stream(stream)), "kkt_refine_apply")
+        return z, lam
+
+    def _refine_step_args(self, nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, rg, rc, gamma, dlam, r, p, dz, tol, max_iter,
+                          iters, mie, expo, z, lam, res):
+        self._refine_check(nx, nu, N, batch, (G, C, g, c, z, lam), (rg, dz), (rc, gamma, dlam, r, p), expo, res)
+        return (self.h, nx, nu, N, batch, _p(G), _p(C), _p(g), _p(c), _p(Ginv32), _p(C32), _p(S32), _p(Pinv32), _p(rg), _p(rc),
+                _p(gamma), _p(dlam), _p(r), _p(p), _p(dz), tol, max_iter, _p(iters), _p(mie), _p(expo), _p(z), _p(lam), _p(res))
+
+    def refine_work(self, nx, nu, N, batch, device="cuda"):
+        """The fp32 work arrays and status words of a refinement step, as a dict of the keyword arguments of kkt_refine_step."""
+        import torch
+        nz, nl = batch * ((nx + nu) * N - nu), batch * nx * N
+        f = dict(dtype=torch.float32, device=device)
+        return dict(rg=torch.empty(nz, **f), rc=torch.empty(nl, **f), gamma=torch.empty(nl, **f), dlam=torch.empty(nl, **f),
+                    r=torch.empty(nl, **f), p=torch.empty(nl, **f), dz=torch.empty(nz, **f),
+                    iters=torch.zeros(batch, dtype=torch.int32, device=device),
+                    max_iter_exit=torch.zeros(batch, dtype=torch.uint8, device=device),
+                    expo=torch.empty(batch, dtype=torch.int32, device=device),
+                    res=torch.empty(batch, 2, dtype=torch.float64, device=device))
+
+    def kkt_refine_step(self, nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, z, lam, *, rg, rc, gamma, dlam, r, p, dz, iters,
+                        max_iter_exit, expo, res, tol=1e-4, max_iter=50, stream=None):
+        """gbdpcg_kkt_refine_step: defect of (z, lam) -> fp32 correction solve on the kept factorisation -> fp64 accumulation.
+        res [batch, 2] holds the norms of the point the step started from.  The work arrays: refine_work()."""
+        args = self._refine_step_args(nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, rg, rc, gamma, dlam, r, p, dz, tol,
+                                      max_iter, iters, max_iter_exit, expo, z, lam, res)
+        self._check(self.lib.gbdpcg_kkt_refine_step(*args, self._stream(stream)), "kkt_refine_step")
+        return res.view(batch, 2)
+
+    def graph_kkt_refine_step(self, nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, z, lam, *, rg, rc, gamma, dlam, r, p, dz,
+                              iters, max_iter_exit, expo, res, tol=1e-4, max_iter=50):
+        """Capture one refinement step into a hipGraph (gbdpcg_graph_create_kkt_refine_step)."""
+        args = self._refine_step_args(nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, rg, rc, gamma, dlam, r, p, dz, tol,
+                                      max_iter, iters, max_iter_exit, expo, z, lam, res)
+        gr = ctypes.c_void_p()
+        self._check(self.lib.gbdpcg_graph_create_kkt_refine_step(*args, ctypes.byref(gr)), "graph_create_kkt_refine_step")
+        return Graph(self, gr, keep=(G, C, g, c, Ginv32, C32, S32, Pinv32, rg, rc, gamma, dlam, r, p, dz, iters, max_iter_exit, expo,
+                                     z, lam, res))
+
+    def kkt_solve_refined(self, nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, z=None, lam=None, max_steps=12, stop_s=0.0,
+                          stop_f=0.0, tol=1e-4, max_iter=50, work=None):
+        """Replay the refinement step from (z, lam) (zeros when not given) until every problem has stationarity <= stop_s and
+        feasibility <= stop_f (scalars or [batch] arrays) or max_steps steps have run; res is read back between steps.
+        Returns (z, lam, history): history[i] is the [batch, 2] numpy array of the norms of the point step i started from; when
+        the loop stops on the norms, the last entry belongs to the point in front of the last step."""
+        import torch
+        if z is None:
+            z = torch.zeros(batch * ((nx + nu) * N - nu), dtype=torch.float64, device=G.device)
+        if lam is None:
+            lam = torch.zeros(batch * nx * N, dtype=torch.float64, device=G.device)
+        work = work or self.refine_work(nx, nu, N, batch, G.device)
+        graph = self.graph_kkt_refine_step(nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, z, lam, tol=tol, max_iter=max_iter,
+                                           **work)
+        history = []
+        try:
+            for _ in range(max_steps):
+                graph.launch()
+                torch.cuda.current_stream().synchronize()
+                res = work["res"].view(batch, 2).cpu().numpy().copy()
+                history.append(res)
+                if (res[:, 0] <= stop_s).all() and (res[:, 1] <= stop_f).all():
+                    break   # (the step just replayed has refined the point that passed once more)
+        finally:
+            graph.close()
+        return z, lam, history
 
 
 class Graph:

@@ -308,6 +308,77 @@ gbdpcg_status kkt_backward_impl(gbdpcg_handle_t h, const KktOperands<T> &k, cons
     return kkt_grad_impl<T>(h, a.n, k.nu, a.N, a.batch, f.z, f.lambda, k.z, a.lambda, f.gG, f.gC, stream, k.shared);
 }
 
+// ---- mixed-precision refinement (kkt_refine.hip): fp64 problem data and point, an fp32 solve on a kept fp32 factorisation
+// The fp64 side of a refinement step: the problem, the point that is refined, and what the defect launch writes next to the
+// right-hand side.  The fp32 side is a KktOperands<float> (g := rg, c := rc, z := dz) and the PcgArgs<float> of its solve.
+struct RefineOperands {
+    const double *G, *C, *g, *c;
+    double *z, *lambda, *res;
+    int32_t *expo;
+    float *rg, *rc;   // the right-hand side of the correction system: the g and the c of the fp32 side
+};
+
+// What the fp64 launches refuse: the rules of gbdpcg_kkt_residual_f64.
+gbdpcg_status refine_shape_status(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch)
+{
+    if (nu == 0 || !shape_ok(nx, N, batch)) return GBDPCG_ERR_INVALID;
+    return schur_shape_ok<double>(h->dev, nx, nu) ? GBDPCG_OK : GBDPCG_ERR_UNSUPPORTED;
+}
+
+gbdpcg_status kkt_defect_mixed_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_G,
+                                    const double *d_C, const double *d_g, const double *d_c, const double *d_z, const double *d_lambda,
+                                    float *d_rg, float *d_rc, float *d_dlambda, int32_t *d_expo, double *d_res, void *stream)
+{
+    if (!h || !d_G || !d_g || !d_c || !d_z || !d_lambda || !d_rg || !d_rc || !d_expo || !d_res || (!d_C && N > 1))
+        return GBDPCG_ERR_INVALID;
+    const gbdpcg_status st = refine_shape_status(h, nx, nu, N, batch);
+    if (st != GBDPCG_OK) return st;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_kkt_defect_mixed(h->dev, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_rg, d_rc, d_dlambda, d_expo, d_res,
+                                       (hipStream_t)stream));
+    return GBDPCG_OK;
+}
+
+gbdpcg_status kkt_refine_apply_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_dz,
+                                    const float *d_dlambda, const int32_t *d_expo, double *d_z, double *d_lambda, void *stream)
+{
+    if (!h || !d_dz || !d_dlambda || !d_expo || !d_z || !d_lambda) return GBDPCG_ERR_INVALID;
+    const gbdpcg_status st = refine_shape_status(h, nx, nu, N, batch);
+    if (st != GBDPCG_OK) return st;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_kkt_refine_apply(nx, nu, N, batch, d_dz, d_dlambda, d_expo, d_z, d_lambda, (hipStream_t)stream));
+    return GBDPCG_OK;
+}
+
+// What gbdpcg_kkt_refine_step refuses before anything is written, reserved or captured: whatever one of its three parts would
+// refuse, every INVALID before every UNSUPPORTED.  solve_limits: as in admm_step_refusal.
+gbdpcg_status refine_step_refusal(gbdpcg_handle_t h, const RefineOperands &f, const KktOperands<float> &k, const PcgArgs<float> &a,
+                                  bool solve_limits)
+{
+    if (!h || !f.G || !f.g || !f.c || !f.z || !f.lambda || !f.expo || !f.res || (!f.C && a.N > 1) || !k.Ginv || !k.g || !k.c ||
+        !k.gamma || !k.z || (!k.C && a.N > 1) || !a.S || !a.lambda || !a.iters)
+        return GBDPCG_ERR_INVALID;
+    gbdpcg_status st = refine_shape_status(h, a.n, k.nu, a.N, a.batch);
+    if (st != GBDPCG_OK) return st;
+    if (!schur_shape_ok<float>(h->dev, a.n, k.nu)) return GBDPCG_ERR_UNSUPPORTED;
+    if (solve_limits && !mappable<float>(a.n)) return GBDPCG_ERR_UNSUPPORTED;
+    return GBDPCG_OK;
+}
+
+// One refinement step: the defect of (z, lambda) in fp64 as the scaled fp32 right-hand side (k.g, k.c) and the zeroed start
+// a.lambda, kkt_resolve_impl<float> on the kept factorisation, the fp64 accumulation of (k.z, a.lambda), on one stream.
+gbdpcg_status kkt_refine_step_impl(gbdpcg_handle_t h, const RefineOperands &f, const KktOperands<float> &k, const PcgArgs<float> &a,
+                                   hipStream_t stream)
+{
+    gbdpcg_status st = refine_step_refusal(h, f, k, a, true);
+    if (st != GBDPCG_OK) return st;
+    st = kkt_defect_mixed_impl(h, a.n, k.nu, a.N, a.batch, f.G, f.C, f.g, f.c, f.z, f.lambda, f.rg, f.rc, a.lambda, f.expo, f.res, stream);
+    if (st != GBDPCG_OK) return st;
+    st = kkt_resolve_impl<float>(h, k, a, stream);
+    if (st != GBDPCG_OK) return st;
+    return kkt_refine_apply_impl(h, a.n, k.nu, a.N, a.batch, k.z, a.lambda, f.expo, f.z, f.lambda, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -546,5 +617,54 @@ GBDPCG_ADMM_STEPS(admm_soc_step)
     if (const gbdpcg_status st = kkt_backward_refusal<TYPE>(h, k, f, a, false)) return st;
 GBDPCG_PAIR_BOTH(kkt_backward, false, BACKWARD_PARAMS, BACKWARD_SETUP, BACKWARD_REFUSE)
 GBDPCG_PAIR_BOTH(kkt_backward_shared, true, BACKWARD_PARAMS, BACKWARD_SETUP, BACKWARD_REFUSE)
+
+// ---- mixed-precision refinement: the three single launches, then the step (defect, gbdpcg_kkt_resolve_f32, apply) as one call /
+// one graph.  No suffix: the precisions are fixed -- fp64 data and point, fp32 solve.
+gbdpcg_status gbdpcg_demote_f32(gbdpcg_handle_t h, uint64_t count, const double *d_src, float *d_dst, void *stream)
+{
+    if (!h || !d_src || !d_dst || count == 0) return GBDPCG_ERR_INVALID;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_demote(h->dev, count, d_src, d_dst, (hipStream_t)stream));
+    return GBDPCG_OK;
+}
+gbdpcg_status gbdpcg_kkt_defect_mixed(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_G,
+                                      const double *d_C, const double *d_g, const double *d_c, const double *d_z,
+                                      const double *d_lambda, float *d_rg, float *d_rc, float *d_dlambda, int32_t *d_expo,
+                                      double *d_res, void *stream)
+{
+    return kkt_defect_mixed_impl(h, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_rg, d_rc, d_dlambda, d_expo, d_res, stream);
+}
+gbdpcg_status gbdpcg_kkt_refine_apply(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_dz,
+                                      const float *d_dlambda, const int32_t *d_expo, double *d_z, double *d_lambda, void *stream)
+{
+    return kkt_refine_apply_impl(h, nx, nu, N, batch, d_dz, d_dlambda, d_expo, d_z, d_lambda, stream);
+}
+#define REFINE_PARAMS                                                                                                               \
+    gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_G, const double *d_C,                  \
+        const double *d_g, const double *d_c, const float *d_Ginv32, const float *d_C32, const float *d_S32,                        \
+        const float *d_Pinv32, float *d_rg, float *d_rc, float *d_gamma, float *d_dlambda, float *d_r, float *d_p, float *d_dz,     \
+        float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, int32_t *d_expo, double *d_z, double *d_lambda,  \
+        double *d_res
+#define REFINE_SETUP                                                                                                                \
+    const RefineOperands f{d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, d_expo, d_rg, d_rc};                                           \
+    const KktOperands<float> k{nu, d_Ginv32, d_C32, d_rg, d_rc, d_gamma, d_dz};                                                     \
+    const PcgArgs<float> a =                                                                                                        \
+        pcg_args<float>(nx, N, batch, d_S32, d_Pinv32, d_gamma, d_dlambda, d_r, d_p, tol, max_iter, d_iters, d_max_iter_exit);      \
+    auto body = [&](hipStream_t s) { return kkt_refine_step_impl(h, f, k, a, s); };
+gbdpcg_status gbdpcg_kkt_refine_step(REFINE_PARAMS, void *stream)
+{
+    REFINE_SETUP
+    return body((hipStream_t)stream);
+}
+gbdpcg_status gbdpcg_graph_create_kkt_refine_step(REFINE_PARAMS, gbdpcg_graph_t *out)
+{
+    REFINE_SETUP
+    if (!out) return GBDPCG_ERR_INVALID;
+    *out = nullptr;
+    if (const gbdpcg_status st = refine_step_refusal(h, f, k, a, false)) return st;
+    return graph_create<float>(h, a, false, out, body);
+}
+#undef REFINE_PARAMS
+#undef REFINE_SETUP
 
 }  // extern "C"

@@ -294,4 +294,17 @@ template <typename T>
 hipError_t launch_kkt_grad(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *z, const T *lam, const T *az, const T *alam,
                            T *gG, T *gC, hipStream_t s, bool shared = false);
 
+// ---- kkt_refine.hip : mixed-precision refinement around an fp32 solve on a kept factorisation; the lines that define every bit
+// are in the head of the file.  One workgroup per problem in the first two.
+//     defect: rg = fl32(G z + g + C' lambda) 2^e_b, rc = fl32(-(C z - c)) 2^e_b, dlambda = 0 (may be null), expo[b] = e_b,
+//             res[2b], res[2b+1] = the norms launch_kkt_residual<double> writes for the same point
+//     apply:  z += (double)dz 2^-e_b, lambda += (double)dlambda 2^-e_b
+//     demote: dst[i] = fl32(src[i]), i < count
+hipError_t launch_kkt_defect_mixed(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *G,
+                                   const double *C, const double *g, const double *c, const double *z, const double *lambda, float *rg,
+                                   float *rc, float *dlambda, int32_t *expo, double *res, hipStream_t s);
+hipError_t launch_kkt_refine_apply(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *dz, const float *dlambda,
+                                   const int32_t *expo, double *z, double *lambda, hipStream_t s);
+hipError_t launch_demote(const DeviceInfo &dev, uint64_t count, const double *src, float *dst, hipStream_t s);
+
 }  // namespace gbdpcg

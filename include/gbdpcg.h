@@ -1018,6 +1018,74 @@ gbdpcg_status gbdpcg_graph_create_kkt_backward_shared_f64(gbdpcg_handle_t h, uin
                                                           uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
                                                           double *d_gG, double *d_gC, gbdpcg_graph_t *out);
 
+/* Mixed-precision refinement of a KKT point: fp32 solves on a kept fp32 factorisation, the defect and the point in fp64.
+ * For a caller who needs more digits in the step than fp32 carries (SQP close to convergence, an adjoint solve, ADMM on a
+ * kept factorisation) without the price of the fp64 pipeline: factor once in fp32 (gbdpcg_demote_f32 of G and C, then
+ * gbdpcg_kkt_step_f32, or gbdpcg_form_schur_f32 + gbdpcg_form_pinv_f32), then per step evaluate the defect of the current
+ * fp64 point in fp64, solve for the correction with gbdpcg_kkt_resolve_f32, accumulate in fp64.  Conventions and layouts are
+ * those of f4 above; the fp64 operands are d_G, d_C, d_g, d_c, d_z, d_lambda.
+ *
+ * gbdpcg_kkt_defect_mixed, per problem b (one launch):
+ *     r_s = G z + g + C' lambda  (layout of d_g),   r_f = C z - c  (layout of d_c)
+ *         every entry the fp64 fma chain of gbdpcg_kkt_residual_f64, in its order of terms
+ *     m_s = max |r_s|,  m_f = max |r_f|     over bit patterns, NaN-propagating, as in gbdpcg_kkt_residual_*
+ *     e_b = 0 where m = max(m_s, m_f) is 0, Inf or NaN; otherwise -ilogb(m) clamped to [-126, 127]  (m 2^e in [1, 2) unclamped)
+ *     d_rg[i]      = fl32(r_s[i]) * 2^e_b       fp32: ONE rounding to fp32, then a product by the power of two in fp32, which is
+ *     d_rc[i]      = fl32(-r_f[i]) * 2^e_b      exact unless it is subnormal or overflows
+ *     d_dlambda[i] = 0                          fp32, nx N per problem, where the pointer is not NULL: the cold start of the
+ *                                               correction solve, written in the same pass
+ *     d_expo[b]    = e_b                        int32_t
+ *     d_res[2b] = m_s, d_res[2b+1] = m_f        fp64: bit for bit what gbdpcg_kkt_residual_f64 writes for the same point
+ * d_rg and d_rc are the g and the c of the correction system G dz + C' dlambda = -r_s, C dz = -r_f, scaled.
+ * WHY THE SCALING: the exit test of gbdpcg_solve_* is ABSOLUTE (|eta| < tol).  From the second refinement step on the defect is
+ * 1e-6 and smaller; an unscaled correction solve would leave after zero iterations and the refinement would stall at fp32
+ * accuracy.  The exact power of two per problem makes every correction solve see a right-hand side whose max-norm is in [1, 2)
+ * -- `tol` below applies to THAT system -- and costs no rounding.
+ * Every output is overwritten whatever it held and depends on nothing it held; a problem with a NaN or an Inf in its defect gets
+ * e_b = 0 and that norm, the other problems of the batch are unaffected.
+ *
+ * gbdpcg_kkt_refine_apply (one launch):  z[i] = z[i] + ldexp((double)dz[i], -e_b), lambda likewise from d_dlambda.  Widening
+ * and scaling are exact, so each element is ONE IEEE addition; the bits do not depend on the alignment of the pointers.
+ *
+ * gbdpcg_demote_f32:  d_dst[i] = fl32(d_src[i]), round to nearest, i < count: the fp32 G and C the factorisation is formed from.
+ *
+ * gbdpcg_kkt_refine_step: the defect launch, gbdpcg_kkt_resolve_f32 with g := d_rg, c := d_rc from the zeroed d_dlambda on the
+ * kept d_Ginv32, d_C32, d_S32, d_Pinv32 (correction d_dz, d_dlambda), the apply launch: bit-identical with those three calls.
+ * d_res holds the norms of the point the step STARTED from.  gbdpcg_graph_create_kkt_refine_step takes the same arguments and
+ * reserves like the other graph constructors: replay it K times from z = lambda = 0 for a whole solve, or after rewriting g, c
+ * in place for the next tick of a kept linearisation.  d_rg, d_rc, d_gamma, d_dlambda, d_r, d_p, d_dz are fp32 work arrays
+ * (layouts of g, c, c, c, c, c, g); d_Pinv32, d_r, d_p, d_max_iter_exit may be NULL as in gbdpcg_kkt_resolve_f32.
+ *
+ * All of them: asynchronous on `stream`, capturable, no allocation beyond what gbdpcg_reserve (or the graph constructor) sizes
+ * for the fp32 solve.  Null handle or required pointer, nx, nu, N, batch or count == 0: GBDPCG_ERR_INVALID; a shape
+ * gbdpcg_form_schur_* refuses (in either precision): GBDPCG_ERR_UNSUPPORTED; nothing is written in either case.  d_C and d_C32
+ * may be NULL when N == 1.
+ * Not provided: _shared twins, and a _reg form.  A factorisation of G + rho I from gbdpcg_kkt_step_reg_f32 may be passed as the
+ * kept one: the defect does not contain rho, so the refinement then converges, more slowly, to the solution of the
+ * UNREGULARISED fp64 system. */
+gbdpcg_status gbdpcg_demote_f32(gbdpcg_handle_t h, uint64_t count, const double *d_src, float *d_dst, void *stream);
+gbdpcg_status gbdpcg_kkt_defect_mixed(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                      const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                      const double *d_z, const double *d_lambda, float *d_rg, float *d_rc, float *d_dlambda,
+                                      int32_t *d_expo, double *d_res, void *stream);
+gbdpcg_status gbdpcg_kkt_refine_apply(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                      const float *d_dz, const float *d_dlambda, const int32_t *d_expo, double *d_z,
+                                      double *d_lambda, void *stream);
+gbdpcg_status gbdpcg_kkt_refine_step(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                     const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                     const float *d_Ginv32, const float *d_C32, const float *d_S32, const float *d_Pinv32,
+                                     float *d_rg, float *d_rc, float *d_gamma, float *d_dlambda, float *d_r, float *d_p,
+                                     float *d_dz, float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                     int32_t *d_expo, double *d_z, double *d_lambda, double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_kkt_refine_step(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                  const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                                  const float *d_Ginv32, const float *d_C32, const float *d_S32,
+                                                  const float *d_Pinv32, float *d_rg, float *d_rc, float *d_gamma,
+                                                  float *d_dlambda, float *d_r, float *d_p, float *d_dz, float tol,
+                                                  uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                                  int32_t *d_expo, double *d_z, double *d_lambda, double *d_res,
+                                                  gbdpcg_graph_t *out);
+
 /* CSR ingestion (f3): repacks a host CSR matrix (csr_t<T>, include/types.cuh:7-15) whose
  * sparsity lies inside the block-tridiagonal pattern into the [L|D|R] layout (host arrays).
  * Entries outside the pattern give GBDPCG_ERR_INVALID.  Implements what the stub overload
