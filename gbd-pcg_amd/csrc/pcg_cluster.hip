@@ -14,7 +14,7 @@
 // Every workgroup sums all 8H partials in the same order -> the exit test of pcg.cuh:195 is uniform over the cluster --
 // what pcg.cuh:147,167,191 ensure with their redundant per-block sums.  Hand-off words are data-tagged 8-byte granules
 // {value, epoch} written with sc1 (write-through) stores and polled with sc1 loads: the data is the flag, no fence
-// (MI355X_MICROARCH.md, Valid forms, R2; the same protocol as pcg_persist.hip).  One such hand-off between two CUs costs
+// (MI355X_MICROARCH.md, Valid forms, R2; the same granules as pcg_persist_handoff.hpp: handoff_words.hpp).  One such hand-off between two CUs costs
 // 0.44-0.56 us (tools/hop_probe.hip), against 1.4-2 us for the chip-wide all-gather of the persistent path.
 //
 // Nothing is initialised or cleared by a launch (a solve stays ONE kernel node in a hipGraph) and a slot is only ever
@@ -44,16 +44,12 @@
 #include <cstdlib>
 
 #include "bt_dense.hpp"
+#include "handoff_words.hpp"
 #include "pcg_stream.hpp"
 
 namespace gbdpcg {
 
 namespace {
-
-typedef unsigned long long u64;
-typedef unsigned int cl_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int cl_u32x4 __attribute__((ext_vector_type(4)));
-constexpr int kClSc1 = 16;   // cache-policy bits of the raw buffer builtins on gfx950: bit 4 = sc1
 
 // Workspace: [256-byte block: stamps of the diagnostic build, words 30 / 31 = finish counter / launch number |
 // per cluster two words: members that have left, and 2^32 - 1 - (first problem a member gave up on) maximised over the
@@ -158,7 +154,7 @@ void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
     __shared__ T bc[4];           // [0] alpha / eta' of the phase just gathered, [1] beta
     __shared__ uint32_t bci[4];   // [0] 0 go on, 1 converged, 2 hand-off timed out; [2], [3] the rescue's bookkeeping
     __shared__ T rescue_red[2 * Dg::WAVES];
-    __shared__ cl_u32x4 lpart[ONE ? Dg::WAVES : 1];   // ONE: the wave partials of a hand-off, laid out like the slot in memory
+    __shared__ u32x4 lpart[ONE ? Dg::WAVES : 1];   // ONE: the wave partials of a hand-off, laid out like the slot in memory
     extern __shared__ __attribute__((aligned(16))) unsigned char stage_raw[];   // STAGED: dense_stage_lds_bytes (bt_dense.hpp)
     // The last PTAIL columns of this lane's block-row of Pinv (its V rows each) live in LDS instead of registers (dense_mv, TAIL):
     // at n = 16 the whole R block of Pinv -- 2 x 96 matrix registers per lane do not fit next to the working set, 96 + 64 do;
@@ -239,16 +235,16 @@ void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
             cl_pack<T, V>(VALS, w0, w1);                                                                             \
             const T part_[1] = {PART};                                                                               \
             cl_pack<T, 1>(part_, q0, q1);                                                                            \
-            const cl_u32x2 x2 = {q0, tag};                                                                           \
-            const cl_u32x4 x4 = {q0, tag, q1, tag};                                                                  \
-            const cl_u32x4 bx = {w0, tag, w1, tag};                                                                  \
+            const u32x2 x2 = {q0, tag};                                                                              \
+            const u32x4 x4 = {q0, tag, q1, tag};                                                                     \
+            const u32x4 bx = {w0, tag, w1, tag};                                                                     \
             const int o_part = (int)(par_off + my_slot + wave * (sizeof(T) == 4 ? 8u : 16u)),                        \
                       o_first = (int)(par_off + my_slot + kClFirstOff + lo * 16),                                    \
                       o_last = (int)(par_off + my_slot + kClLastOff + (lo - lb * LPB) * 16);                         \
             const bool p_first = wave == 0 && has_left && lo < LPB, p_last = wave == wl && has_right && lo - lb * LPB < LPB; \
             if constexpr (ONE) {                                                                                     \
                 if (lo == 0) {                                                                                       \
-                    if constexpr (sizeof(T) == 4) reinterpret_cast<cl_u32x2 *>(lpart)[wave] = x2;                    \
+                    if constexpr (sizeof(T) == 4) reinterpret_cast<u32x2 *>(lpart)[wave] = x2;                       \
                     else lpart[wave] = x4;                                                                           \
                 }                                                                                                    \
             } else if (same_xcd) {   /* plain: the line stays in this XCD's L2, where every member of the cluster polls */   \
@@ -260,11 +256,11 @@ void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
                 if (p_last) __builtin_amdgcn_raw_buffer_store_b128(bx, region, o_last, 0, 0);                        \
             } else {          /* sc1: write-through, seen from any XCD */                                            \
                 if (lo == 0) {                                                                                       \
-                    if constexpr (sizeof(T) == 4) __builtin_amdgcn_raw_buffer_store_b64(x2, region, o_part, 0, kClSc1); \
-                    else __builtin_amdgcn_raw_buffer_store_b128(x4, region, o_part, 0, kClSc1);                      \
+                    if constexpr (sizeof(T) == 4) __builtin_amdgcn_raw_buffer_store_b64(x2, region, o_part, 0, kSc1);   \
+                    else __builtin_amdgcn_raw_buffer_store_b128(x4, region, o_part, 0, kSc1);                        \
                 }                                                                                                    \
-                if (p_first) __builtin_amdgcn_raw_buffer_store_b128(bx, region, o_first, 0, kClSc1);                 \
-                if (p_last) __builtin_amdgcn_raw_buffer_store_b128(bx, region, o_last, 0, kClSc1);                   \
+                if (p_first) __builtin_amdgcn_raw_buffer_store_b128(bx, region, o_first, 0, kSc1);                   \
+                if (p_last) __builtin_amdgcn_raw_buffer_store_b128(bx, region, o_last, 0, kSc1);                     \
             }                                                                                                        \
         }                                                                                                            \
         if constexpr (ONE) wg_barrier();                                                                             \
@@ -288,7 +284,7 @@ void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
             if (HIDX != 0xffffffffu) {                                                                               \
                 _Pragma("unroll") for (int j_ = 0; j_ < V; ++j_) HV[j_] = (HWIN)[HIDX + j_];                         \
             }                                                                                                        \
-            cl_u32x4 got = {0u, 0u, 0u, 0u};                                                                         \
+            u32x4 got = {0u, 0u, 0u, 0u};                                                                            \
             OK = true;                                                                                               \
             if constexpr (ONE) {                                                                                     \
                 got = lpart[lo < PPM ? lo : 0u];                                                                     \
@@ -297,7 +293,7 @@ void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
             for (uint32_t spins = 0;; ++spins) {                                                                     \
                 asm volatile("" ::: "memory");   /* the poll is re-issued on every pass */                           \
                 if (!have) {   /* only the lanes that still miss their piece load again */                           \
-                    got = __builtin_amdgcn_raw_buffer_load_b128(region, (int)(par_off + poll_off), 0, kClSc1);       \
+                    got = __builtin_amdgcn_raw_buffer_load_b128(region, (int)(par_off + poll_off), 0, kSc1);         \
                     have = got.y == tag && got.w == tag;                                                             \
                 }                                                                                                    \
                 if (__all(have)) break;                                                                              \
@@ -362,20 +358,20 @@ void pcg_cluster_kernel(PcgArgs<T> a, unsigned char *ws, uint32_t H, uint32_t C,
     if (any) {
         // this workgroup's slot, both parities, cleared by the lanes that will publish into the same words (a wave's stores
         // to one address arrive in order): tag 0 is nobody's
-        const cl_u32x2 z2 = {0u, 0u};
-        const cl_u32x4 z4 = {0u, 0u, 0u, 0u};
+        const u32x2 z2 = {0u, 0u};
+        const u32x4 z4 = {0u, 0u, 0u, 0u};
         uint32_t lo = lane;
         asm volatile("" : "+v"(lo));
 #pragma unroll
         for (uint32_t par = 0; par < 2; ++par) {
             const uint32_t o = par * par_stride + my_slot;
             if (lo == 0) {
-                if constexpr (sizeof(T) == 4) __builtin_amdgcn_raw_buffer_store_b64(z2, region, (int)(o + wave * 8), 0, kClSc1);
-                else __builtin_amdgcn_raw_buffer_store_b128(z4, region, (int)(o + wave * 16), 0, kClSc1);
+                if constexpr (sizeof(T) == 4) __builtin_amdgcn_raw_buffer_store_b64(z2, region, (int)(o + wave * 8), 0, kSc1);
+                else __builtin_amdgcn_raw_buffer_store_b128(z4, region, (int)(o + wave * 16), 0, kSc1);
             }
-            if (wave == 0 && has_left && lo < LPB) __builtin_amdgcn_raw_buffer_store_b128(z4, region, (int)(o + kClFirstOff + lo * 16), 0, kClSc1);
+            if (wave == 0 && has_left && lo < LPB) __builtin_amdgcn_raw_buffer_store_b128(z4, region, (int)(o + kClFirstOff + lo * 16), 0, kSc1);
             if (wave == wl && has_right && lo - lb * LPB < LPB)
-                __builtin_amdgcn_raw_buffer_store_b128(z4, region, (int)(o + kClLastOff + (lo - lb * LPB) * 16), 0, kClSc1);
+                __builtin_amdgcn_raw_buffer_store_b128(z4, region, (int)(o + kClLastOff + (lo - lb * LPB) * 16), 0, kSc1);
         }
     }
     if (any) for (uint32_t prob = c; prob < a.batch; prob += clusters) {
@@ -800,7 +796,8 @@ bool launch_pcg_cluster(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t 
     const double epochs = 2.0 + (double)rounds * (2.0 * a.max_iter + 4.0);
     if (epochs >= (double)(1u << kClEpochBits)) return false;
     const uint32_t C = (a.N + H - 1) / H;
-    uint32_t spin_limit = 1u << 21;      // polls before a hand-off is given up (~1 us per poll: about two seconds)
+    uint32_t spin_limit = 1u << 21;      // polls before a hand-off is given up (~1 us per poll: about two seconds per bound; a member
+                                         // that arrives late spins its own bound after the others': up to two bounds, then the streaming solve)
     uint32_t drop_block = 0xffffffffu;
 #ifdef GBDPCG_TEST_HOOKS
     // variants/libgbdpcg_hooks.so only (tests/test_gpu_cluster.py): a short bound, and a workgroup that never publishes

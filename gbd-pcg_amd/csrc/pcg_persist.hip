@@ -1,5 +1,6 @@
 // pcg_persist.hip -- PCG for ONE large problem spread over many CUs inside a single persistent launch: the host side, and
-// the kernels of the first group of block sizes.  The kernels themselves (and what they do) are in pcg_persist_kernels.hpp;
+// the kernels of the first group of block sizes.  The kernels themselves are in the headers behind pcg_persist_kernels.hpp
+// (protocol: pcg_persist_handoff.hpp; lane map and shared steps: pcg_persist_geom.hpp; pcg_persist_2r.hpp, pcg_persist_1r.hpp);
 // their instantiations -- 20 kernels per block size, the longest compile of the library -- are spread over three units that
 // build side by side: this one (stateSize 14 - 20), pcg_persist_b.hip (22 - 28) and pcg_persist_c.hip (30 - 36).
 #include "pcg_persist_kernels.hpp"
@@ -8,20 +9,9 @@ namespace gbdpcg {
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 
-// Block sizes with persistent kernels, by the unit that holds them: BASELINE's 14 and 36 and every even size in between (one
-// problem of any other size takes the split path, whose hipGraph is 2 max_iter + 4 launches whatever the iteration count).
-#define GBDPCG_PERSIST_N_A(X) X(14) X(16) X(18) X(20)
-#define GBDPCG_PERSIST_N_B(X) X(22) X(24) X(26) X(28)
-#define GBDPCG_PERSIST_N_C(X) X(30) X(32) X(34) X(36)
-#define GBDPCG_PERSIST_N(X) GBDPCG_PERSIST_N_A(X) GBDPCG_PERSIST_N_B(X) GBDPCG_PERSIST_N_C(X)
-
 template <typename T> static bool persist_has_kernel(uint32_t n)
 {
-#define GBDPCG_CASE(NN) \
-    if (n == NN) return true;
-    GBDPCG_PERSIST_N(GBDPCG_CASE)
-#undef GBDPCG_CASE
-    return false;
+    return PersistGroup<0>::has(n) || PersistGroup<1>::has(n) || PersistGroup<2>::has(n);
 }
 
 // Knots per workgroup for this launch (0: the shape cannot run persistently): every workgroup must be resident at
@@ -58,18 +48,9 @@ hipError_t launch_pcg_persist(const DeviceInfo &dev, const PcgArgs<T> &a, void *
 {
     const uint32_t K = persist_knots_per_wg<T>(dev, a.n, a.N, a.batch, one_reduction);
     if (K == 0 || workspace == nullptr) return hipErrorInvalidValue;
-#define GBDPCG_CASE(NN) \
-    if (a.n == NN) return launch_persist_n<T, NN>(a, workspace, s, one_reduction, K);
-    GBDPCG_PERSIST_N_A(GBDPCG_CASE)
-#undef GBDPCG_CASE
-#define GBDPCG_CASE(NN) \
-    if (a.n == NN) return launch_pcg_persist_b<T>(a, workspace, s, one_reduction, K);
-    GBDPCG_PERSIST_N_B(GBDPCG_CASE)
-#undef GBDPCG_CASE
-#define GBDPCG_CASE(NN) \
-    if (a.n == NN) return launch_pcg_persist_c<T>(a, workspace, s, one_reduction, K);
-    GBDPCG_PERSIST_N_C(GBDPCG_CASE)
-#undef GBDPCG_CASE
+    if (PersistGroup<0>::has(a.n)) return launch_pcg_persist_group<T, 0>(a, workspace, s, one_reduction, K);
+    if (PersistGroup<1>::has(a.n)) return launch_pcg_persist_group<T, 1>(a, workspace, s, one_reduction, K);
+    if (PersistGroup<2>::has(a.n)) return launch_pcg_persist_group<T, 2>(a, workspace, s, one_reduction, K);
     return hipErrorInvalidValue;
 }
 
@@ -81,5 +62,6 @@ template size_t persist_rescue_bytes<float>(uint32_t, uint32_t, uint32_t);
 template size_t persist_rescue_bytes<double>(uint32_t, uint32_t, uint32_t);
 template hipError_t launch_pcg_persist<float>(const DeviceInfo &, const PcgArgs<float> &, void *, hipStream_t, bool);
 template hipError_t launch_pcg_persist<double>(const DeviceInfo &, const PcgArgs<double> &, void *, hipStream_t, bool);
+GBDPCG_PERSIST_GROUP(, 0)
 
 }  // namespace gbdpcg

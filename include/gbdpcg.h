@@ -58,10 +58,11 @@ typedef enum gbdpcg_path {
     GBDPCG_PATH_PERSISTENT = 3, /* one large problem over many CUs in ONE launch: block-rows register-resident for the
                                   whole solve (the reference's layout, pcg.cuh:104-110), two in-kernel all-gathers of
                                   {partial inner product, boundary knots} per iteration instead of 4 grid.sync().  Wants
-                                  every workgroup resident at once (ceil(N/K) * batch <= CU count, K <= 4).  The
+                                  every workgroup resident at once (ceil(N/K) * batch <= CU count, K = 2, 3 or 1).  The
                                   reference refuses a launch that cannot be co-resident before it starts
                                   (checkPcgOccupancy, pcg.cuh:23-49); here, if another kernel holds compute units for
-                                  about two seconds, the workgroups give up after a bounded spin WITHOUT having written
+                                  about two seconds (up to twice that when a workgroup arrives late, plus the streaming
+                                  solve), the workgroups give up after a bounded spin WITHOUT having written
                                   anything, and the one that leaves last solves the problem alone inside the same launch
                                   (streaming kernel: slow, correct).  The caller always gets a solved problem; on a
                                   device shared with long-running kernels GBDPCG_PATH_SPLIT avoids the wait. */
