@@ -63,6 +63,8 @@ SYMBOLS = [
     "gbdpcg_graph_create_kkt_backward_shared_f32", "gbdpcg_graph_create_kkt_backward_shared_f64",
     "gbdpcg_demote_f32", "gbdpcg_kkt_defect_mixed", "gbdpcg_kkt_refine_apply", "gbdpcg_kkt_refine_step",
     "gbdpcg_graph_create_kkt_refine_step",
+    "gbdpcg_kkt_defect_mixed_reg", "gbdpcg_kkt_defect_mixed_shared", "gbdpcg_kkt_refine_step_reg", "gbdpcg_kkt_refine_step_shared",
+    "gbdpcg_graph_create_kkt_refine_step_reg", "gbdpcg_graph_create_kkt_refine_step_shared",
     "gbdpcg_csr_to_bt_f32", "gbdpcg_csr_to_bt_f64", "gbdpcg_version",
 ]
 
@@ -121,12 +123,15 @@ def _resolve_argtypes(lib):
     # mixed-precision refinement (no suffix: fp64 data and point, fp32 solve)
     head = [vp, u32, u32, u32, u32, vp, vp, vp, vp]                # h, nx, nu, N, batch, G, C, g, c (fp64)
     lib.gbdpcg_demote_f32.argtypes = [vp, ctypes.c_uint64, vp, vp, vp]                    # h, count, src, dst, stream
-    lib.gbdpcg_kkt_defect_mixed.argtypes = head + [vp, vp, vp, vp, vp, vp, vp, vp]        # z, lambda | rg, rc, dlambda, expo, res | stream
+    # the defect: head | z, lambda | rg, rc, dlambda, expo, res | stream
     lib.gbdpcg_kkt_refine_apply.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp]   # dz, dlambda, expo | z, lambda | stream
     # Ginv32, C32, S32, Pinv32 | rg, rc, gamma, dlambda, r, p, dz | tol, max_iter, iters, flags | expo, z, lambda, res
-    step = head + [vp] * 4 + [vp] * 7 + [ctypes.c_float, u32, vp, vp] + [vp] * 4
-    lib.gbdpcg_kkt_refine_step.argtypes = step + [vp]
-    lib.gbdpcg_graph_create_kkt_refine_step.argtypes = step + [ctypes.POINTER(vp)]
+    tail = [vp] * 4 + [vp] * 7 + [ctypes.c_float, u32, vp, vp] + [vp] * 4
+    # the _shared forms: the same argument lists; the _reg forms: rho (fp64, [batch]) directly behind c
+    for name, hd in (("", head), ("_shared", head), ("_reg", head + [vp])):
+        getattr(lib, f"gbdpcg_kkt_defect_mixed{name}").argtypes = hd + [vp, vp, vp, vp, vp, vp, vp, vp]
+        getattr(lib, f"gbdpcg_kkt_refine_step{name}").argtypes = hd + tail + [vp]
+        getattr(lib, f"gbdpcg_graph_create_kkt_refine_step{name}").argtypes = hd + tail + [ctypes.POINTER(vp)]
 
 
 _lib = None
@@ -945,10 +950,35 @@ class Solver:
         assert expo is None or (expo.is_cuda and expo.is_contiguous() and expo.dtype == torch.int32 and expo.numel() == batch)
         assert res is None or (res.is_cuda and res.is_contiguous() and res.dtype == torch.float64 and res.numel() == 2 * batch)
 
+    @staticmethod
+    def _rho_args(batch, rho, reg):
+        """The arguments that stand directly behind c: rho ([batch], fp64) in the _reg forms, nothing otherwise."""
+        import torch
+        if not reg:
+            return ()
+        assert rho is None or (rho.is_cuda and rho.is_contiguous() and rho.dtype == torch.float64 and rho.numel() == batch)
+        return (_p(rho),)
+
     def kkt_defect_mixed(self, nx, nu, N, batch, G, C, g, c, z, lam, rg=None, rc=None, dlam=None, expo=None, res=None, stream=None,
                          zero_dlam=True):
         """gbdpcg_kkt_defect_mixed: the fp64 defect of (z, lam) as the scaled fp32 right-hand side of the correction system.
         Returns (rg, rc, dlam, expo, res [batch, 2]); zero_dlam=False passes NULL for dlam."""
+        return self._kkt_defect_mixed("kkt_defect_mixed", nx, nu, N, batch, G, C, g, c, None, False, z, lam, rg, rc, dlam, expo, res,
+                                      stream, zero_dlam)
+
+    def kkt_defect_mixed_reg(self, nx, nu, N, batch, G, C, g, c, rho, z, lam, rg=None, rc=None, dlam=None, expo=None, res=None,
+                             stream=None, zero_dlam=True):
+        """gbdpcg_kkt_defect_mixed_reg: the defect of (G_b + rho_b I) z + g + C' lam; rho [batch], fp64, on the device."""
+        return self._kkt_defect_mixed("kkt_defect_mixed_reg", nx, nu, N, batch, G, C, g, c, rho, True, z, lam, rg, rc, dlam, expo, res,
+                                      stream, zero_dlam)
+
+    def kkt_defect_mixed_shared(self, nx, nu, N, batch, G, C, g, c, z, lam, rg=None, rc=None, dlam=None, expo=None, res=None,
+                                stream=None, zero_dlam=True):
+        """gbdpcg_kkt_defect_mixed_shared: ONE problem's G and C for the whole batch; everything else per problem."""
+        return self._kkt_defect_mixed("kkt_defect_mixed_shared", nx, nu, N, batch, G, C, g, c, None, False, z, lam, rg, rc, dlam, expo,
+                                      res, stream, zero_dlam)
+
+    def _kkt_defect_mixed(self, name, nx, nu, N, batch, G, C, g, c, rho, reg, z, lam, rg, rc, dlam, expo, res, stream, zero_dlam):
         import torch
         if rg is None:
             rg = torch.empty(batch * ((nx + nu) * N - nu), dtype=torch.float32, device=G.device)
@@ -961,8 +991,9 @@ class Solver:
         if res is None:
             res = torch.empty(batch, 2, dtype=torch.float64, device=G.device)
         self._refine_check(nx, nu, N, batch, (G, C, g, c, z, lam), (rg,), (rc, dlam), expo, res)
-        self._check(self.lib.gbdpcg_kkt_defect_mixed(self.h, nx, nu, N, batch, _p(G), _p(C), _p(g), _p(c), _p(z), _p(lam), _p(rg),
-                                                     _p(rc), _p(dlam), _p(expo), _p(res), self._stream(stream)), "kkt_defect_mixed")
+        fn = getattr(self.lib, "gbdpcg_" + name)
+        self._check(fn(self.h, nx, nu, N, batch, _p(G), _p(C), _p(g), _p(c), *self._rho_args(batch, rho, reg), _p(z), _p(lam), _p(rg),
+                       _p(rc), _p(dlam), _p(expo), _p(res), self._stream(stream)), name)
         return rg, rc, dlam, expo, res.view(batch, 2)
 
     def kkt_refine_apply(self, nx, nu, N, batch, dz, dlam, expo, z, lam, stream=None):
@@ -973,9 +1004,10 @@ class Solver:
         return z, lam
 
     def _refine_step_args(self, nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, rg, rc, gamma, dlam, r, p, dz, tol, max_iter,
-                          iters, mie, expo, z, lam, res):
+                          iters, mie, expo, z, lam, res, rho=None, reg=False):
         self._refine_check(nx, nu, N, batch, (G, C, g, c, z, lam), (rg, dz), (rc, gamma, dlam, r, p), expo, res)
-        return (self.h, nx, nu, N, batch, _p(G), _p(C), _p(g), _p(c), _p(Ginv32), _p(C32), _p(S32), _p(Pinv32), _p(rg), _p(rc),
+        return (self.h, nx, nu, N, batch, _p(G), _p(C), _p(g), _p(c), *self._rho_args(batch, rho, reg), _p(Ginv32), _p(C32), _p(S32),
+                _p(Pinv32), _p(rg), _p(rc),
                 _p(gamma), _p(dlam), _p(r), _p(p), _p(dz), tol, max_iter, _p(iters), _p(mie), _p(expo), _p(z), _p(lam), _p(res))
 
     def refine_work(self, nx, nu, N, batch, device="cuda"):
@@ -1009,10 +1041,51 @@ class Solver:
         return Graph(self, gr, keep=(G, C, g, c, Ginv32, C32, S32, Pinv32, rg, rc, gamma, dlam, r, p, dz, iters, max_iter_exit, expo,
                                      z, lam, res))
 
+    def kkt_refine_step_reg(self, nx, nu, N, batch, G, C, g, c, rho, Ginv32, C32, S32, Pinv32, z, lam, *, rg, rc, gamma, dlam, r, p, dz,
+                            iters, max_iter_exit, expo, res, tol=1e-4, max_iter=50, stream=None):
+        """gbdpcg_kkt_refine_step_reg: the step towards the solution of the system with G_b + rho_b I; the kept factorisation is
+        that of kkt_step_reg (fp32) with the demoted rho."""
+        args = self._refine_step_args(nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, rg, rc, gamma, dlam, r, p, dz, tol,
+                                      max_iter, iters, max_iter_exit, expo, z, lam, res, rho, True)
+        self._check(self.lib.gbdpcg_kkt_refine_step_reg(*args, self._stream(stream)), "kkt_refine_step_reg")
+        return res.view(batch, 2)
+
+    def kkt_refine_step_shared(self, nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, z, lam, *, rg, rc, gamma, dlam, r, p, dz,
+                               iters, max_iter_exit, expo, res, tol=1e-4, max_iter=50, stream=None):
+        """gbdpcg_kkt_refine_step_shared: ONE G, C, Ginv32, C32, S32, Pinv32 for the whole batch (the solve: kkt_resolve_shared)."""
+        args = self._refine_step_args(nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, rg, rc, gamma, dlam, r, p, dz, tol,
+                                      max_iter, iters, max_iter_exit, expo, z, lam, res)
+        self._check(self.lib.gbdpcg_kkt_refine_step_shared(*args, self._stream(stream)), "kkt_refine_step_shared")
+        return res.view(batch, 2)
+
+    def graph_kkt_refine_step_reg(self, nx, nu, N, batch, G, C, g, c, rho, Ginv32, C32, S32, Pinv32, z, lam, *, rg, rc, gamma, dlam, r,
+                                  p, dz, iters, max_iter_exit, expo, res, tol=1e-4, max_iter=50):
+        """Capture one regularised refinement step into a hipGraph (gbdpcg_graph_create_kkt_refine_step_reg); the graph keeps the
+        pointer of rho: rewrite it in place between replays."""
+        args = self._refine_step_args(nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, rg, rc, gamma, dlam, r, p, dz, tol,
+                                      max_iter, iters, max_iter_exit, expo, z, lam, res, rho, True)
+        gr = ctypes.c_void_p()
+        self._check(self.lib.gbdpcg_graph_create_kkt_refine_step_reg(*args, ctypes.byref(gr)), "graph_create_kkt_refine_step_reg")
+        return Graph(self, gr, keep=(G, C, g, c, rho, Ginv32, C32, S32, Pinv32, rg, rc, gamma, dlam, r, p, dz, iters, max_iter_exit,
+                                     expo, z, lam, res))
+
+    def graph_kkt_refine_step_shared(self, nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, z, lam, *, rg, rc, gamma, dlam, r,
+                                     p, dz, iters, max_iter_exit, expo, res, tol=1e-4, max_iter=50):
+        """Capture one shared-matrix refinement step into a hipGraph (gbdpcg_graph_create_kkt_refine_step_shared)."""
+        args = self._refine_step_args(nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, rg, rc, gamma, dlam, r, p, dz, tol,
+                                      max_iter, iters, max_iter_exit, expo, z, lam, res)
+        gr = ctypes.c_void_p()
+        self._check(self.lib.gbdpcg_graph_create_kkt_refine_step_shared(*args, ctypes.byref(gr)),
+                    "graph_create_kkt_refine_step_shared")
+        return Graph(self, gr, keep=(G, C, g, c, Ginv32, C32, S32, Pinv32, rg, rc, gamma, dlam, r, p, dz, iters, max_iter_exit, expo,
+                                     z, lam, res))
+
     def kkt_solve_refined(self, nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, z=None, lam=None, max_steps=12, stop_s=0.0,
-                          stop_f=0.0, tol=1e-4, max_iter=50, work=None):
+                          stop_f=0.0, tol=1e-4, max_iter=50, work=None, rho=None, shared=False):
         """Replay the refinement step from (z, lam) (zeros when not given) until every problem has stationarity <= stop_s and
         feasibility <= stop_f (scalars or [batch] arrays) or max_steps steps have run; res is read back between steps.
+        rho ([batch], fp64): the _reg step, on the system with G_b + rho_b I; shared: the _shared step, one problem's matrices.
+        Both together are refused, as by the library (write G + rho I into the one G).
         Returns (z, lam, history): history[i] is the [batch, 2] numpy array of the norms of the point step i started from; when
         the loop stops on the norms, the last entry belongs to the point in front of the last step."""
         import torch
@@ -1021,8 +1094,14 @@ class Solver:
         if lam is None:
             lam = torch.zeros(batch * nx * N, dtype=torch.float64, device=G.device)
         work = work or self.refine_work(nx, nu, N, batch, G.device)
-        graph = self.graph_kkt_refine_step(nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, z, lam, tol=tol, max_iter=max_iter,
-                                           **work)
+        if rho is not None and shared:
+            raise ValueError("kkt_solve_refined: rho and shared together are not provided")
+        if rho is not None:
+            graph = self.graph_kkt_refine_step_reg(nx, nu, N, batch, G, C, g, c, rho, Ginv32, C32, S32, Pinv32, z, lam, tol=tol,
+                                                   max_iter=max_iter, **work)
+        else:
+            make = self.graph_kkt_refine_step_shared if shared else self.graph_kkt_refine_step
+            graph = make(nx, nu, N, batch, G, C, g, c, Ginv32, C32, S32, Pinv32, z, lam, tol=tol, max_iter=max_iter, **work)
         history = []
         try:
             for _ in range(max_steps):

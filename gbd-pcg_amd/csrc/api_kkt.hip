@@ -311,11 +311,15 @@ gbdpcg_status kkt_backward_impl(gbdpcg_handle_t h, const KktOperands<T> &k, cons
 // ---- mixed-precision refinement (kkt_refine.hip): fp64 problem data and point, an fp32 solve on a kept fp32 factorisation
 // The fp64 side of a refinement step: the problem, the point that is refined, and what the defect launch writes next to the
 // right-hand side.  The fp32 side is a KktOperands<float> (g := rg, c := rc, z := dz) and the PcgArgs<float> of its solve.
+// reg (gbdpcg_kkt_*_reg): the defect of G_b + rho_b I, rho [batch] fp64 on the device.  The shared forms set k.shared of the fp32
+// side: G and C here are then one problem's too.
 struct RefineOperands {
     const double *G, *C, *g, *c;
     double *z, *lambda, *res;
     int32_t *expo;
     float *rg, *rc;   // the right-hand side of the correction system: the g and the c of the fp32 side
+    const double *rho = nullptr;
+    bool reg = false;
 };
 
 // What the fp64 launches refuse: the rules of gbdpcg_kkt_residual_f64.
@@ -327,15 +331,16 @@ gbdpcg_status refine_shape_status(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, u
 
 gbdpcg_status kkt_defect_mixed_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_G,
                                     const double *d_C, const double *d_g, const double *d_c, const double *d_z, const double *d_lambda,
-                                    float *d_rg, float *d_rc, float *d_dlambda, int32_t *d_expo, double *d_res, void *stream)
+                                    float *d_rg, float *d_rc, float *d_dlambda, int32_t *d_expo, double *d_res, void *stream,
+                                    bool shared = false, const double *d_rho = nullptr, bool reg = false)
 {
-    if (!h || !d_G || !d_g || !d_c || !d_z || !d_lambda || !d_rg || !d_rc || !d_expo || !d_res || (!d_C && N > 1))
+    if (!h || !d_G || !d_g || !d_c || !d_z || !d_lambda || !d_rg || !d_rc || !d_expo || !d_res || (!d_C && N > 1) || (reg && !d_rho))
         return GBDPCG_ERR_INVALID;
     const gbdpcg_status st = refine_shape_status(h, nx, nu, N, batch);
     if (st != GBDPCG_OK) return st;
     DEVICE_SCOPE(h);
     HIP_TRY(h, launch_kkt_defect_mixed(h->dev, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_rg, d_rc, d_dlambda, d_expo, d_res,
-                                       (hipStream_t)stream));
+                                       (hipStream_t)stream, shared, reg ? d_rho : nullptr));
     return GBDPCG_OK;
 }
 
@@ -351,17 +356,18 @@ gbdpcg_status kkt_refine_apply_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu,
 }
 
 // What gbdpcg_kkt_refine_step refuses before anything is written, reserved or captured: whatever one of its three parts would
-// refuse, every INVALID before every UNSUPPORTED.  solve_limits: as in admm_step_refusal.
+// refuse, every INVALID before every UNSUPPORTED.  solve_limits: as in admm_step_refusal.  The _reg and _shared forms come here too:
+// a null rho where f.reg asks for one, and the one-workgroup limit of the shared solve.
 gbdpcg_status refine_step_refusal(gbdpcg_handle_t h, const RefineOperands &f, const KktOperands<float> &k, const PcgArgs<float> &a,
                                   bool solve_limits)
 {
     if (!h || !f.G || !f.g || !f.c || !f.z || !f.lambda || !f.expo || !f.res || (!f.C && a.N > 1) || !k.Ginv || !k.g || !k.c ||
-        !k.gamma || !k.z || (!k.C && a.N > 1) || !a.S || !a.lambda || !a.iters)
+        !k.gamma || !k.z || (!k.C && a.N > 1) || !a.S || !a.lambda || !a.iters || (f.reg && !f.rho))
         return GBDPCG_ERR_INVALID;
     gbdpcg_status st = refine_shape_status(h, a.n, k.nu, a.N, a.batch);
     if (st != GBDPCG_OK) return st;
     if (!schur_shape_ok<float>(h->dev, a.n, k.nu)) return GBDPCG_ERR_UNSUPPORTED;
-    if (solve_limits && !mappable<float>(a.n)) return GBDPCG_ERR_UNSUPPORTED;
+    if (solve_limits && (!mappable<float>(a.n) || (k.shared && !fused_fits<float>(h->dev, a.n, a.N)))) return GBDPCG_ERR_UNSUPPORTED;
     return GBDPCG_OK;
 }
 
@@ -372,7 +378,8 @@ gbdpcg_status kkt_refine_step_impl(gbdpcg_handle_t h, const RefineOperands &f, c
 {
     gbdpcg_status st = refine_step_refusal(h, f, k, a, true);
     if (st != GBDPCG_OK) return st;
-    st = kkt_defect_mixed_impl(h, a.n, k.nu, a.N, a.batch, f.G, f.C, f.g, f.c, f.z, f.lambda, f.rg, f.rc, a.lambda, f.expo, f.res, stream);
+    st = kkt_defect_mixed_impl(h, a.n, k.nu, a.N, a.batch, f.G, f.C, f.g, f.c, f.z, f.lambda, f.rg, f.rc, a.lambda, f.expo, f.res, stream,
+                               k.shared, f.rho, f.reg);
     if (st != GBDPCG_OK) return st;
     st = kkt_resolve_impl<float>(h, k, a, stream);
     if (st != GBDPCG_OK) return st;
@@ -639,32 +646,55 @@ gbdpcg_status gbdpcg_kkt_refine_apply(gbdpcg_handle_t h, uint32_t nx, uint32_t n
 {
     return kkt_refine_apply_impl(h, nx, nu, N, batch, d_dz, d_dlambda, d_expo, d_z, d_lambda, stream);
 }
-#define REFINE_PARAMS                                                                                                               \
+// The _reg forms take d_rho directly behind d_c, the _shared forms the argument list of the plain ones.
+gbdpcg_status gbdpcg_kkt_defect_mixed_reg(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_G,
+                                          const double *d_C, const double *d_g, const double *d_c, const double *d_rho,
+                                          const double *d_z, const double *d_lambda, float *d_rg, float *d_rc, float *d_dlambda,
+                                          int32_t *d_expo, double *d_res, void *stream)
+{
+    return kkt_defect_mixed_impl(h, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_rg, d_rc, d_dlambda, d_expo, d_res, stream,
+                                 false, d_rho, true);
+}
+gbdpcg_status gbdpcg_kkt_defect_mixed_shared(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                             const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                             const double *d_z, const double *d_lambda, float *d_rg, float *d_rc, float *d_dlambda,
+                                             int32_t *d_expo, double *d_res, void *stream)
+{
+    return kkt_defect_mixed_impl(h, nx, nu, N, batch, d_G, d_C, d_g, d_c, d_z, d_lambda, d_rg, d_rc, d_dlambda, d_expo, d_res, stream,
+                                 true);
+}
+#define REFINE_TAIL                                                                                                                 \
+    const float *d_Ginv32, const float *d_C32, const float *d_S32, const float *d_Pinv32, float *d_rg, float *d_rc, float *d_gamma, \
+        float *d_dlambda, float *d_r, float *d_p, float *d_dz, float tol, uint32_t max_iter, uint32_t *d_iters,                     \
+        uint8_t *d_max_iter_exit, int32_t *d_expo, double *d_z, double *d_lambda, double *d_res
+#define REFINE_PARAMS(TYPE)                                                                                                         \
     gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_G, const double *d_C,                  \
-        const double *d_g, const double *d_c, const float *d_Ginv32, const float *d_C32, const float *d_S32,                        \
-        const float *d_Pinv32, float *d_rg, float *d_rc, float *d_gamma, float *d_dlambda, float *d_r, float *d_p, float *d_dz,     \
-        float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, int32_t *d_expo, double *d_z, double *d_lambda,  \
-        double *d_res
-#define REFINE_SETUP                                                                                                                \
-    const RefineOperands f{d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, d_expo, d_rg, d_rc};                                           \
-    const KktOperands<float> k{nu, d_Ginv32, d_C32, d_rg, d_rc, d_gamma, d_dz};                                                     \
+        const double *d_g, const double *d_c, REFINE_TAIL
+#define REFINE_REG_PARAMS(TYPE)                                                                                                     \
+    gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_G, const double *d_C,                  \
+        const double *d_g, const double *d_c, const double *d_rho, REFINE_TAIL
+#define REFINE_SETUP_OF(SHARED, RHO, REG)                                                                                           \
+    const RefineOperands f{d_G, d_C, d_g, d_c, d_z, d_lambda, d_res, d_expo, d_rg, d_rc, RHO, REG};                                 \
+    const KktOperands<float> k{nu, d_Ginv32, d_C32, d_rg, d_rc, d_gamma, d_dz, SHARED};                                             \
     const PcgArgs<float> a =                                                                                                        \
         pcg_args<float>(nx, N, batch, d_S32, d_Pinv32, d_gamma, d_dlambda, d_r, d_p, tol, max_iter, d_iters, d_max_iter_exit);      \
     auto body = [&](hipStream_t s) { return kkt_refine_step_impl(h, f, k, a, s); };
-gbdpcg_status gbdpcg_kkt_refine_step(REFINE_PARAMS, void *stream)
-{
-    REFINE_SETUP
-    return body((hipStream_t)stream);
-}
-gbdpcg_status gbdpcg_graph_create_kkt_refine_step(REFINE_PARAMS, gbdpcg_graph_t *out)
-{
-    REFINE_SETUP
-    if (!out) return GBDPCG_ERR_INVALID;
-    *out = nullptr;
+#define REFINE_SETUP(TYPE, SHARED) REFINE_SETUP_OF(SHARED, nullptr, false)
+#define REFINE_REG_SETUP(TYPE, SHARED) REFINE_SETUP_OF(SHARED, d_rho, true)
+#define REFINE_REFUSE(TYPE)                                                                                                         \
+    if (!out) return GBDPCG_ERR_INVALID;                                                                                            \
+    *out = nullptr;                                                                                                                 \
     if (const gbdpcg_status st = refine_step_refusal(h, f, k, a, false)) return st;
-    return graph_create<float>(h, a, false, out, body);
-}
+// (GBDPCG_PAIR names its entries NAME_SUF: the step has no precision suffix, so its last word stands in that place)
+GBDPCG_PAIR(kkt_refine, step, float, false, REFINE_PARAMS, REFINE_SETUP, REFINE_REFUSE)
+GBDPCG_PAIR(kkt_refine_step, reg, float, false, REFINE_REG_PARAMS, REFINE_REG_SETUP, REFINE_REFUSE)
+GBDPCG_PAIR(kkt_refine_step, shared, float, true, REFINE_PARAMS, REFINE_SETUP, REFINE_REFUSE)
+#undef REFINE_TAIL
 #undef REFINE_PARAMS
+#undef REFINE_REG_PARAMS
+#undef REFINE_SETUP_OF
 #undef REFINE_SETUP
+#undef REFINE_REG_SETUP
+#undef REFINE_REFUSE
 
 }  // extern "C"

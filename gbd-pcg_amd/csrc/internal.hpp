@@ -297,9 +297,12 @@ hipError_t launch_kkt_grad(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
 //             res[2b], res[2b+1] = the norms launch_kkt_residual<double> writes for the same point
 //     apply:  z += (double)dz 2^-e_b, lambda += (double)dlambda 2^-e_b
 //     demote: dst[i] = fl32(src[i]), i < count
+// defect, shared: G and C are one problem's blocks (zero problem stride); rho != nullptr ([batch]): the defect of G_b + rho_b I,
+// the diagonal entries as fl(d + rho_b); both as in launch_kkt_residual, and both together are hipErrorInvalidValue as there.
 hipError_t launch_kkt_defect_mixed(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *G,
                                    const double *C, const double *g, const double *c, const double *z, const double *lambda, float *rg,
-                                   float *rc, float *dlambda, int32_t *expo, double *res, hipStream_t s);
+                                   float *rc, float *dlambda, int32_t *expo, double *res, hipStream_t s, bool shared = false,
+                                   const double *rho = nullptr);
 hipError_t launch_kkt_refine_apply(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *dz, const float *dlambda,
                                    const int32_t *expo, double *z, double *lambda, hipStream_t s);
 hipError_t launch_demote(const DeviceInfo &dev, uint64_t count, const double *src, float *dst, hipStream_t s);

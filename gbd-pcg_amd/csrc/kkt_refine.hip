@@ -96,11 +96,16 @@ __device__ __forceinline__ void refine_finish(uint64_t ms, uint64_t mf, uint32_t
 }  // namespace
 
 // Any block size: schur_residual_kernel<double> with the vectors written out (one wavefront per row, blocks staged in LDS).
+// SHARED (gbdpcg_kkt_defect_mixed_shared): G and C are ONE problem's blocks, read with a zero problem stride; everything else
+// stays per problem.  REG (gbdpcg_kkt_defect_mixed_reg): Q_k(r,r) and R_k(r,r) are staged as fl(d + rho_b), rho [batch]: the
+// defect of (G + rho I) z + g + C' lambda, every chain behind the staging unchanged (schur_residual.hip, REG).
+template <bool SHARED = false, bool REG = false>
 __global__ __launch_bounds__(256) void kkt_defect_kernel(uint32_t nx, uint32_t nu, uint32_t N, const double *__restrict__ G,
                                                          const double *__restrict__ C, const double *__restrict__ g,
                                                          const double *__restrict__ c, const double *__restrict__ z,
                                                          const double *__restrict__ lambda, float *rg, float *rc, float *dl,
-                                                         int32_t *__restrict__ expo, double *__restrict__ res)
+                                                         int32_t *__restrict__ expo, double *__restrict__ res,
+                                                         const double *__restrict__ rho)   // [batch], REG only
 {
     using T = double;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -110,9 +115,13 @@ __global__ __launch_bounds__(256) void kkt_defect_kernel(uint32_t nx, uint32_t n
     const uint32_t nn = nx * nx, uu = nu * nu, xu = nx * nu, we = residual_wave_elems(nx, nu);
     T *base = reinterpret_cast<T *>(smem_raw);
     T *Q = base + (size_t)wave * we, *A = Q + nn, *R = A + nn, *B = R + uu, *xk = B + xu, *nl = xk + nx, *uk = nl + 2 * nx;
-    const T *Gp = G + prob * d.szG, *Cp = C + prob * d.szC;
+    const uint64_t mprob = SHARED ? 0 : prob;   // the problem whose matrices this workgroup reads
+    const T *Gp = G + mprob * d.szG, *Cp = C + mprob * d.szC;
     const T *gp = g + prob * d.szg, *zp = z + prob * d.szg, *lp = lambda + prob * d.szc, *cp = c + prob * d.szc;
     float *rgp = rg + prob * d.szg, *rcp = rc + prob * d.szc, *dlp = dl ? dl + prob * d.szc : nullptr;
+
+    T rb = T(0);
+    if constexpr (REG) rb = rho[prob];   // (the workgroup's problem: a scalar load)
 
     uint64_t ms = 0, mf = 0;
     for (uint32_t k = wave; k < N; k += waves) {   // (whole waves)
@@ -121,11 +130,19 @@ __global__ __launch_bounds__(256) void kkt_defect_kernel(uint32_t nx, uint32_t n
         const T *lk = lp + (size_t)k * nx, *ck = cp + (size_t)k * nx;
         float *rgk = rgp + (size_t)k * d.sv, *rck = rcp + (size_t)k * nx;
         wave_sync();   // the previous row has read its blocks
-        for (uint32_t i = lane; i < nn; i += 64) Q[i] = Gk[i];
+        if constexpr (REG) {   // (entry i of a column-major m x m block is on the diagonal where i is a multiple of m + 1)
+            for (uint32_t i = lane; i < nn; i += 64) Q[i] = i % (nx + 1) == 0 ? Gk[i] + rb : Gk[i];
+        } else {
+            for (uint32_t i = lane; i < nn; i += 64) Q[i] = Gk[i];
+        }
         for (uint32_t i = lane; i < nx; i += 64) xk[i] = zk[i];
         if (has_next) {
             for (uint32_t i = lane; i < nn; i += 64) A[i] = Ck[i];
-            for (uint32_t i = lane; i < uu; i += 64) R[i] = Gk[nn + i];
+            if constexpr (REG) {
+                for (uint32_t i = lane; i < uu; i += 64) R[i] = i % (nu + 1) == 0 ? Gk[nn + i] + rb : Gk[nn + i];
+            } else {
+                for (uint32_t i = lane; i < uu; i += 64) R[i] = Gk[nn + i];
+            }
             for (uint32_t i = lane; i < xu; i += 64) B[i] = Ck[nn + i];
             for (uint32_t i = lane; i < nx; i += 64) nl[i] = -lk[nx + i];
             for (uint32_t i = lane; i < nu; i += 64) uk[i] = zk[nx + i];
@@ -169,12 +186,13 @@ __global__ __launch_bounds__(256) void kkt_defect_kernel(uint32_t nx, uint32_t n
 // Compile-time block sizes: schur_residual_quad_kernel<double, NX, NU> with the vectors written out -- four rows per wavefront,
 // one per 16-lane quarter, operands from memory straight into registers; lane l of a quarter owns entry l of its knot's vectors
 // and stores it (the lanes past NX, past NU in the u-part, repeat lane 0's entry for the maxima and store nothing).
-template <int NX, int NU>
+// SHARED, REG: as above; REG is the select per element of schur_residual_quad_kernel on the lane that holds the row.
+template <int NX, int NU, bool SHARED = false, bool REG = false>
 __global__ __launch_bounds__(256) void kkt_defect_quad_kernel(uint32_t N, const double *__restrict__ G, const double *__restrict__ C,
                                                               const double *__restrict__ g, const double *__restrict__ c,
                                                               const double *__restrict__ z, const double *__restrict__ lambda,
                                                               float *rg, float *rc, float *dl, int32_t *__restrict__ expo,
-                                                              double *__restrict__ res)
+                                                              double *__restrict__ res, const double *__restrict__ rho)
 {
     static_assert(NX <= 16 && NU <= NX, "one row per 16-lane quarter");
     using T = double;
@@ -184,9 +202,12 @@ __global__ __launch_bounds__(256) void kkt_defect_quad_kernel(uint32_t N, const 
     const uint64_t prob = blockIdx.x;
     const KktDims d(NX, NU, N);
     const uint32_t cx = l < NX ? l : 0u, cu = l < NU ? l : 0u;   // clamped: idle lanes read what a live lane reads
-    const T *Gp = G + prob * d.szG, *Cp = C + prob * d.szC;
+    const uint64_t mprob = SHARED ? 0 : prob;
+    const T *Gp = G + mprob * d.szG, *Cp = C + mprob * d.szC;
     const T *gp = g + prob * d.szg, *zp = z + prob * d.szg, *lp = lambda + prob * d.szc, *cp = c + prob * d.szc;
     float *rgp = rg + prob * d.szg, *rcp = rc + prob * d.szc, *dlp = dl ? dl + prob * d.szc : nullptr;
+    T rb = T(0);
+    if constexpr (REG) rb = rho[prob];   // (the workgroup's problem: a scalar load)
 
     uint64_t ms = 0, mf = 0;
     for (uint32_t k0 = 0; k0 < N; k0 += 16) {   // (the whole workgroup)
@@ -203,6 +224,10 @@ __global__ __launch_bounds__(256) void kkt_defect_quad_kernel(uint32_t N, const 
             sx = gk[cx] + lk[cx];
 #pragma unroll
             for (int q = 0; q < NX; ++q) qr[q] = Gk[q * NX + cx];
+            if constexpr (REG) {
+#pragma unroll
+                for (int q = 0; q < NX; ++q) qr[q] = (uint32_t)q == cx ? qr[q] + rb : qr[q];
+            }
         } else {
 #pragma unroll
             for (int q = 0; q < NX; ++q) qr[q] = T(0);
@@ -223,6 +248,10 @@ __global__ __launch_bounds__(256) void kkt_defect_quad_kernel(uint32_t N, const 
             for (int q = 0; q < NU; ++q) {
                 rr[q] = Gk[NX * NX + q * NU + cu];
                 br[q] = Ck[NX * NX + q * NX + cx];
+            }
+            if constexpr (REG) {
+#pragma unroll
+                for (int q = 0; q < NU; ++q) rr[q] = (uint32_t)q == cu ? rr[q] + rb : rr[q];
             }
         } else {
 #pragma unroll
@@ -300,20 +329,25 @@ __global__ __launch_bounds__(256) void demote_kernel(uint64_t count, uint32_t ve
     for (uint64_t i = body * 4 + tid; i < count; i += threads) dst[i] = (float)src[i];
 }
 
+// rho != nullptr: the REG instantiations; shared: the SHARED ones (as launch_kkt_residual); one workgroup per problem either way.
 hipError_t launch_kkt_defect_mixed(const DeviceInfo &dev, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *G,
                                    const double *C, const double *g, const double *c, const double *z, const double *lambda, float *rg,
-                                   float *rc, float *dlambda, int32_t *expo, double *res, hipStream_t s)
+                                   float *rc, float *dlambda, int32_t *expo, double *res, hipStream_t s, bool shared, const double *rho)
 {
     if (batch > 0x7fffffffu) return hipErrorInvalidValue;   // one workgroup per problem
+    if (shared && rho) return hipErrorInvalidValue;         // (a shared batch has one G: the caller writes G + rho I into it)
     hipError_t st;
     if (quad_dispatch(nx, nu, 0, st, [&](auto NX, auto NU) {
-            hipLaunchKernelGGL((kkt_defect_quad_kernel<NX(), NU()>), dim3(batch), dim3(256), 0, s, N, G, C, g, c, z, lambda, rg, rc, dlambda,
-                               expo, res);
+            auto kern = rho      ? kkt_defect_quad_kernel<NX(), NU(), false, true>
+                        : shared ? kkt_defect_quad_kernel<NX(), NU(), true>
+                                 : kkt_defect_quad_kernel<NX(), NU()>;
+            hipLaunchKernelGGL(kern, dim3(batch), dim3(256), 0, s, N, G, C, g, c, z, lambda, rg, rc, dlambda, expo, res, rho);
             return hipGetLastError();
         }))
         return st;
-    return launch_lds_rows(dev, kkt_defect_kernel, (size_t)residual_wave_elems(nx, nu) * sizeof(double),
-                           [&](uint32_t) { return (uint64_t)batch; }, s, nx, nu, N, G, C, g, c, z, lambda, rg, rc, dlambda, expo, res);
+    auto kern = rho ? kkt_defect_kernel<false, true> : shared ? kkt_defect_kernel<true> : kkt_defect_kernel<>;
+    return launch_lds_rows(dev, kern, (size_t)residual_wave_elems(nx, nu) * sizeof(double), [&](uint32_t) { return (uint64_t)batch; }, s,
+                           nx, nu, N, G, C, g, c, z, lambda, rg, rc, dlambda, expo, res, rho);
 }
 
 hipError_t launch_kkt_refine_apply(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *dz, const float *dlambda,

@@ -7,7 +7,9 @@ At 1024 x (14, 7, 128), fp64 data: windows of K launches between two device even
   * the apply launch,
   * the refine-step graph replay next to the kkt_resolve_f32 and kkt_resolve_f64 graph replays (each resolve from lambda = 0),
   * the refinement from z = lambda = 0 to the fp64 floor -- every problem with m_s <= (2 nx + 2) u mag_s, m_f <= (nx + nu + 2) u mag_f,
-    the bounds of tests/test_gpu_kkt_refine.py -- in steps and in time, next to ONE fp64 kkt_step + kkt_residual_f64 at --tol64.
+    the bounds of tests/test_gpu_kkt_refine.py -- in steps and in time, next to ONE fp64 kkt_step + kkt_residual_f64 at --tol64,
+  * the _reg and the _shared defect launch and step replay next to the plain ones, in the same windows: the ratio reg / plain and
+    shared / plain is what they report (rho_b = 0.3 on the same data; the shared batch is problem 0's plant under every state).
 The magnitudes come from the device: kkt_residual_f64 of (|G|, -|C|, |g|, -|c|, |z|, |lambda|) is max(|G||z| + |g| + |C'||lambda|) and
 max(|C||z| + |c|) row by row.  Small shapes of the GPU test follow with their step counts."""
 import argparse
@@ -148,10 +150,14 @@ def flagship(s, a):
         "apply": lambda: s.kkt_refine_apply(nx, nu, N, B, w["dz"], w["dlam"], w["expo"], p.z, p.lam),
         "step": graph.launch, "resolve32": resolve32, "resolve64": resolve64, "refined": solve_refined, "solve64": solve64,
     }
+    extra = variants(s, a, p, K)
+    fns.update({k: v[0] for k, v in extra.items() if v[0]})
     solve_refined()     # (the single launches are timed at a converged point: dz, dlam, expo are those of the last step)
     w["dz"].zero_()     # ... with a zero correction, so that K applications leave the point where it is
     w["dlam"].zero_()
-    order = ("defect", "residual64", "apply", "resolve32", "resolve64", "solve64", "step", "refined")
+    order = ("defect", "defect_reg", "defect_shared", "residual64", "apply", "resolve32", "resolve64", "solve64", "step", "step_reg",
+             "step_shared", "refined")
+    order = tuple(k for k in order if k in fns)
     for _ in range(2):
         for k in order:
             window(fns[k], max(1, a.warmup // (K if k == "refined" else 1)))
@@ -174,9 +180,54 @@ def flagship(s, a):
     print(f"  {K} refinement steps from zero   {stat(t['refined'])}   (kept fp32 factorisation; its formation is not in this figure)")
     print(f"  fp64 kkt_step + kkt_residual   {stat(t['solve64'])}   (forms S, Phi^-1 in fp64 every time)")
     print(f"  refined / fp64: {md(t['refined']) / md(t['solve64']):.3f}")
-    for g in (graph, g_step64, g_res64, g_res32):
+    for k, label, base in (("defect_reg", "kkt_defect_mixed_reg launch   ", "defect"), ("defect_shared", "kkt_defect_mixed_shared launch", "defect"),
+                           ("step_reg", "refine_step_reg graph replay  ", "step"), ("step_shared", "refine_step_shared graph replay", "step")):
+        if k in t:
+            print(f"  {label} {stat(t[k])}   ({k.split('_')[1]} / plain {md(t[k]) / md(t[base]):.3f}; {extra[k][1]})")
+        else:
+            print(f"  {label} not timed: {extra[k][1]}")
+    for g in [graph, g_step64, g_res64, g_res32] + [v[2] for v in extra.values() if v[2]]:
         g.close()
     return reached is not None
+
+
+def variants(s, a, p, K):
+    """The _reg and _shared rows: name -> (callable or None, note, graph or None).  Each step has its own point and work arrays and
+    is replayed K times from zero first, so that it is timed at ITS converged point, as the plain step is."""
+    nx, nu, N, B = p.dims
+    out = {}
+    rho = torch.full((B,), 0.3, dtype=torch.float64, device="cuda")
+    wr = s.refine_work(nx, nu, N, B)
+    out["defect_reg"] = (lambda: s.kkt_defect_mixed_reg(nx, nu, N, B, *p.data(), rho, p.z, p.lam, rg=wr["rg"], rc=wr["rc"], dlam=wr["dlam"],
+                                                        expo=wr["expo"], res=wr["res"]), "rho_b = 0.3", None)
+    G1, C1 = p.G[:p.G.numel() // B].clone(), None if p.C is None else p.C[:p.C.numel() // B].clone()
+    ws = s.refine_work(nx, nu, N, B)
+    out["defect_shared"] = (lambda: s.kkt_defect_mixed_shared(nx, nu, N, B, G1, C1, p.g, p.c, p.z, p.lam, rg=ws["rg"], rc=ws["rc"],
+                                                              dlam=ws["dlam"], expo=ws["expo"], res=ws["res"]), "one G, C", None)
+
+    def converged(make, note):
+        z, lam = torch.zeros_like(p.g), torch.zeros_like(p.c)
+        try:
+            graph = make(z, lam)
+        except Exception as e:   # (a shape the shared solve does not take: reported, not timed)
+            return None, f"refused ({e})", None
+        for _ in range(K):
+            graph.launch()
+        torch.cuda.synchronize()
+        return graph.launch, note, graph
+
+    S32, _, Ginv32 = s.form_schur_reg(nx, nu, N, B, p.G32, p.C32, p.g32, p.c32, s.demote(rho))
+    Pinv32 = s.form_pinv(nx, N, B, S32, binding.PINV_STAIR)
+    out["step_reg"] = converged(lambda z, lam: s.graph_kkt_refine_step_reg(nx, nu, N, B, *p.data(), rho, Ginv32, p.C32, S32, Pinv32, z, lam,
+                                                                           tol=a.tol, max_iter=a.max_iter, **wr),
+                                f"after {K} steps on the factorisation of fl32(G) + fl32(rho)")
+    n1 = lambda t: None if t is None else t[:t.numel() // B].clone()   # noqa: E731
+    S1, _, Gi1 = s.form_schur(nx, nu, N, 1, n1(p.G32), n1(p.C32), n1(p.g32), n1(p.c32))
+    P1 = s.form_pinv(nx, N, 1, S1, binding.PINV_STAIR)
+    out["step_shared"] = converged(lambda z, lam: s.graph_kkt_refine_step_shared(nx, nu, N, B, G1, C1, p.g, p.c, Gi1, n1(p.C32), S1, P1, z,
+                                                                                 lam, tol=a.tol, max_iter=a.max_iter, **ws),
+                                   f"after {K} steps; one G, C, Ginv32, C32, S32, Pinv32")
+    return out
 
 
 def small_shapes(s, a):

@@ -1061,9 +1061,37 @@ gbdpcg_status gbdpcg_graph_create_kkt_backward_shared_f64(gbdpcg_handle_t h, uin
  * for the fp32 solve.  Null handle or required pointer, nx, nu, N, batch or count == 0: GBDPCG_ERR_INVALID; a shape
  * gbdpcg_form_schur_* refuses (in either precision): GBDPCG_ERR_UNSUPPORTED; nothing is written in either case.  d_C and d_C32
  * may be NULL when N == 1.
- * Not provided: _shared twins, and a _reg form.  A factorisation of G + rho I from gbdpcg_kkt_step_reg_f32 may be passed as the
- * kept one: the defect does not contain rho, so the refinement then converges, more slowly, to the solution of the
- * UNREGULARISED fp64 system. */
+ *
+ * Regularised and shared-matrix forms.  Conventions, outputs, exponent rule and refusals are those above unless said here.
+ * gbdpcg_kkt_defect_mixed_reg: the defect of the REGULARISED system, r_s = (G_b + rho_b I) z + g + C' lambda.  d_rho: [batch]
+ *   fp64 on the device, directly behind d_c, required.  Every diagonal entry d of every Q_k and R_k enters its chain as
+ *   fl(d + rho_b), ONE fp64 rounding, as gbdpcg_kkt_residual_reg_f64 takes it; the chains and r_f are unchanged.  d_G is
+ *   untouched, no second buffer, no extra launch.  d_res is bit for bit what gbdpcg_kkt_residual_reg_f64 writes for the same
+ *   point; with every rho_b == 0 every output has the bits of gbdpcg_kkt_defect_mixed.  rho is not validated: a NaN in rho_b
+ *   costs problem b only (e_b = 0, NaN norm).
+ * gbdpcg_kkt_refine_step_reg, gbdpcg_graph_create_kkt_refine_step_reg: the step with that defect.  The kept factorisation is
+ *   what gbdpcg_kkt_step_reg_f32 (or gbdpcg_form_schur_reg_f32 + gbdpcg_form_pinv_f32) wrote from the demoted G and C with rho
+ *   demoted by gbdpcg_demote_f32.  The refinement then converges to the solution of the fp64 system with G + rho I: the case of
+ *   every ADMM z-update, of a damped SQP step, and of a cost that is only positive semi-definite, which has no plain
+ *   factorisation at all.  The graph keeps the POINTER d_rho, as gbdpcg_graph_create_kkt_step_reg_* does: rewrite rho in place
+ *   between replays (the kept fp32 factorisation should then be formed again, or the refinement slows down).
+ * gbdpcg_kkt_defect_mixed_shared: d_G and d_C are ONE problem's blocks, read by every problem of the batch; exactly one
+ *   problem's worth is read behind each.  g, c, z, lambda and every output stay per problem.  Problem b gets the bits of
+ *   gbdpcg_kkt_defect_mixed on `batch` copies of the matrices; d_res is bit for bit gbdpcg_kkt_residual_shared_f64.
+ * gbdpcg_kkt_refine_step_shared, gbdpcg_graph_create_kkt_refine_step_shared: d_G, d_C, d_Ginv32, d_C32, d_S32, d_Pinv32 are one
+ *   problem's each; the correction solve is gbdpcg_kkt_resolve_shared_f32 and its rules hold as stated there (fused family only,
+ *   one verdict for the one pair in symmetric mode 2, GBDPCG_ERR_UNSUPPORTED for a shape beyond one workgroup).  Problem b gets
+ *   the bits of gbdpcg_kkt_refine_step on `batch` copies of the matrices, on the same handle with the path set to
+ *   GBDPCG_PATH_FUSED.
+ * Each step is bit-identical with its three calls (defect, gbdpcg_kkt_resolve[_shared]_f32, gbdpcg_kkt_refine_apply).
+ * d_rho == NULL: GBDPCG_ERR_INVALID; every other refusal is that of the function extended; nothing is written on refusal.
+ * Not provided: _shared and _reg TOGETHER.  A shared batch has one G, so rho could only be one number: the caller writes
+ *   G + rho I into that one G (gbdpcg_admm_lin_form_f64 with E = I, batch 1, d_Gt == d_G allowed) and uses the _shared forms,
+ *   as for gbdpcg_kkt_residual_shared_*.  Refinement behind the gbdpcg_admm_*_step_* entry points themselves is not provided
+ *   either: an ADMM loop in mixed precision replays the refine_step_reg graph with g := the shifted gradient and calls
+ *   gbdpcg_admm_update_f64 (examples/refine_box_mpc_loop.cpp).
+ * A factorisation of G + rho I from gbdpcg_kkt_step_reg_f32 may still be passed as the kept one of the PLAIN step: the plain
+ * defect does not contain rho, so the refinement then converges, more slowly, to the solution of the UNREGULARISED fp64 system. */
 gbdpcg_status gbdpcg_demote_f32(gbdpcg_handle_t h, uint64_t count, const double *d_src, float *d_dst, void *stream);
 gbdpcg_status gbdpcg_kkt_defect_mixed(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
                                       const double *d_G, const double *d_C, const double *d_g, const double *d_c,
@@ -1086,6 +1114,45 @@ gbdpcg_status gbdpcg_graph_create_kkt_refine_step(gbdpcg_handle_t h, uint32_t nx
                                                   uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
                                                   int32_t *d_expo, double *d_z, double *d_lambda, double *d_res,
                                                   gbdpcg_graph_t *out);
+
+gbdpcg_status gbdpcg_kkt_defect_mixed_reg(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                          const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                          const double *d_rho, const double *d_z, const double *d_lambda, float *d_rg,
+                                          float *d_rc, float *d_dlambda, int32_t *d_expo, double *d_res, void *stream);
+gbdpcg_status gbdpcg_kkt_defect_mixed_shared(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                             const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                             const double *d_z, const double *d_lambda, float *d_rg, float *d_rc,
+                                             float *d_dlambda, int32_t *d_expo, double *d_res, void *stream);
+gbdpcg_status gbdpcg_kkt_refine_step_reg(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                         const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                         const double *d_rho, const float *d_Ginv32, const float *d_C32, const float *d_S32,
+                                         const float *d_Pinv32, float *d_rg, float *d_rc, float *d_gamma, float *d_dlambda,
+                                         float *d_r, float *d_p, float *d_dz, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                         uint8_t *d_max_iter_exit, int32_t *d_expo, double *d_z, double *d_lambda,
+                                         double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_kkt_refine_step_reg(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                      const double *d_G, const double *d_C, const double *d_g,
+                                                      const double *d_c, const double *d_rho, const float *d_Ginv32,
+                                                      const float *d_C32, const float *d_S32, const float *d_Pinv32,
+                                                      float *d_rg, float *d_rc, float *d_gamma, float *d_dlambda, float *d_r,
+                                                      float *d_p, float *d_dz, float tol, uint32_t max_iter,
+                                                      uint32_t *d_iters, uint8_t *d_max_iter_exit, int32_t *d_expo,
+                                                      double *d_z, double *d_lambda, double *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_kkt_refine_step_shared(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                            const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                            const float *d_Ginv32, const float *d_C32, const float *d_S32,
+                                            const float *d_Pinv32, float *d_rg, float *d_rc, float *d_gamma, float *d_dlambda,
+                                            float *d_r, float *d_p, float *d_dz, float tol, uint32_t max_iter,
+                                            uint32_t *d_iters, uint8_t *d_max_iter_exit, int32_t *d_expo, double *d_z,
+                                            double *d_lambda, double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_kkt_refine_step_shared(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N,
+                                                         uint32_t batch, const double *d_G, const double *d_C,
+                                                         const double *d_g, const double *d_c, const float *d_Ginv32,
+                                                         const float *d_C32, const float *d_S32, const float *d_Pinv32,
+                                                         float *d_rg, float *d_rc, float *d_gamma, float *d_dlambda,
+                                                         float *d_r, float *d_p, float *d_dz, float tol, uint32_t max_iter,
+                                                         uint32_t *d_iters, uint8_t *d_max_iter_exit, int32_t *d_expo,
+                                                         double *d_z, double *d_lambda, double *d_res, gbdpcg_graph_t *out);
 
 /* CSR ingestion (f3): repacks a host CSR matrix (csr_t<T>, include/types.cuh:7-15) whose
  * sparsity lies inside the block-tridiagonal pattern into the [L|D|R] layout (host arrays).
