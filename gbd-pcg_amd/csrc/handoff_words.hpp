@@ -1,6 +1,6 @@
 // handoff_words.hpp -- the primitive types and constants of the tagged hand-off words that workgroups on different CUs pass
 // each other inside one launch: shared by the persistent kernels (pcg_persist_handoff.hpp) and the cluster kernel
-// (pcg_cluster.hip), whose protocols differ in everything above this level.
+// (pcg_cluster_handoff.hpp), whose protocols differ in everything above this level.
 #pragma once
 
 namespace gbdpcg {

@@ -169,8 +169,9 @@ template <typename T> bool resident_sym_verifies(const DeviceInfo &dev, uint32_t
 template <typename T>
 bool launch_pcg_resident_sym_verify(const DeviceInfo &dev, const PcgArgs<T> &a, hipStream_t s, hipError_t *err);
 
-// ---- pcg_cluster.hip : general-storage matrices register-resident, a problem over a cluster of 2-4 workgroups (CUs)
-// Workgroups per problem the cluster path would use; 0 = shape not handled (n = 14, fp32, 72 < N <= 288 only).
+// ---- pcg_cluster.hip : general-storage matrices register-resident, a problem over a cluster of up to eight (fp64: four) workgroups
+// Workgroups per problem the cluster path would use; 0 = shape not handled (block size not built, a horizon one workgroup of
+// pcg_resident.hip holds, or more members than a cluster has: at n = 14 in fp32 the path takes 72 < N <= 576).
 template <typename T> uint32_t cluster_members(uint32_t n, uint32_t N);
 size_t cluster_workspace_bytes(const DeviceInfo &dev);
 size_t cluster_rescue_bytes(const DeviceInfo &dev);   // PcgArgs::rescue_vec of a cluster launch

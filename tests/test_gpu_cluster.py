@@ -451,6 +451,49 @@ def test_cluster_launches_do_not_see_each_other(solver, orc):
         assert relerr(out["lambda_"][b], ob["lambda_"][j]) < 1e-6, b
 
 
+FIXED_SOLVE = r"""
+import sys, numpy as np, torch
+sys.path.insert(0, sys.argv[1])
+from gbd_pcg_amd import binding, synth
+n, N, B, dt = int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]), np.dtype(sys.argv[6]).type
+d = synth.gen_numpy(n, N, seed=77, batch=B, dtype=dt)
+s = binding.Solver(0)
+assert s.cluster_members(np.dtype(dt).itemsize, n, N) == 2
+s.set_symmetric(0)
+dS, dP, dg = (torch.from_numpy(np.ascontiguousarray(d[k])).cuda() for k in ("S", "Pinv", "gamma"))
+lam = torch.zeros_like(dg)
+r, p = torch.full_like(dg, float("nan")), torch.full_like(dg, float("nan"))
+it, fl = s.solve(n, N, B, dS, dP, dg, lam, r, p, tol=0.0, max_iter=7)
+torch.cuda.synchronize()
+np.savez(sys.argv[2], lambda_=lam.cpu().numpy(), r=r.cpu().numpy(), p=p.cpu().numpy(), iters=it.cpu().numpy(), flags=fl.cpu().numpy())
+s.close()
+"""
+
+
+@pytest.mark.parametrize("n,N,dtype", [(14, 73, "float32"), (4, 129, "float64")])
+def test_cluster_plain_and_sc1_stores_give_the_same_bits(tmp_path, n, N, dtype):
+    """The publish is one template on the cache policy of its stores: the same solve with GBDPCG_CLUSTER_NO_PLAIN=1 (always sc1;
+    the switch is read once per process, hence the child processes) and without it (plain stores where HELLO finds the cluster on
+    one XCD: 8 clusters of two members sit 8 blocks apart) -- lambda, r, p, iteration counts and flags bit for bit, whatever
+    placement the device gives.  The smallest shapes with two members (fp32: 37 knots each, the second member's last wave partly
+    filled), tol = 0 and seven iterations so that every hand-off of a fixed count runs."""
+    outs = []
+    for tag, switch in (("plain", None), ("sc1", "1")):
+        env = dict(os.environ, PYTHONPATH=ROOT)
+        env.pop("GBDPCG_CLUSTER_NO_PLAIN", None)
+        if switch:
+            env["GBDPCG_CLUSTER_NO_PLAIN"] = switch
+        path = str(tmp_path / f"{tag}.npz")
+        res = subprocess.run([sys.executable, "-c", FIXED_SOLVE, ROOT, path, str(n), str(N), "8", dtype], env=env, cwd=ROOT,
+                             capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stdout[-1000:] + res.stderr[-3000:]
+        outs.append(np.load(path))
+    assert (outs[0]["iters"] == 7).all() and (outs[0]["flags"] == 1).all()
+    for key in ("lambda_", "r", "p", "iters", "flags"):
+        assert outs[0][key].tobytes() == outs[1][key].tobytes(), key
+    assert np.isfinite(outs[0]["lambda_"]).all() and np.isfinite(outs[0]["r"]).all() and np.isfinite(outs[0]["p"]).all()
+
+
 HOOKS_LIB = os.path.join(ROOT, "gbd-pcg_amd", "csrc", "variants", "libgbdpcg_hooks.so")
 
 GIVE_UP = r"""
