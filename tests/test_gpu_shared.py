@@ -12,6 +12,7 @@ tests/test_gpu_footprint.py does.
 import ctypes
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -83,6 +84,7 @@ CASES = [
     Case("14x128-m2-nonsym", {"cluster"}, 14, 128, F32, mode=2, sym=False),
     Case("14x128-ident", {"cluster"}, 14, 128, F32, pinv=False),
     Case("14x128-off4", {"fused"}, 14, 128, F32, shift=4),
+    Case("14x128-m1-off8", {"resident_sym"}, 14, 128, F32, mode=1, shift=8),
 ]
 
 
@@ -213,6 +215,35 @@ def test_batch_one_is_the_twin(solver):
     d = Data(c, 1, seed=3)
     a, b = solve_both(solver, c, 1, dev(d.S), dev(d.P), dev(d.gamma.reshape(-1)), dev(d.lam0.reshape(-1)), 1e-6, 60)
     assert_same(a, b, "batch 1")
+
+
+_OFF8_CHILD = r"""
+import sys
+sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests"]
+import test_gpu_shared as t
+s = t.binding.Solver(0)
+for N in (3, 128):
+    c = t.Case(f"14x{N}-m1-off8", {"resident_sym"}, 14, N, t.F32, mode=1, shift=8)
+    d = t.Data(c, 3)
+    S1, P1, gamma = t.shifted(t.dev(d.S), 8), t.shifted(t.dev(d.P), 8), t.dev(d.gamma.reshape(-1))
+    for lam0, tol, mi in ((d.lam0, 1e-6, 60), (d.warm0, 0.0, 6)):
+        a, b = t.solve_both(s, c, 3, S1, P1, gamma, t.dev(lam0.reshape(-1)), tol, mi)
+        it, fl = a["it"].cpu().numpy(), a["fl"].cpu().numpy()
+        assert ((it >= 1).all() and (it < 60).all() and not fl.any()) if tol else ((it == 6).all() and (fl == 1).all()), (N, it, fl)
+        assert bool(t.torch.isfinite(b["lam"]).all())
+        t.assert_same(a, b, (N, tol))
+print("off8 ok")
+"""
+
+
+def test_shared_pair_at_8_byte_offset_is_the_plain_kernel():
+    """pcg_resident_sym.hip's shared instantiation with direct tile loads (the one pair only 8-byte aligned) at N = 3 and N = 128,
+    batch 3: the checks of test_solve_shared_is_the_replicated_solve, whose case 14x128-m1-off8 asserts that the family is reached
+    at N = 128.  In a child process, because N = 3 gets past pcg_resident.hip only with GBDPCG_NO_RESIDENT, read once per process
+    (csrc/pcg_fused.hip, launch_pcg_fused: pcg_resident.hip first, then pcg_resident_sym.hip when the caller asserts symmetry)."""
+    env = dict(os.environ, GBDPCG_NO_RESIDENT="1")
+    res = subprocess.run([sys.executable, "-c", _OFF8_CHILD, ROOT], env=env, capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0 and "off8 ok" in res.stdout, res.stderr[-3000:]
 
 
 SCHUR_SHAPES = [(14, 7, 128, 3), (14, 7, 1, 2), (14, 7, 2, 1), (2, 1, 5, 4), (3, 3, 2, 1), (5, 2, 9, 2), (12, 4, 33, 2), (4, 6, 3, 2),
