@@ -57,6 +57,13 @@ SYMBOLS = [
     "gbdpcg_graph_create_admm_soc_step_f32", "gbdpcg_graph_create_admm_soc_step_f64",
     "gbdpcg_admm_soc_step_shared_f32", "gbdpcg_admm_soc_step_shared_f64",
     "gbdpcg_graph_create_admm_soc_step_shared_f32", "gbdpcg_graph_create_admm_soc_step_shared_f64",
+    "gbdpcg_admm_rebalance_f32", "gbdpcg_admm_rebalance_f64", "gbdpcg_admm_lin_rebalance_f32", "gbdpcg_admm_lin_rebalance_f64",
+    "gbdpcg_admm_soc_rebalance_f32", "gbdpcg_admm_soc_rebalance_f64",
+    "gbdpcg_admm_restep_f32", "gbdpcg_admm_restep_f64", "gbdpcg_graph_create_admm_restep_f32", "gbdpcg_graph_create_admm_restep_f64",
+    "gbdpcg_admm_lin_restep_f32", "gbdpcg_admm_lin_restep_f64",
+    "gbdpcg_graph_create_admm_lin_restep_f32", "gbdpcg_graph_create_admm_lin_restep_f64",
+    "gbdpcg_admm_soc_restep_f32", "gbdpcg_admm_soc_restep_f64",
+    "gbdpcg_graph_create_admm_soc_restep_f32", "gbdpcg_graph_create_admm_soc_restep_f64",
     "gbdpcg_kkt_grad_f32", "gbdpcg_kkt_grad_f64", "gbdpcg_kkt_grad_shared_f32", "gbdpcg_kkt_grad_shared_f64",
     "gbdpcg_kkt_backward_f32", "gbdpcg_kkt_backward_f64", "gbdpcg_kkt_backward_shared_f32", "gbdpcg_kkt_backward_shared_f64",
     "gbdpcg_graph_create_kkt_backward_f32", "gbdpcg_graph_create_kkt_backward_f64",
@@ -110,6 +117,16 @@ def _resolve_argtypes(lib):
                 step_args = fsizes + [vp, vp, vp, vp] + fset + solve + [vp, vp, vp, vp]
                 getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = step_args + [vp]
                 getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = step_args + [ctypes.POINTER(vp)]
+            # adaptive rho.  The rule: ratio, shift, rho_min, rho_max, expo
+            #   rebalance  ...                   | g | [E, lo, hi], res, rho | w, y, gt | rule | stream
+            #   restep     ...   | G, [Gt], Ginv, C, g, c | [E], lo, hi, rho | S, Pinv, kind, the rest of the solve | w, y, gt, res | rule |
+            rule = [ft, u32, ft, ft, vp]
+            getattr(lib, f"gbdpcg_{fam}_rebalance_{suf}").argtypes = (fsizes + [vp] + (fset[:-1] if extra else []) + [vp, vp] + [vp, vp, vp] +
+                                                                     rule + [vp])
+            restep_args = (fsizes + [vp] + ([vp] if extra else []) + [vp, vp, vp, vp] + fset + [vp, vp, ctypes.c_int] + solve[2:] +
+                           [vp, vp, vp, vp] + rule)
+            getattr(lib, f"gbdpcg_{fam}_restep_{suf}").argtypes = restep_args + [vp]
+            getattr(lib, f"gbdpcg_graph_create_{fam}_restep_{suf}").argtypes = restep_args + [ctypes.POINTER(vp)]
         getattr(lib, f"gbdpcg_admm_lin_form_{suf}").argtypes = sizes + [u32, u32] + [vp, vp, vp, vp, vp]   # (mx, mu) G, E, rho, Gt, stream
         # the backward pass: z, lambda, az, alambda | gG, gC, stream
         for name in ("kkt_grad", "kkt_grad_shared"):
@@ -837,6 +854,149 @@ class Solver:
         """Capture the shared-matrix iteration into a hipGraph (gbdpcg_graph_create_admm_soc_step_shared_*)."""
         return self._graph_admm_step("admm_soc_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
                                      max_iter, iters, max_iter_exit, z, w, y, gt, res, rows=(mx, mu, E), cones=cones)
+
+    # ---- adaptive rho (include/gbdpcg.h): residual balancing in powers of two on the device.  rho is rewritten in place, y rescaled so
+    # that rho y stays, expo [batch] int32 receives the exponent applied to rho (+shift, -shift or 0)
+    @staticmethod
+    def _expo(expo, batch, like):
+        import torch
+        if expo is None:
+            expo = torch.zeros(batch, dtype=torch.int32, device=like.device)
+        assert expo.is_cuda and expo.is_contiguous() and expo.numel() == batch and expo.dtype == torch.int32
+        return expo
+
+    @staticmethod
+    def _res(res, batch, g):
+        assert res is not None and res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == g.dtype
+        return res
+
+    def admm_rebalance(self, nx, nu, N, batch, g, res, rho, w, y, gt, expo=None, *, ratio=10.0, shift=1, rho_min, rho_max, stream=None):
+        """gbdpcg_admm_rebalance_*: rho and y in place from the residuals in res, gt rebuilt as admm_init would, one launch.
+        Returns expo."""
+        suf, _ = _suffix(g)
+        self._box(g, batch, w, y, gt)
+        expo = self._expo(expo, batch, g)
+        fn = getattr(self.lib, f"gbdpcg_admm_rebalance_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(g), _p(self._res(res, batch, g)), _p(self._rho(rho, batch, g)), _p(w), _p(y), _p(gt),
+                       ratio, shift, rho_min, rho_max, _p(expo), self._stream(stream)), "admm_rebalance")
+        return expo
+
+    def _rows_rebalance(self, name, sizes, nx, nu, mx, mu, N, batch, g, E, lo, hi, res, rho, w, y, gt, expo, ratio, shift, rho_min, rho_max,
+                        stream):
+        suf, _ = _suffix(g)
+        self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y), (g, gt))
+        expo = self._expo(expo, batch, g)
+        fn = getattr(self.lib, f"gbdpcg_{name}_{suf}")
+        self._check(fn(self.h, nx, nu, *sizes, N, batch, _p(g), _p(E), _p(lo), _p(hi), _p(self._res(res, batch, g)),
+                       _p(self._rho(rho, batch, g)), _p(w), _p(y), _p(gt), ratio, shift, rho_min, rho_max, _p(expo), self._stream(stream)),
+                    name)
+        return expo
+
+    def admm_lin_rebalance(self, nx, nu, mx, mu, N, batch, g, E, lo, hi, res, rho, w, y, gt, expo=None, *, ratio=10.0, shift=1, rho_min,
+                           rho_max, stream=None):
+        """gbdpcg_admm_lin_rebalance_*: rho and y (layout of the rows) in place, then admm_lin_init rebuilds gt.  Returns expo."""
+        return self._rows_rebalance("admm_lin_rebalance", (mx, mu), nx, nu, mx, mu, N, batch, g, E, lo, hi, res, rho, w, y, gt, expo, ratio,
+                                    shift, rho_min, rho_max, stream)
+
+    def admm_soc_rebalance(self, nx, nu, mx, mu, cones, N, batch, g, E, lo, hi, res, rho, w, y, gt, expo=None, *, ratio=10.0, shift=1,
+                           rho_min, rho_max, stream=None):
+        """gbdpcg_admm_soc_rebalance_*: the same through admm_soc_init, which re-projects w (cone rows may move by ulps).  Returns expo."""
+        assert len(cones) == 4
+        return self._rows_rebalance("admm_soc_rebalance", (mx, mu) + tuple(int(v) for v in cones), nx, nu, mx, mu, N, batch, g, E, lo, hi,
+                                    res, rho, w, y, gt, expo, ratio, shift, rho_min, rho_max, stream)
+
+    def _admm_restep_args(self, nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, kind, gamma, lam, r, p, tol, max_iter, iters,
+                          mie, z, w, y, gt, res, expo, ratio, shift, rho_min, rho_max, rows=None, cones=None):
+        """(suffix, the argument tuple up to d_expo, the tensors a graph has to keep alive); Gt is None for the box."""
+        suf, _ = _suffix(g)
+        self._res(res, batch, g)
+        sizes, E, mats = (), (), (G,)
+        if rows is None:
+            assert cones is None and Gt is None
+            self._box(g, batch, lo, hi, z, w, y, gt)
+        else:
+            mx, mu, E = rows
+            self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y), (g, z, gt))
+            assert Gt is not None and Gt.numel() == G.numel() and Gt.dtype == G.dtype and Gt.is_cuda and Gt.is_contiguous()
+            sizes, E, mats = (mx, mu), (E,), (G, Gt)
+            if cones is not None:
+                assert len(cones) == 4
+                sizes += tuple(int(v) for v in cones)
+        args = ((self.h, nx, nu) + sizes + (N, batch) + tuple(_p(t) for t in mats) + (_p(Ginv), _p(C), _p(g), _p(c)) +
+                tuple(_p(t) for t in E) + (_p(lo), _p(hi), _p(self._rho(rho, batch, g)), _p(S), _p(Pinv), kind, _p(gamma), _p(lam), _p(r),
+                                           _p(p), tol, max_iter, _p(iters), _p(mie), _p(z), _p(w), _p(y), _p(gt), _p(res), ratio, shift,
+                                           rho_min, rho_max, _p(expo)))
+        return suf, args, mats + (Ginv, C, g, c) + E + (lo, hi, rho, S, Pinv, gamma, lam, r, p, iters, mie, z, w, y, gt, res, expo)
+
+    def _admm_restep(self, name, nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, expo, kind, r, p,
+                     tol, max_iter, iters, max_iter_exit, ratio, shift, rho_min, rho_max, stream, rows=None, cones=None):
+        import torch
+        if iters is None:
+            iters = torch.zeros(batch, dtype=torch.int32, device=g.device)
+        if max_iter_exit is None:
+            max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=g.device)
+        expo = self._expo(expo, batch, g)
+        suf, args, _ = self._admm_restep_args(nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, kind, gamma, lam, r, p, tol,
+                                              max_iter, iters, max_iter_exit, z, w, y, gt, res, expo, ratio, shift, rho_min, rho_max,
+                                              rows, cones)
+        self._check(getattr(self.lib, f"gbdpcg_{name}_{suf}")(*args, self._stream(stream)), name)
+        return iters, max_iter_exit, res.view(batch, 2), expo
+
+    def _graph_admm_restep(self, name, nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                           max_iter_exit, z, w, y, gt, res, expo, kind, ratio, shift, rho_min, rho_max, rows=None, cones=None):
+        suf, args, keep = self._admm_restep_args(nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, kind, gamma, lam, r, p, tol,
+                                                 max_iter, iters, max_iter_exit, z, w, y, gt, res, self._expo(expo, batch, g), ratio,
+                                                 shift, rho_min, rho_max, rows, cones)
+        gr = ctypes.c_void_p()
+        self._check(getattr(self.lib, f"gbdpcg_graph_create_{name}_{suf}")(*args, ctypes.byref(gr)), f"graph_create_{name}")
+        return Graph(self, gr, keep=keep)
+
+    def admm_restep(self, nx, nu, N, batch, G, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, expo=None, kind=PINV_STAIR,
+                    r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, *, ratio=10.0, shift=1, rho_min, rho_max,
+                    stream=None):
+        """gbdpcg_admm_restep_*: one iteration with a new rho -- admm_rebalance, kkt_step_reg on G and rho with gt in the place of g,
+        admm_update.  Every problem is refactored.  Returns (iters, flags, res [batch, 2], expo)."""
+        return self._admm_restep("admm_restep", nx, nu, N, batch, G, None, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res,
+                                 expo, kind, r, p, tol, max_iter, iters, max_iter_exit, ratio, shift, rho_min, rho_max, stream)
+
+    def graph_admm_restep(self, nx, nu, N, batch, G, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                          max_iter_exit, z, w, y, gt, res, expo, kind=PINV_STAIR, *, ratio=10.0, shift=1, rho_min, rho_max):
+        """Capture the iteration with a new rho into a hipGraph (gbdpcg_graph_create_admm_restep_*): replay it once per P replays of the
+        step graph; it keeps the pointers of rho, res and expo."""
+        return self._graph_admm_restep("admm_restep", nx, nu, N, batch, G, None, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                       max_iter, iters, max_iter_exit, z, w, y, gt, res, expo, kind, ratio, shift, rho_min, rho_max)
+
+    def admm_lin_restep(self, nx, nu, mx, mu, N, batch, G, Gt, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, expo=None,
+                        kind=PINV_STAIR, r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, *, ratio=10.0, shift=1,
+                        rho_min, rho_max, stream=None):
+        """gbdpcg_admm_lin_restep_*: admm_lin_rebalance, admm_lin_form from G into Gt (not G itself), kkt_step on Gt with gt in the
+        place of g, admm_lin_update.  Returns (iters, flags, res [batch, 2], expo)."""
+        return self._admm_restep("admm_lin_restep", nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res,
+                                 expo, kind, r, p, tol, max_iter, iters, max_iter_exit, ratio, shift, rho_min, rho_max, stream,
+                                 rows=(mx, mu, E))
+
+    def graph_admm_lin_restep(self, nx, nu, mx, mu, N, batch, G, Gt, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter,
+                              iters, max_iter_exit, z, w, y, gt, res, expo, kind=PINV_STAIR, *, ratio=10.0, shift=1, rho_min, rho_max):
+        """Capture gbdpcg_admm_lin_restep_* into a hipGraph; it keeps the pointers of rho, res and expo."""
+        return self._graph_admm_restep("admm_lin_restep", nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                       max_iter, iters, max_iter_exit, z, w, y, gt, res, expo, kind, ratio, shift, rho_min, rho_max,
+                                       rows=(mx, mu, E))
+
+    def admm_soc_restep(self, nx, nu, mx, mu, cones, N, batch, G, Gt, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res,
+                        expo=None, kind=PINV_STAIR, r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, *, ratio=10.0,
+                        shift=1, rho_min, rho_max, stream=None):
+        """gbdpcg_admm_soc_restep_*: the same with cone rows (admm_soc_rebalance, admm_soc_update).  Returns (iters, flags, res, expo)."""
+        return self._admm_restep("admm_soc_restep", nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res,
+                                 expo, kind, r, p, tol, max_iter, iters, max_iter_exit, ratio, shift, rho_min, rho_max, stream,
+                                 rows=(mx, mu, E), cones=cones)
+
+    def graph_admm_soc_restep(self, nx, nu, mx, mu, cones, N, batch, G, Gt, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                              max_iter, iters, max_iter_exit, z, w, y, gt, res, expo, kind=PINV_STAIR, *, ratio=10.0, shift=1, rho_min,
+                              rho_max):
+        """Capture gbdpcg_admm_soc_restep_* into a hipGraph; it keeps the pointers of rho, res and expo."""
+        return self._graph_admm_restep("admm_soc_restep", nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                       max_iter, iters, max_iter_exit, z, w, y, gt, res, expo, kind, ratio, shift, rho_min, rho_max,
+                                       rows=(mx, mu, E), cones=cones)
 
     # ---- the backward pass (include/gbdpcg.h): gradients of a scalar in G and C from the forward point (z, lam) and the adjoint pair
     # (az, alam), which is kkt_resolve with g := dl/dz, c := -dl/dlambda on the kept factorisation

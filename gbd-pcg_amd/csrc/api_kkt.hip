@@ -3,6 +3,8 @@
 // kkt_resolve, the ADMM steps, the backward pass, with their _shared and _reg forms and their graphs.  Host code only.
 #include "api_context.hpp"
 
+#include <limits>
+
 #ifndef GBDPCG_KKT_SKIP_L
 #define GBDPCG_KKT_SKIP_L 1   // 0: the stair kernel of gbdpcg_kkt_step_* reads and compares L_{k+1} like everywhere else (A/B runs)
 #endif
@@ -266,6 +268,105 @@ gbdpcg_status admm_step_impl(gbdpcg_handle_t h, const KktOperands<T> &k, const A
     return admm_update_impl<T>(h, p.n, k.nu, p.N, p.batch, k.g, a.lo, a.hi, a.rho, k.z, a.w, a.y, a.gt, a.res, stream, false);
 }
 
+// ---- adaptive rho (admm_rebalance.hip): residual balancing in powers of two, and the iteration that refactors with the new rho
+// The rule of gbdpcg_admm*_rebalance_* and what it writes next to y: rho [batch] in place, expo [batch].
+template <typename T> struct RhoRule {
+    T ratio;
+    uint32_t shift;
+    T rho_min, rho_max;
+    T *rho;
+    int32_t *expo;
+};
+// (comparisons: a NaN among ratio, rho_min, rho_max is refused; rho_min is finite where rho_max is)
+template <typename T> bool rho_rule_ok(const RhoRule<T> &r)
+{
+    return r.rho && r.expo && r.shift >= 1 && r.shift <= 16 && r.ratio >= T(1) && r.rho_min > T(0) && r.rho_min <= r.rho_max &&
+           r.rho_max <= std::numeric_limits<T>::max();
+}
+
+// The box form, one launch: rho, y, expo and the gt that gbdpcg_admm_init_* would rebuild.  Elementwise: no shape is refused.
+template <typename T>
+gbdpcg_status admm_rebalance_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_g, const T *d_res,
+                                  const T *d_w, T *d_y, T *d_gt, const RhoRule<T> &rule, void *stream)
+{
+    if (!h || !d_g || !d_res || !d_w || !d_y || !d_gt || nx == 0 || nu == 0 || N == 0 || batch == 0 || !rho_rule_ok<T>(rule))
+        return GBDPCG_ERR_INVALID;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_admm_rebalance<T>(((uint64_t)nx + nu) * N - nu, batch, d_g, d_res, rule.rho, d_w, d_y, d_gt, rule.ratio, rule.shift,
+                                        rule.rho_min, rule.rho_max, rule.expo, (hipStream_t)stream, true));
+    return GBDPCG_OK;
+}
+
+// The rows form (admm_lin, admm_soc): rho, y over the rows of a, expo; then the family's init launch rebuilds gt (and re-projects w).
+// a.rho is rule.rho.  Whatever the init launch refuses is refused here before the first launch.
+template <typename T>
+gbdpcg_status admm_rows_rebalance_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_g,
+                                       const AdmmOperands<T> &a, const RhoRule<T> &rule, void *stream)
+{
+    if (!h || !d_g || !a.E || !a.lo || !a.hi || !a.res || !a.w || !a.y || !a.gt || nx == 0 || nu == 0 || N == 0 || batch == 0 ||
+        !rho_rule_ok<T>(rule))
+        return GBDPCG_ERR_INVALID;
+    const gbdpcg_status st = admm_rows_status<T>(nx, nu, a, N);
+    if (st != GBDPCG_OK) return st;
+    {
+        DEVICE_SCOPE(h);
+        HIP_TRY(h, launch_admm_rebalance<T>(((uint64_t)a.mx + a.mu) * N - a.mu, batch, nullptr, a.res, rule.rho, nullptr, a.y, nullptr,
+                                            rule.ratio, rule.shift, rule.rho_min, rule.rho_max, rule.expo, (hipStream_t)stream, false));
+    }
+    return admm_rows_update_impl<T>(h, nx, nu, N, batch, d_g, a, nullptr, stream, true);
+}
+
+// What gbdpcg_admm*_restep_* refactors with next to the rule: the original G, and for the families with rows the Gt = G + rho E'E
+// that is formed from it (null for the box, whose formation adds rho I itself).
+template <typename T> struct Refactor {
+    const T *G;
+    T *Gt;
+    T *S, *Ginv, *Pinv;
+    gbdpcg_pinv_kind kind;
+    KktFormed<T> formed(const AdmmOperands<T> &a) const
+    {
+        if (a.rows) return KktFormed<T>{Gt, S, Ginv, Pinv, kind};
+        return KktFormed<T>{G, S, Ginv, Pinv, kind, a.rho, true};
+    }
+};
+
+// What gbdpcg_admm*_restep_* refuses before anything is written, reserved or captured: whatever the rebalance, the formation, the
+// step of kkt_step_* (as its graph form asks: everything it writes, and the kind) or the iteration would refuse, every INVALID
+// before every UNSUPPORTED.  The families with rows need a Gt of their own: the next restep forms from the original G again.
+template <typename T>
+gbdpcg_status admm_restep_refusal(gbdpcg_handle_t h, const Refactor<T> &f, const KktOperands<T> &k, const AdmmOperands<T> &a,
+                                  const RhoRule<T> &rule, const PcgArgs<T> &p, bool solve_limits)
+{
+    if (!rho_rule_ok<T>(rule) || !f.G || (a.rows && (!f.Gt || f.Gt == f.G)) || kkt_step_refusal<T>(f.formed(a), k, true) != GBDPCG_OK)
+        return GBDPCG_ERR_INVALID;
+    return admm_step_refusal<T>(h, k, a, p, solve_limits);
+}
+
+// One iteration with a new rho, on one stream: rebalance (rho, y, gt, expo), the formation and the solve of kkt_step_impl with a.gt
+// in the place of g -- on G with rho (box) or on Gt = G + rho E'E formed here (rows) --, then the family's update.
+template <typename T>
+gbdpcg_status admm_restep_impl(gbdpcg_handle_t h, const Refactor<T> &f, const KktOperands<T> &k, const AdmmOperands<T> &a,
+                               const RhoRule<T> &rule, const PcgArgs<T> &p, hipStream_t stream)
+{
+    gbdpcg_status st = admm_restep_refusal<T>(h, f, k, a, rule, p, true);
+    if (st != GBDPCG_OK) return st;
+    const uint32_t nx = p.n, N = p.N, batch = p.batch;
+    if (a.rows) {
+        st = admm_rows_rebalance_impl<T>(h, nx, k.nu, N, batch, k.g, a, rule, stream);
+        if (st != GBDPCG_OK) return st;
+        st = admm_lin_form_impl<T>(h, nx, k.nu, a.mx, a.mu, N, batch, f.G, a.E, a.rho, f.Gt, stream);
+    } else {
+        st = admm_rebalance_impl<T>(h, nx, k.nu, N, batch, k.g, a.res, a.w, a.y, a.gt, rule, stream);
+    }
+    if (st != GBDPCG_OK) return st;
+    KktOperands<T> shifted = k;
+    shifted.g = a.gt;
+    st = kkt_step_impl<T>(h, f.formed(a), shifted, p, stream);
+    if (st != GBDPCG_OK) return st;
+    if (a.rows) return admm_rows_update_impl<T>(h, nx, k.nu, N, batch, k.g, a, k.z, stream, false);
+    return admm_update_impl<T>(h, nx, k.nu, N, batch, k.g, a.lo, a.hi, a.rho, k.z, a.w, a.y, a.gt, a.res, stream, false);
+}
+
 // The gradient launch (kkt_grad.hip), no handle state.  shared: gG, gC are one problem's worth, summed over the batch.
 template <typename T>
 gbdpcg_status kkt_grad_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_z, const T *d_lambda,
@@ -506,11 +607,13 @@ GBDPCG_PAIR_BOTH(kkt_resolve_shared, true, RESOLVE_PARAMS, RESOLVE_SETUP, RESOLV
 //   admm_lin   stage-wise linear rows lo <= E z <= hi, the matrices of G + rho E'E (gbdpcg_admm_lin_form_*)
 //   admm_soc   second-order cone rows next to the linear ones, the same matrices
 // Each has init, update, step and graph_create_step, the last two with a _shared twin on one problem's Ginv, C, S, Pinv (and E);
-// the set, rho and the splitting state stay per problem.  A family is described by four macros, defined in front of its entries:
-//   ADMM_SIZES        the sizes between h and N
-//   ADMM_SET(TYPE)    the set, in front of d_rho
-//   ADMM_CONES        the declaration of `cones`, the RowClasses of the family, where it has any
-//   ADMM_OPERANDS     the initialiser of its AdmmOperands
+// the set, rho and the splitting state stay per problem.  Adaptive rho: rebalance, restep and graph_create_restep, per problem only.
+// A family is described by these macros, defined in front of its entries:
+//   ADMM_SIZES           the sizes between h and N
+//   ADMM_SET(TYPE)       the set, in front of d_rho
+//   ADMM_CONES           the declaration of `cones`, the RowClasses of the family, where it has any
+//   ADMM_OPERANDS        the initialiser of its AdmmOperands (rows: its tail behind d_res is ADMM_ROWS_OPERANDS)
+//   ADMM_MATS, ADMM_GT   what a restep refactors from (below)
 #define ADMM_STEP_PARAMS(TYPE)                                                                                                      \
     gbdpcg_handle_t h, ADMM_SIZES, uint32_t N, uint32_t batch, const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g,                \
         const TYPE *d_c, ADMM_SET(TYPE), const TYPE *d_rho, const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_lambda,     \
@@ -529,7 +632,30 @@ GBDPCG_PAIR_BOTH(kkt_resolve_shared, true, RESOLVE_PARAMS, RESOLVE_SETUP, RESOLV
 #define GBDPCG_ADMM_STEPS(NAME)                                                                                                     \
     GBDPCG_PAIR_BOTH(NAME, false, ADMM_STEP_PARAMS, ADMM_STEP_SETUP, ADMM_STEP_REFUSE)                                              \
     GBDPCG_PAIR_BOTH(NAME##_shared, true, ADMM_STEP_PARAMS, ADMM_STEP_SETUP, ADMM_STEP_REFUSE)
-// init and update of a family with rows: thin forwards to admm_rows_update_impl (init has neither d_z nor d_res)
+// One iteration with a new rho (admm_restep_impl): the list of the step with what the refactorisation writes no longer const,
+// ADMM_MATS (the original G, and for the families with rows the Gt formed from it) in front of d_Ginv, the kind of Phi^-1 behind
+// d_Pinv and the rule at the end.  ADMM_GT: the Gt of the family, nullptr for the box.  No _shared twin: one factorisation, one rho.
+#define ADMM_RULE(TYPE) TYPE ratio, uint32_t shift, TYPE rho_min, TYPE rho_max, int32_t *d_expo
+#define ADMM_RESTEP_PARAMS(TYPE)                                                                                                    \
+    gbdpcg_handle_t h, ADMM_SIZES, uint32_t N, uint32_t batch, ADMM_MATS(TYPE), TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_g,     \
+        const TYPE *d_c, ADMM_SET(TYPE), TYPE *d_rho, TYPE *d_S, TYPE *d_Pinv, gbdpcg_pinv_kind kind, TYPE *d_gamma,                \
+        TYPE *d_lambda, TYPE *d_r, TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, TYPE *d_z,  \
+        TYPE *d_w, TYPE *d_y, TYPE *d_gt, TYPE *d_res, ADMM_RULE(TYPE)
+#define ADMM_RESTEP_SETUP(TYPE, SHARED)                                                                                             \
+    ADMM_CONES                                                                                                                      \
+    const AdmmOperands<TYPE> ad{ADMM_OPERANDS};                                                                                     \
+    const RhoRule<TYPE> rule{ratio, shift, rho_min, rho_max, d_rho, d_expo};                                                        \
+    const Refactor<TYPE> f{d_G, ADMM_GT, d_S, d_Ginv, d_Pinv, kind};                                                                \
+    const KktOperands<TYPE> k{nu, d_Ginv, d_C, d_g, d_c, d_gamma, d_z};                                                             \
+    const PcgArgs<TYPE> a = PCG_ARGS(TYPE, nx);                                                                                     \
+    auto body = [&](hipStream_t s) { return admm_restep_impl<TYPE>(h, f, k, ad, rule, a, s); };
+#define ADMM_RESTEP_REFUSE(TYPE)                                                                                                    \
+    if (!out) return GBDPCG_ERR_INVALID;                                                                                            \
+    *out = nullptr;                                                                                                                 \
+    if (const gbdpcg_status st = admm_restep_refusal<TYPE>(h, f, k, ad, rule, a, false)) return st;
+#define GBDPCG_ADMM_RESTEPS(NAME) GBDPCG_PAIR_BOTH(NAME, false, ADMM_RESTEP_PARAMS, ADMM_RESTEP_SETUP, ADMM_RESTEP_REFUSE)
+// init, update and rebalance of a family with rows: thin forwards to admm_rows_update_impl (init has neither d_z nor d_res) and
+// admm_rows_rebalance_impl
 #define GBDPCG_ADMM_ROWS(NAME, SUF, TYPE)                                                                                           \
     gbdpcg_status gbdpcg_##NAME##_init_##SUF(gbdpcg_handle_t h, ADMM_SIZES, uint32_t N, uint32_t batch, const TYPE *d_g,            \
                                              ADMM_SET(TYPE), const TYPE *d_rho, TYPE *d_w, TYPE *d_y, TYPE *d_gt, void *stream)     \
@@ -546,6 +672,15 @@ GBDPCG_PAIR_BOTH(kkt_resolve_shared, true, RESOLVE_PARAMS, RESOLVE_SETUP, RESOLV
         ADMM_CONES                                                                                                                  \
         const AdmmOperands<TYPE> a{ADMM_OPERANDS};                                                                                  \
         return admm_rows_update_impl<TYPE>(h, nx, nu, N, batch, d_g, a, d_z, stream, false);                                        \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_##NAME##_rebalance_##SUF(gbdpcg_handle_t h, ADMM_SIZES, uint32_t N, uint32_t batch, const TYPE *d_g,       \
+                                                  ADMM_SET(TYPE), const TYPE *d_res, TYPE *d_rho, TYPE *d_w, TYPE *d_y, TYPE *d_gt, \
+                                                  ADMM_RULE(TYPE), void *stream)                                                    \
+    {                                                                                                                               \
+        ADMM_CONES                                                                                                                  \
+        const AdmmOperands<TYPE> a{d_lo, d_hi, d_rho, d_w, d_y, d_gt, const_cast<TYPE *>(d_res), ADMM_ROWS_OPERANDS};               \
+        const RhoRule<TYPE> rule{ratio, shift, rho_min, rho_max, d_rho, d_expo};                                                    \
+        return admm_rows_rebalance_impl<TYPE>(h, nx, nu, N, batch, d_g, a, rule, stream);                                           \
     }
 
 #define ADMM_SIZES uint32_t nx, uint32_t nu
@@ -564,11 +699,23 @@ GBDPCG_PAIR_BOTH(kkt_resolve_shared, true, RESOLVE_PARAMS, RESOLVE_SETUP, RESOLV
                                            TYPE *d_y, TYPE *d_gt, TYPE *d_res, void *stream)                                        \
     {                                                                                                                               \
         return admm_update_impl<TYPE>(h, nx, nu, N, batch, d_g, d_lo, d_hi, d_rho, d_z, d_w, d_y, d_gt, d_res, stream, false);      \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_rebalance_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,              \
+                                              const TYPE *d_g, const TYPE *d_res, TYPE *d_rho, const TYPE *d_w, TYPE *d_y,          \
+                                              TYPE *d_gt, ADMM_RULE(TYPE), void *stream)                                            \
+    {                                                                                                                               \
+        const RhoRule<TYPE> rule{ratio, shift, rho_min, rho_max, d_rho, d_expo};                                                    \
+        return admm_rebalance_impl<TYPE>(h, nx, nu, N, batch, d_g, d_res, d_w, d_y, d_gt, rule, stream);                            \
     }
+#define ADMM_MATS(TYPE) const TYPE *d_G
+#define ADMM_GT nullptr
 GBDPCG_ADMM(f32, float)
 GBDPCG_ADMM(f64, double)
 GBDPCG_ADMM_STEPS(admm_step)
+GBDPCG_ADMM_RESTEPS(admm_restep)
 #undef GBDPCG_ADMM
+#undef ADMM_MATS
+#undef ADMM_GT
 #undef ADMM_SIZES
 #undef ADMM_SET
 #undef ADMM_OPERANDS
@@ -576,7 +723,10 @@ GBDPCG_ADMM_STEPS(admm_step)
 // (admm_lin: ADMM_CONES stays empty)
 #define ADMM_SIZES uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu
 #define ADMM_SET(TYPE) const TYPE *d_E, const TYPE *d_lo, const TYPE *d_hi
-#define ADMM_OPERANDS d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res, true, d_E, mx, mu
+#define ADMM_OPERANDS d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res, ADMM_ROWS_OPERANDS
+#define ADMM_ROWS_OPERANDS true, d_E, mx, mu
+#define ADMM_MATS(TYPE) const TYPE *d_G, TYPE *d_Gt
+#define ADMM_GT d_Gt
 #define GBDPCG_ADMM_LIN(SUF, TYPE)                                                                                                  \
     gbdpcg_status gbdpcg_admm_lin_form_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,     \
                                              uint32_t batch, const TYPE *d_G, const TYPE *d_E, const TYPE *d_rho, TYPE *d_Gt,       \
@@ -588,24 +738,34 @@ GBDPCG_ADMM_STEPS(admm_step)
 GBDPCG_ADMM_LIN(f32, float)
 GBDPCG_ADMM_LIN(f64, double)
 GBDPCG_ADMM_STEPS(admm_lin_step)
+GBDPCG_ADMM_RESTEPS(admm_lin_restep)
 #undef GBDPCG_ADMM_LIN
 #undef ADMM_SIZES
 #undef ADMM_CONES
-#undef ADMM_OPERANDS
+#undef ADMM_ROWS_OPERANDS
 
-// (admm_soc: ADMM_SET stays that of admm_lin)
+// (admm_soc: ADMM_SET, ADMM_OPERANDS, ADMM_MATS and ADMM_GT stay those of admm_lin)
 #define ADMM_SIZES uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu
 #define ADMM_CONES const RowClasses cones{lx, qx, lu, qu};
-#define ADMM_OPERANDS d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res, true, d_E, mx, mu, &cones
+#define ADMM_ROWS_OPERANDS true, d_E, mx, mu, &cones
 GBDPCG_ADMM_ROWS(admm_soc, f32, float)
 GBDPCG_ADMM_ROWS(admm_soc, f64, double)
 GBDPCG_ADMM_STEPS(admm_soc_step)
+GBDPCG_ADMM_RESTEPS(admm_soc_restep)
 #undef ADMM_SIZES
 #undef ADMM_SET
 #undef ADMM_CONES
 #undef ADMM_OPERANDS
+#undef ADMM_ROWS_OPERANDS
+#undef ADMM_MATS
+#undef ADMM_GT
 #undef GBDPCG_ADMM_ROWS
 #undef GBDPCG_ADMM_STEPS
+#undef GBDPCG_ADMM_RESTEPS
+#undef ADMM_RULE
+#undef ADMM_RESTEP_PARAMS
+#undef ADMM_RESTEP_SETUP
+#undef ADMM_RESTEP_REFUSE
 
 // ---- the KKT backward pass: the adjoint solve + gradient launch as one call / one graph (the gradient launch alone is with the
 // single launches).  shared: one problem's Ginv, C, S, Pinv, and gG, gC summed over the batch.

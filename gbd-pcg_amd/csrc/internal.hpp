@@ -260,6 +260,14 @@ template <typename T>
 hipError_t launch_admm_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *g, const T *lo, const T *hi, const T *rho,
                               const T *z, T *w, T *y, T *gt, T *res, hipStream_t s, bool init);
 
+// ---- admm_rebalance.hip : adaptive rho by residual balancing in powers of two, one launch, one workgroup per problem.  From
+// r = res[2b], s = res[2b+1] and rho_b: rho_b <- rho_b 2^e with e in {+shift, -shift, 0} (the rule is in the head of the file and in
+// include/gbdpcg.h), y <- y 2^-e over `len` elements per problem, expo[b] = e.  box: len is that of g and gt <- fma(-rho_b, w - y, g)
+// is rebuilt in the same launch (w is read); otherwise g, w, gt are not looked at (may be null).  res is read only.
+template <typename T>
+hipError_t launch_admm_rebalance(uint64_t len, uint32_t batch, const T *g, const T *res, T *rho, const T *w, T *y, T *gt, T ratio,
+                                 uint32_t shift, T rho_min, T rho_max, int32_t *expo, hipStream_t s, bool box);
+
 // ---- admm_rows.hip : ADMM with stage-wise rows on E z, linear (lo <= E z <= hi) or in second-order cones; the layouts are in
 // include/gbdpcg.h, the lines that define every bit in the head of the file.  Two kernels:
 //     form:   Gt = G + rho_b E'E per diagonal block, one lane per entry (Gt may be G)

@@ -605,7 +605,7 @@ gbdpcg_status gbdpcg_kkt_residual_reg_f64(gbdpcg_handle_t h, uint32_t nx, uint32
  *    d_hi, d_rho [batch], d_w, d_y, d_gt and d_res stay per problem.  The caller fills d_rho with the rho the single matrices were
  *    formed with; nothing checks that.
  *  - the graphs keep the POINTER d_rho like gbdpcg_graph_create_kkt_step_reg_* (rewriting rho in place changes the update, not the
- *    matrices: a new rho needs gbdpcg_kkt_step_reg_* again); the constructors reserve what the solve needs, nothing allocates under
+ *    matrices: a new rho needs gbdpcg_kkt_step_reg_* again, or gbdpcg_admm_restep_* below, which also rescales y); the constructors reserve what the solve needs, nothing allocates under
  *    capture.  Replay the graph once per iteration and read d_res every few replays to stop.
  *  - d_rho, d_lo, d_hi are NOT validated on the device: lo > hi, NaN or a negative rho give what the formulas give, inside their
  *    own problem only.
@@ -922,6 +922,171 @@ gbdpcg_status gbdpcg_graph_create_admm_soc_step_shared_f64(gbdpcg_handle_t h, ui
                                                            uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
                                                            double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res,
                                                            gbdpcg_graph_t *out);
+
+/* Adaptive rho for the three ADMM families: residual balancing in powers of two, decided and applied on the device, and the
+ * iteration that refactors with the new rho.  The number of ADMM iterations depends on rho by orders of magnitude and the problems
+ * of a batch do not share one good value; these calls move rho_b per problem without a host round trip.
+ * THE RULE.  All quantities are of the call's type, every line is ONE IEEE operation or a comparison.  Per problem b the inputs are
+ * r = d_res[2b], s = d_res[2b+1] as the last update launch wrote them and rho = d_rho[b]; the host passes `ratio` (>= 1), `shift`
+ * (1 .. 16, tau = 2^shift) and the limits 0 < rho_min <= rho_max, both finite:
+ *     up = fl(rho tau)          dn = fl(rho (1/tau))                           tau and 1/tau are exact constants
+ *     if      r > fl(ratio s)  and  up <= rho_max :  rho' = up,  e = +shift
+ *     else if s > fl(ratio r)  and  dn >= rho_min :  rho' = dn,  e = -shift
+ *     else                                           rho' = rho, e = 0
+ *     y'_i = fl(y_i 2^-e)                            one multiplication; y is not touched in bits when e = 0
+ * The tests are comparisons, so a NaN in r, s or rho leaves the problem as it is (e = 0).  Scaling y keeps the multiplier
+ * mu = rho y the iteration carries: a caller who rewrites rho and forgets y restarts from a wrong multiplier.  Outputs: d_rho[b] =
+ * rho' in place (one lane writes it and d_expo[b] = e, int32, after the workgroup has read rho), d_y in place.  d_res is read, never
+ * written.  The rule's arguments always come in the order ratio, shift, rho_min, rho_max, d_expo.
+ *  - gbdpcg_admm_rebalance_* (box): ONE launch that additionally writes gt_i = fma(-rho', fl(w_i - y'_i), g_i), the line of
+ *    gbdpcg_admm_init_*.  d_w is read only: it lies in the box already (it was written by an update or an init).  For such a w the
+ *    bits of d_y, d_gt, d_rho and d_expo are those of the rows form (below) over the layout of g followed by gbdpcg_admm_init_*.
+ *  - gbdpcg_admm_lin_rebalance_*: the same launch without w, g, gt over the (mx + mu) N - mu rows of a problem, then
+ *    gbdpcg_admm_lin_init_* on the same stream, which rebuilds d_gt with the new rho and y.  With E = I its outputs have the bits of
+ *    the box call.
+ *  - gbdpcg_admm_soc_rebalance_*: the same through gbdpcg_admm_soc_init_*.  That init RE-PROJECTS an already projected w, as it
+ *    documents: on cone rows c s_i is rounded, so d_w may move by ulps.
+ *  - gbdpcg_admm_restep_*, gbdpcg_admm_lin_restep_*, gbdpcg_admm_soc_restep_*: one whole iteration with a new rho on one stream --
+ *    the family's rebalance; the refactorisation and solve with d_gt in the place of d_g; the family's update launch.  The box
+ *    refactors with gbdpcg_kkt_step_reg_* on d_G and d_rho; the families with rows form d_Gt from d_G with gbdpcg_admm_lin_form_* and
+ *    run gbdpcg_kkt_step_* on d_Gt.  The arguments are those of the family's step with d_G (rows: d_G, d_Gt) in front of d_Ginv,
+ *    `kind` (the Phi^-1 of the refactorisation) behind d_Pinv and the rule at the end; d_Ginv, d_S, d_Pinv and d_rho are written.
+ *    The results are bit-identical with the constituent calls made one after another.  The families with rows refuse d_Gt == d_G
+ *    with GBDPCG_ERR_INVALID: the next restep needs the original G.  EVERY restep refactors EVERY problem, whether its rho moved or
+ *    not: it costs a gbdpcg_kkt_step_* where a step costs a gbdpcg_kkt_resolve_*, so it is made once per P plain steps.
+ *  - gbdpcg_graph_create_admm*_restep_*: the graph forms.  They keep the POINTERS d_rho, d_res and d_expo: the decision is taken
+ *    from what d_res holds at replay.  *out is set to NULL before the first refusal.  Intended use: replay the family's step graph P
+ *    times, the restep graph once, and read d_res (and d_expo) as before.
+ *  - no _shared twins: not provided.  A shared batch has one factorisation and hence one rho.
+ * Refused with GBDPCG_ERR_INVALID before anything is written, reserved or captured: a null handle or pointer among those named
+ * (d_r, d_p and d_max_iter_exit may be NULL, d_C when N == 1; a restep needs d_Pinv and d_gamma), nx, nu, N or batch == 0, shift
+ * outside 1 .. 16, ratio < 1, rho_min <= 0, rho_max < rho_min, a limit that is not finite, a NaN among them; for the rows what
+ * gbdpcg_admm_lin_* / gbdpcg_admm_soc_* refuse.  A restep refuses everything its constituent calls would, every INVALID before every
+ * UNSUPPORTED. */
+gbdpcg_status gbdpcg_admm_rebalance_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_g,
+                                        const float *d_res, float *d_rho, const float *d_w, float *d_y, float *d_gt, float ratio,
+                                        uint32_t shift, float rho_min, float rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_admm_rebalance_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_g,
+                                        const double *d_res, double *d_rho, const double *d_w, double *d_y, double *d_gt,
+                                        double ratio, uint32_t shift, double rho_min, double rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_admm_lin_rebalance_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                            uint32_t batch, const float *d_g, const float *d_E, const float *d_lo, const float *d_hi,
+                                            const float *d_res, float *d_rho, float *d_w, float *d_y, float *d_gt, float ratio,
+                                            uint32_t shift, float rho_min, float rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_admm_lin_rebalance_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                            uint32_t batch, const double *d_g, const double *d_E, const double *d_lo,
+                                            const double *d_hi, const double *d_res, double *d_rho, double *d_w, double *d_y,
+                                            double *d_gt, double ratio, uint32_t shift, double rho_min, double rho_max,
+                                            int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_admm_soc_rebalance_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,
+                                            uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const float *d_g,
+                                            const float *d_E, const float *d_lo, const float *d_hi, const float *d_res, float *d_rho,
+                                            float *d_w, float *d_y, float *d_gt, float ratio, uint32_t shift, float rho_min,
+                                            float rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_admm_soc_rebalance_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,
+                                            uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const double *d_g,
+                                            const double *d_E, const double *d_lo, const double *d_hi, const double *d_res,
+                                            double *d_rho, double *d_w, double *d_y, double *d_gt, double ratio, uint32_t shift,
+                                            double rho_min, double rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_admm_restep_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_G,
+                                     float *d_Ginv, const float *d_C, const float *d_g, const float *d_c, const float *d_lo,
+                                     const float *d_hi, float *d_rho, float *d_S, float *d_Pinv, gbdpcg_pinv_kind kind,
+                                     float *d_gamma, float *d_lambda, float *d_r, float *d_p, float tol, uint32_t max_iter,
+                                     uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y, float *d_gt,
+                                     float *d_res, float ratio, uint32_t shift, float rho_min, float rho_max, int32_t *d_expo,
+                                     void *stream);
+gbdpcg_status gbdpcg_admm_restep_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_G,
+                                     double *d_Ginv, const double *d_C, const double *d_g, const double *d_c, const double *d_lo,
+                                     const double *d_hi, double *d_rho, double *d_S, double *d_Pinv, gbdpcg_pinv_kind kind,
+                                     double *d_gamma, double *d_lambda, double *d_r, double *d_p, double tol, uint32_t max_iter,
+                                     uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y,
+                                     double *d_gt, double *d_res, double ratio, uint32_t shift, double rho_min, double rho_max,
+                                     int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_restep_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                  const float *d_G, float *d_Ginv, const float *d_C, const float *d_g,
+                                                  const float *d_c, const float *d_lo, const float *d_hi, float *d_rho, float *d_S,
+                                                  float *d_Pinv, gbdpcg_pinv_kind kind, float *d_gamma, float *d_lambda, float *d_r,
+                                                  float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                                  uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y, float *d_gt,
+                                                  float *d_res, float ratio, uint32_t shift, float rho_min, float rho_max,
+                                                  int32_t *d_expo, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_restep_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                  const double *d_G, double *d_Ginv, const double *d_C, const double *d_g,
+                                                  const double *d_c, const double *d_lo, const double *d_hi, double *d_rho,
+                                                  double *d_S, double *d_Pinv, gbdpcg_pinv_kind kind, double *d_gamma,
+                                                  double *d_lambda, double *d_r, double *d_p, double tol, uint32_t max_iter,
+                                                  uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y,
+                                                  double *d_gt, double *d_res, double ratio, uint32_t shift, double rho_min,
+                                                  double rho_max, int32_t *d_expo, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_admm_lin_restep_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                         uint32_t batch, const float *d_G, float *d_Gt, float *d_Ginv, const float *d_C,
+                                         const float *d_g, const float *d_c, const float *d_E, const float *d_lo, const float *d_hi,
+                                         float *d_rho, float *d_S, float *d_Pinv, gbdpcg_pinv_kind kind, float *d_gamma,
+                                         float *d_lambda, float *d_r, float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                         uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res,
+                                         float ratio, uint32_t shift, float rho_min, float rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_admm_lin_restep_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                         uint32_t batch, const double *d_G, double *d_Gt, double *d_Ginv, const double *d_C,
+                                         const double *d_g, const double *d_c, const double *d_E, const double *d_lo,
+                                         const double *d_hi, double *d_rho, double *d_S, double *d_Pinv, gbdpcg_pinv_kind kind,
+                                         double *d_gamma, double *d_lambda, double *d_r, double *d_p, double tol, uint32_t max_iter,
+                                         uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y,
+                                         double *d_gt, double *d_res, double ratio, uint32_t shift, double rho_min, double rho_max,
+                                         int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_lin_restep_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                      uint32_t N, uint32_t batch, const float *d_G, float *d_Gt, float *d_Ginv,
+                                                      const float *d_C, const float *d_g, const float *d_c, const float *d_E,
+                                                      const float *d_lo, const float *d_hi, float *d_rho, float *d_S, float *d_Pinv,
+                                                      gbdpcg_pinv_kind kind, float *d_gamma, float *d_lambda, float *d_r, float *d_p,
+                                                      float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                                      float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res, float ratio,
+                                                      uint32_t shift, float rho_min, float rho_max, int32_t *d_expo,
+                                                      gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_lin_restep_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                      uint32_t N, uint32_t batch, const double *d_G, double *d_Gt, double *d_Ginv,
+                                                      const double *d_C, const double *d_g, const double *d_c, const double *d_E,
+                                                      const double *d_lo, const double *d_hi, double *d_rho, double *d_S,
+                                                      double *d_Pinv, gbdpcg_pinv_kind kind, double *d_gamma, double *d_lambda,
+                                                      double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                      uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y, double *d_gt,
+                                                      double *d_res, double ratio, uint32_t shift, double rho_min, double rho_max,
+                                                      int32_t *d_expo, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_admm_soc_restep_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,
+                                         uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const float *d_G,
+                                         float *d_Gt, float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                         const float *d_E, const float *d_lo, const float *d_hi, float *d_rho, float *d_S,
+                                         float *d_Pinv, gbdpcg_pinv_kind kind, float *d_gamma, float *d_lambda, float *d_r,
+                                         float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                         float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res, float ratio, uint32_t shift,
+                                         float rho_min, float rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_admm_soc_restep_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t lx,
+                                         uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N, uint32_t batch, const double *d_G,
+                                         double *d_Gt, double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                         const double *d_E, const double *d_lo, const double *d_hi, double *d_rho, double *d_S,
+                                         double *d_Pinv, gbdpcg_pinv_kind kind, double *d_gamma, double *d_lambda, double *d_r,
+                                         double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                         double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res, double ratio,
+                                         uint32_t shift, double rho_min, double rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_soc_restep_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                      uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N,
+                                                      uint32_t batch, const float *d_G, float *d_Gt, float *d_Ginv,
+                                                      const float *d_C, const float *d_g, const float *d_c, const float *d_E,
+                                                      const float *d_lo, const float *d_hi, float *d_rho, float *d_S, float *d_Pinv,
+                                                      gbdpcg_pinv_kind kind, float *d_gamma, float *d_lambda, float *d_r, float *d_p,
+                                                      float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                                      float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res, float ratio,
+                                                      uint32_t shift, float rho_min, float rho_max, int32_t *d_expo,
+                                                      gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_soc_restep_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                      uint32_t lx, uint32_t qx, uint32_t lu, uint32_t qu, uint32_t N,
+                                                      uint32_t batch, const double *d_G, double *d_Gt, double *d_Ginv,
+                                                      const double *d_C, const double *d_g, const double *d_c, const double *d_E,
+                                                      const double *d_lo, const double *d_hi, double *d_rho, double *d_S,
+                                                      double *d_Pinv, gbdpcg_pinv_kind kind, double *d_gamma, double *d_lambda,
+                                                      double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                      uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y, double *d_gt,
+                                                      double *d_res, double ratio, uint32_t shift, double rho_min, double rho_max,
+                                                      int32_t *d_expo, gbdpcg_graph_t *out);
 
 /* The backward pass: gradients of a scalar through (G, C, g, c) -> (z, lambda), on the device.  Forward convention as above:
  * G z + g + C' lambda = 0, C z = c.  For a scalar l with upstream gradients gz = dl/dz (layout of d_g) and glam = dl/dlambda (layout
