@@ -2,8 +2,10 @@
 
 Plumbing over binding.Solver: the forward pass is gbdpcg_kkt_step_* (gbdpcg_kkt_step_reg_* when rho is given; for a shared-matrix
 batch gbdpcg_kkt_step_* at batch 1 followed by gbdpcg_kkt_resolve_shared_*), the backward pass is gbdpcg_kkt_backward_* on the S,
-Phi^-1 and G^-1 the forward pass left behind -- one adjoint solve and one gradient launch (include/gbdpcg.h has the formulas).
-Nothing here computes a gradient in torch except dl/drho = a_z' z, one dot product per problem.  There is no CPU path.
+Phi^-1 and G^-1 the forward pass left behind -- one adjoint solve and one gradient launch (include/gbdpcg.h has the formulas); for a
+shared-matrix batch the two are gbdpcg_kkt_resolve_shared_* and gbdpcg_kkt_grad_shared_*, with the adjoint pairs of problems outside
+the loss zeroed in between.  Nothing here computes a gradient in torch except dl/drho = a_z' z, one dot product per problem, and the
+selects that give problems with zero cotangents zero gradients.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -57,15 +59,26 @@ class _KktSolve(torch.autograd.Function):
         need_G, need_C = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and N > 1
         gG = torch.empty(mats * sz["G"], dtype=z.dtype, device=z.device) if need_G else None
         gC = torch.empty(mats * sz["C"], dtype=z.dtype, device=z.device) if need_C else None
-        if need_G or need_C:
-            back = solver.kkt_backward_shared if shared else solver.kkt_backward
-            back(nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, gG, gC, tol=tol, max_iter=max_iter)
-        else:   # only the adjoint pair is asked for: the solve alone
+        # A problem that does not enter the loss (padding, a mask) has an exactly zero right-hand side: the adjoint solve starts from a
+        # zero residual and returns NaN for it (the solve's rule, include/gbdpcg.h), where the gradients are exactly zero.  The mask
+        # is a device tensor and the selects are stream-ordered: nothing here waits for the device.
+        live = ((gz.view(batch, -1) != 0).any(1) | (nglam.view(batch, -1) != 0).any(1)).view(batch, 1)
+
+        def keep(t):
+            return None if t is None else torch.where(live, t.view(batch, -1), t.new_zeros(())).view(-1)
+
+        if (need_G or need_C) and not shared:
+            solver.kkt_backward(nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, gG, gC, tol=tol, max_iter=max_iter)
+            az, alam, gG, gC = keep(az), keep(alam), keep(gG), keep(gC)
+        else:   # the adjoint solve alone; the single gG, gC of a shared batch are summed from the pairs behind the mask
             resolve = solver.kkt_resolve_shared if shared else solver.kkt_resolve
             resolve(nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, alam, az, tol=tol, max_iter=max_iter)
+            az, alam = keep(az), keep(alam)
+            if need_G or need_C:
+                solver.kkt_grad_shared(nx, nu, N, batch, z, lam, az, alam, gG=gG, gC=gC, want="")
         if ctx.needs_input_grad[1] and N == 1:
             gC = torch.zeros(mats * sz["C"], dtype=z.dtype, device=z.device)
-        grho = (az.view(batch, -1) * z.view(batch, -1)).sum(1) if has_rho and ctx.needs_input_grad[4] else None
+        grho = keep((az.view(batch, -1) * z.view(batch, -1)).sum(1)) if has_rho and ctx.needs_input_grad[4] else None
         grads = [t if t is None else t.view(s) for t, s in zip((gG, gC, az, -alam), ctx.shapes)]
         return (*grads, grho) + (None,) * 8
 
@@ -77,7 +90,15 @@ def kkt_solve(solver, nx, nu, N, G, C, g, c, rho=None, shared=False, tol=1e-6, m
     problem's extent.  rho: [batch], the per-problem regularisation of gbdpcg_kkt_step_reg_* (problem b is solved with
     G_b + rho_b I).  shared=True: G and C are ONE problem's blocks, used by every problem of the batch, and their gradients are
     the sums over the batch.  tol, max_iter: the PCG settings of the forward and of the adjoint solve.  The gradient in G is
-    the symmetrised one (the library reads G as symmetric).  The handle's symmetric mode and path are left as found."""
+    the symmetrised one (the library reads G as symmetric).  The handle's symmetric mode and path are left as found.
+
+    Exactly zero right-hand sides.  Forward: a problem whose gamma = -(c + C G^-1 g) is exactly zero (g = 0 and c = 0, say) starts
+    the PCG from a zero residual and, by the reference's rule (0/0 in the first step; include/gbdpcg.h), comes back with z and
+    lambda NaN in every entry where the answer is zero.  That is confined to its problem -- the others keep every bit -- and shows on
+    the device as max_iter_exit = 1 of the step and as NaN norms from Solver.kkt_residual; kkt_solve does not repair it.  Backward:
+    a problem whose rows of dl/dz and dl/dlambda are exactly zero (it does not enter the loss: padding, a per-sample mask) gets
+    exactly zero gradients in g, c, rho and its rows of G and C, and contributes exact zeros to the summed gradients of a shared
+    batch; the mask is built and applied on the device, in stream order."""
     if not isinstance(solver, binding.Solver):
         raise TypeError("kkt_solve: solver is a binding.Solver")
     sz = _sizes(nx, nu, N)

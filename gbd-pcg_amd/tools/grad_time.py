@@ -8,8 +8,12 @@ Per precision at 1024 x (nx 14, nu 7, N 128): windows of K calls between two dev
     the kkt_backward graph replay next to the kkt_resolve graph replay of the same run, alternating (both from lambda = 0)
     the same gradients in plain torch: what a caller writes today from the (z, lambda, a_z, a_lambda) the solves return -- batched
     outer products per block, packed into the layouts of G and C
+    loss.backward() through gbd_pcg_amd.autograd.kkt_solve (l = 1/2 ||z||^2; a fresh forward pass outside the timed span each
+    time), and, with --against FILE, the same through another version of autograd.py (the parent commit's, say:
+    git show HEAD~1:gbd-pcg_amd/autograd.py > FILE), the two alternating in one run
 The grad launch is reported against the bytes it must write (reads are 0.5 % of that) as a fraction of the 8 TB/s HBM peak."""
 import argparse
+import importlib.util
 import statistics
 import sys
 
@@ -17,7 +21,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, __file__.rsplit("/gbd-pcg_amd/", 1)[0])
-from gbd_pcg_amd import binding  # noqa: E402
+from gbd_pcg_amd import autograd, binding  # noqa: E402
 from oracle import schur_oracle as so  # noqa: E402
 
 HBM_PEAK = 8.0e12   # bytes / s
@@ -52,7 +56,42 @@ def torch_grads(nx, nu, N, B, z, lam, az, alam):
     return gG.reshape(-1).contiguous(), gC.reshape(B, (N - 1) * sc).reshape(-1).contiguous()
 
 
-def one_precision(s, nx, nu, N, B, dtype, a):
+def backward_window(mod, s, nx, nu, N, G, C, g, c, a, count):
+    """ms per loss.backward() of mod.kkt_solve: device time between an event in front of the call and one behind it."""
+    total = 0.0
+    for _ in range(count):
+        z, _ = mod.kkt_solve(s, nx, nu, N, G, C, g, c, tol=a.tol, max_iter=a.max_iter)
+        loss = 0.5 * (z * z).sum()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        loss.backward()
+        e1.record()
+        e1.synchronize()
+        total += e0.elapsed_time(e1)
+        for t in (G, C, g, c):
+            t.grad = None
+    return total / count
+
+
+def autograd_backward(s, nx, nu, N, G, C, g, c, a, against):
+    mods = {"this tree": autograd}
+    if against is not None:
+        mods[a.against] = against
+    leaves = [t.clone().requires_grad_() for t in (G, C, g, c)]
+    t = {k: [] for k in mods}
+    for m in mods.values():
+        backward_window(m, s, nx, nu, N, *leaves, a, a.warmup)
+    for _ in range(a.rounds):
+        for k, m in mods.items():
+            t[k].append(backward_window(m, s, nx, nu, N, *leaves, a, a.steps))
+    for k, v in t.items():
+        print(f"  autograd loss.backward(), {k:<12} {stat(v)}")
+    if against is not None:
+        m0, m1 = statistics.median(t["this tree"]), statistics.median(t[a.against])
+        print(f"  this tree - {a.against}: {1e3 * (m0 - m1):.1f} us ({100.0 * (m0 - m1) / m1:.1f} %)")
+
+
+def one_precision(s, nx, nu, N, B, dtype, a, against=None):
     td = torch.float32 if dtype == np.float32 else torch.float64
     base = so.gen(nx, nu, N, seed=77, batch=8, dtype=dtype)
     arr = {k: np.tile(base[k], ((B + 7) // 8, 1))[:B] for k in "GCgc"}
@@ -106,6 +145,7 @@ def one_precision(s, nx, nu, N, B, dtype, a):
     print(f"  the same gradients in torch    {stat(t['torch'])}; {m['torch'] / m['grad']:.1f} x the kkt_grad launch")
     for gr in (g_res, g_back):
         gr.close()
+    autograd_backward(s, nx, nu, N, G, C, g, c, a, against)
 
 
 def main():
@@ -116,14 +156,20 @@ def main():
     ap.add_argument("--tol", type=float, default=1e-6)
     ap.add_argument("--max-iter", type=int, default=25)
     ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--against", default=None, help="another version of autograd.py to time loss.backward() against")
     a = ap.parse_args()
+    against = None
+    if a.against:
+        spec = importlib.util.spec_from_file_location("gbd_pcg_amd.autograd_against", a.against)
+        against = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(against)
     assert torch.cuda.is_available(), "needs the MI355X: there is no CPU path"
     s = binding.Solver(0)
     print(f"# grad_time.py --warmup {a.warmup} --steps {a.steps} --rounds {a.rounds} --tol {a.tol} --max-iter {a.max_iter} "
           f"--batch {a.batch}; {torch.cuda.get_device_name(0)}; {s.lib.gbdpcg_version().decode()}")
     for dtype in (np.float32, np.float64):
         print(f"{a.batch} x (nx 14, nu 7, N 128) {np.dtype(dtype).name}")
-        one_precision(s, 14, 7, 128, a.batch, dtype, a)
+        one_precision(s, 14, 7, 128, a.batch, dtype, a, against)
     s.close()
     return 0
 

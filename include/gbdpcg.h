@@ -191,7 +191,12 @@ gbdpcg_status gbdpcg_spmv_f64(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_
  *   d_max_iter_exit [batch] out: 1 if the loop ran out, 0 if converged (pcg.cuh:212), may be NULL
  * d_Pinv == NULL means the identity preconditioner.  The reference's scratch arguments
  * d_v_temp / d_eta_new_temp (interface.cuh:101-102) have no counterpart: dot products are
- * reduced on chip.  Asynchronous on `stream`; no host synchronisation. */
+ * reduced on chip.  Asynchronous on `stream`; no host synchronisation.
+ * A start from an exactly zero preconditioned residual (gamma == 0 with d_lambda == 0, or a warm start that solves the system
+ * exactly) follows the reference's rule as well (pcg.cuh:169,195): the first alpha is 0/0, so lambda, r and p of THAT problem
+ * come back NaN in every entry, |NaN| < tol is false, d_iters = max_iter and d_max_iter_exit = 1.  It is confined to its
+ * problem: the other problems of the batch keep every bit, and nothing stays behind in the handle.  Detect it on the device
+ * by d_max_iter_exit, or by the NaN norms gbdpcg_kkt_residual_* reports for such a point. */
 gbdpcg_status gbdpcg_solve_f32(gbdpcg_handle_t h, uint32_t n, uint32_t N, uint32_t batch,
                                const float *d_S, const float *d_Pinv, const float *d_gamma,
                                float *d_lambda, float *d_r, float *d_p, float tol,
@@ -339,7 +344,19 @@ gbdpcg_status gbdpcg_recover_primal_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t
  * symmetric mode the solve runs its resident symmetric kernels without a test launch of its own) and iterates from the
  * d_lambda it finds (warm start), gbdpcg_recover_primal_* writes the primal step z.  Same results as the three calls.
  * Every buffer is the caller's (layouts above); d_r, d_p may be NULL as in gbdpcg_solve_*.  Replay the graph after
- * rewriting G, C, g, c (and lambda, if no warm start is wanted) in place. */
+ * rewriting G, C, g, c (and lambda, if no warm start is wanted) in place.
+ * Exactly zero right-hand sides.  A problem with g = 0 and c = 0 (a regulator at its set-point), or any g, c whose
+ * gamma = -(c + C G^-1 g) is exactly zero, started from lambda = 0 has the true answer z = 0, lambda = 0 -- and does NOT get it:
+ * the gamma written is exactly zero, the solve starts from a zero residual and returns what the exit rule of gbdpcg_solve_*
+ * above states (the reference's rule), so d_lambda and d_z of that problem are NaN in every entry, d_iters = max_iter and
+ * d_max_iter_exit = 1.  The same holds for gbdpcg_kkt_step_reg_*, gbdpcg_kkt_resolve_* (also for a warm start that already solves
+ * the system exactly), the _shared twins, every gbdpcg_admm_*_step_* whose shifted gradient and c are zero, the backward pass on a
+ * zero cotangent pair (gbd_pcg_amd.autograd masks those problems), and every graph form.  The mixed-precision refinement at a point
+ * whose fp64 defect is exactly zero writes d_res = (0, 0), e = 0 and a zero correction system, whose solve returns NaN;
+ * gbdpcg_kkt_refine_apply then DESTROYS the point, which was exact: test d_res before applying.  In every case the damage is
+ * confined to its problem: the other problems of the batch are bit-identical with a batch that has a regular problem in that
+ * place, and nothing stays behind in the handle.  On the device the case shows as d_max_iter_exit = 1 and as NaN in both norms of
+ * gbdpcg_kkt_residual_* for that problem (tests/test_gpu_kkt_degenerate.py). */
 gbdpcg_status gbdpcg_kkt_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_G,
                                   const float *d_C, const float *d_g, const float *d_c, float *d_S, float *d_gamma,
                                   float *d_Ginv, float *d_Pinv, gbdpcg_pinv_kind kind, float *d_lambda, float *d_r, float *d_p,

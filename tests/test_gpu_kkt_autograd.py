@@ -51,15 +51,23 @@ def problem(nx, nu, N, B, mode, seed=0):
     return d, wz, wl, rho, refs
 
 
-def run(solver, nx, nu, N, B, dtype, mode, seed=0):
-    """kkt_solve and backward on the device; returns the gradients as numpy arrays and (z, lambda)."""
+def run(solver, nx, nu, N, B, dtype, mode, seed=0, live=None, with_lam=True):
+    """kkt_solve and backward on the device; returns the gradients as numpy arrays and (z, lambda).  live: the problems that enter
+    the loss (all of them when None); with_lam=False leaves lambda out of the loss."""
     d, wz, wl, rho, _ = problem(nx, nu, N, B, mode, seed)
     mats = 1 if mode == "shared" else B
     t = lambda a: torch.from_numpy(np.array(a, dtype=dtype).reshape(-1)).cuda().requires_grad_()   # noqa: E731
     G, C, g, c = t(d["G"][:mats]), t(d["C"][:mats]), t(d["g"]), t(d["c"])
     r = t(rho) if mode == "rho" else None
     z, lam = autograd.kkt_solve(solver, nx, nu, N, G, C, g, c, rho=r, shared=mode == "shared", tol=PCG_TOL[dtype], max_iter=MAX_ITER)
-    loss = (t(wz).detach() * z).sum() + (t(wl).detach() * lam).sum() + 0.5 * (z * z).sum()
+    if live is None and with_lam:
+        loss = (t(wz).detach() * z).sum() + (t(wl).detach() * lam).sum() + 0.5 * (z * z).sum()
+    else:
+        idx = torch.tensor(list(range(B) if live is None else live), dtype=torch.long, device="cuda")
+        zs, ls = z.view(B, -1)[idx], lam.view(B, -1)[idx]
+        loss = (t(wz).detach().view(B, -1)[idx] * zs).sum() + 0.5 * (zs * zs).sum()
+        if with_lam:
+            loss = loss + (t(wl).detach().view(B, -1)[idx] * ls).sum()
     loss.backward()
     torch.cuda.synchronize()
     n = lambda x: None if x is None else x.detach().cpu().numpy().astype(F64)   # noqa: E731
@@ -129,3 +137,70 @@ def test_second_backward_on_the_same_solver(solver, dtype):
     again = run(solver, nx, nu, N, B, dtype, "plain")
     for k in ("z", "lam", "G", "C", "g", "c"):
         assert np.array_equal(first[k], again[k]), k
+
+
+# ---- problems that do not enter the loss: their adjoint right-hand side is exactly zero, and so are their gradients
+MASK_SHAPES = [(2, 1, 3, 7), (5, 2, 9, 3), (14, 7, 24, 5)]
+PER_PROBLEM = {"plain": ("G", "C", "g", "c"), "rho": ("G", "C", "g", "c", "rho"), "shared": ("g", "c")}
+
+
+def rows(got, k, B):
+    return got[k].reshape(B, -1)
+
+
+def check_masked(nx, nu, N, B, dtype, mode, got, full, refs, live, what):
+    """Masked problems: exact zeros.  Live problems: the bits of the run in which every problem enters the loss (per-problem
+    gradients), and check()'s bound against the twin, summed over the live problems for the single G and C of the shared form."""
+    dead = [b for b in range(B) if b not in live]
+    for k in ("G", "C", "g", "c", "rho"):
+        if got[k] is not None:
+            assert np.isfinite(got[k]).all(), (what, k)
+    for k in PER_PROBLEM[mode]:
+        assert not rows(got, k, B)[dead].any(), (what, k)
+        if full is not None:
+            assert np.array_equal(rows(got, k, B)[live], rows(full, k, B)[live]), (what, k)
+    for k in ("z", "lam"):
+        assert full is None or np.array_equal(got[k], full[k]), (what, k)
+    if not live:
+        assert not got["G"].any() and not got["C"].any(), what
+        return
+    sub = {k: (None if got[k] is None else got[k] if mode == "shared" and k in "GC" else rows(got, k, B)[live].reshape(-1))
+           for k in ("G", "C", "g", "c", "rho")}
+    sub.update(z=got["z"], lam=got["lam"])
+    check(nx, nu, N, len(live), dtype, mode, sub, [refs[b] for b in live], what)
+
+
+@pytest.mark.parametrize("mode", ["plain", "rho", "shared"])
+@pytest.mark.parametrize("dtype", [F32, F64])
+@pytest.mark.parametrize("nx,nu,N,B", MASK_SHAPES)
+def test_problems_outside_the_loss_get_zero_gradients(solver, nx, nu, N, B, dtype, mode):
+    live = list(range(0, B, 2))
+    full = run(solver, nx, nu, N, B, dtype, mode) if mode != "shared" else None
+    got = run(solver, nx, nu, N, B, dtype, mode, live=live)
+    if mode == "shared":     # the forward pass is that of the unmasked run; its per-problem gradients serve as `full`
+        full = run(solver, nx, nu, N, B, dtype, mode)
+    check_masked(nx, nu, N, B, dtype, mode, got, full, problem(nx, nu, N, B, mode)[4], live, "masked")
+
+
+@pytest.mark.parametrize("mode", ["plain", "rho", "shared"])
+@pytest.mark.parametrize("dtype", [F32, F64])
+def test_every_problem_outside_the_loss(solver, dtype, mode):
+    nx, nu, N, B = 5, 2, 9, 3
+    got = run(solver, nx, nu, N, B, dtype, mode, live=[])
+    check_masked(nx, nu, N, B, dtype, mode, got, None, None, [], "all masked")
+    for k in ("G", "C", "g", "c") + (("rho",) if mode == "rho" else ()):
+        assert got[k] is not None and not got[k].any(), k
+
+
+@pytest.mark.parametrize("mode", ["plain", "shared"])
+@pytest.mark.parametrize("dtype", [F32, F64])
+def test_loss_without_lambda_and_masked_problems(solver, dtype, mode):
+    """dl/dlambda is absent (None, or the zeros autograd materialises for an unused output): the mask is built from gz alone."""
+    nx, nu, N, B = 5, 2, 9, 3
+    live = [0, 2]
+    d, wz, wl, rho, _ = problem(nx, nu, N, B, mode)
+    refs = [kgr.reference(nx, nu, N, d["G"][0 if mode == "shared" else b], d["C"][0 if mode == "shared" else b], d["g"][b], d["c"][b],
+                          wz[b], 0.0 * wl[b], 0.0, quad=1.0) for b in range(B)]
+    full = run(solver, nx, nu, N, B, dtype, mode, with_lam=False)
+    got = run(solver, nx, nu, N, B, dtype, mode, live=live, with_lam=False)
+    check_masked(nx, nu, N, B, dtype, mode, got, full, refs, live, "no lambda in the loss")
