@@ -64,6 +64,11 @@ SYMBOLS = [
     "gbdpcg_graph_create_admm_lin_restep_f32", "gbdpcg_graph_create_admm_lin_restep_f64",
     "gbdpcg_admm_soc_restep_f32", "gbdpcg_admm_soc_restep_f64",
     "gbdpcg_graph_create_admm_soc_restep_f32", "gbdpcg_graph_create_admm_soc_restep_f64",
+    # soft (L1-penalised) bounds: the box and the linear rows with kappa behind hi
+    *[f"gbdpcg_{pre}{fam}_{op}_{suf}" for fam in ("admm_soft", "admm_lin_soft")
+      for pre, op in (("", "init"), ("", "update"), ("", "step"), ("graph_create_", "step"), ("", "step_shared"),
+                      ("graph_create_", "step_shared"), ("", "restep"), ("graph_create_", "restep")) for suf in ("f32", "f64")],
+    "gbdpcg_admm_lin_soft_rebalance_f32", "gbdpcg_admm_lin_soft_rebalance_f64",
     "gbdpcg_kkt_grad_f32", "gbdpcg_kkt_grad_f64", "gbdpcg_kkt_grad_shared_f32", "gbdpcg_kkt_grad_shared_f64",
     "gbdpcg_kkt_backward_f32", "gbdpcg_kkt_backward_f64", "gbdpcg_kkt_backward_shared_f32", "gbdpcg_kkt_backward_shared_f64",
     "gbdpcg_graph_create_kkt_backward_f32", "gbdpcg_graph_create_kkt_backward_f64",
@@ -107,10 +112,13 @@ def _resolve_argtypes(lib):
         #   init    h, nx, nu, [sizes], N, batch | g | [E], lo, hi, rho | w, y, gt | stream
         #   update  ...                          | g | [E], lo, hi, rho | z, w, y, gt, res | stream
         #   step    ...             | Ginv, C, g, c | [E], lo, hi, rho | the solve's arguments | w, y, gt, res | stream / graph out
+        # The soft twins (admm_soft, admm_lin_soft) put kappa directly behind hi, everywhere; the soft box has no rebalance of its
+        # own (gbdpcg_admm_rebalance_* is it).
         sizes = [vp, u32, u32, u32, u32]
-        for fam, extra in (("admm", []), ("admm_lin", [u32, u32]), ("admm_soc", [u32] * 6)):   # mx, mu | lx, qx, lu, qu
+        for fam, extra, soft in (("admm", [], False), ("admm_lin", [u32, u32], False), ("admm_soc", [u32] * 6, False),   # mx, mu | lx, qx, lu, qu
+                                 ("admm_soft", [], True), ("admm_lin_soft", [u32, u32], True)):
             fsizes = [vp, u32, u32] + extra + [u32, u32]
-            fset = ([vp] if extra else []) + [vp, vp, vp]
+            fset = ([vp] if extra else []) + [vp, vp] + ([vp] if soft else []) + [vp]
             getattr(lib, f"gbdpcg_{fam}_init_{suf}").argtypes = fsizes + [vp] + fset + [vp, vp, vp] + [vp]
             getattr(lib, f"gbdpcg_{fam}_update_{suf}").argtypes = fsizes + [vp] + fset + [vp, vp, vp, vp, vp] + [vp]
             for name in (f"{fam}_step", f"{fam}_step_shared"):
@@ -121,8 +129,9 @@ def _resolve_argtypes(lib):
             #   rebalance  ...                   | g | [E, lo, hi], res, rho | w, y, gt | rule | stream
             #   restep     ...   | G, [Gt], Ginv, C, g, c | [E], lo, hi, rho | S, Pinv, kind, the rest of the solve | w, y, gt, res | rule |
             rule = [ft, u32, ft, ft, vp]
-            getattr(lib, f"gbdpcg_{fam}_rebalance_{suf}").argtypes = (fsizes + [vp] + (fset[:-1] if extra else []) + [vp, vp] + [vp, vp, vp] +
-                                                                     rule + [vp])
+            if extra or not soft:
+                getattr(lib, f"gbdpcg_{fam}_rebalance_{suf}").argtypes = (fsizes + [vp] + (fset[:-1] if extra else []) + [vp, vp] +
+                                                                         [vp, vp, vp] + rule + [vp])
             restep_args = (fsizes + [vp] + ([vp] if extra else []) + [vp, vp, vp, vp] + fset + [vp, vp, ctypes.c_int] + solve[2:] +
                            [vp, vp, vp, vp] + rule)
             getattr(lib, f"gbdpcg_{fam}_restep_{suf}").argtypes = restep_args + [vp]
@@ -652,28 +661,30 @@ class Solver:
     # One set of helpers for the three families.  rows = (mx, mu, E) for the calls with stage-wise rows (lo, hi, w, y then have the
     # layout of the rows), cones = (lx, qx, lu, qu) next to rows for the calls with cone rows; `name` ends in "shared" for the twins.
     def _admm_step_args(self, name, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters, mie,
-                        z, w, y, gt, res, rows=None, cones=None):
-        """(suffix, the argument tuple up to d_res, the tensors a graph has to keep alive)."""
+                        z, w, y, gt, res, rows=None, cones=None, kappa=None):
+        """(suffix, the argument tuple up to d_res, the tensors a graph has to keep alive).  kappa: the soft families, behind hi."""
         suf, _ = _suffix(g)
         assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == g.dtype
         sizes, E = (), ()
+        soft = () if kappa is None else (kappa,)
         if rows is None:
             assert cones is None
-            self._box(g, batch, lo, hi, z, w, y, gt)
+            self._box(g, batch, lo, hi, z, w, y, gt, *soft)
         else:
             mx, mu, E = rows
-            self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y), (g, z, gt), mats=1 if name.endswith("shared") else None)
+            self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y) + soft, (g, z, gt), mats=1 if name.endswith("shared") else None)
             sizes, E = (mx, mu), (E,)
             if cones is not None:
                 assert len(cones) == 4
                 sizes += tuple(int(v) for v in cones)
         args = ((self.h, nx, nu) + sizes + (N, batch, _p(Ginv), _p(C), _p(g), _p(c)) + tuple(_p(t) for t in E) +
-                (_p(lo), _p(hi), _p(self._rho(rho, batch, g)), _p(S), _p(Pinv), _p(gamma), _p(lam), _p(r), _p(p), tol, max_iter,
+                (_p(lo), _p(hi)) + tuple(_p(t) for t in soft) +
+                (_p(self._rho(rho, batch, g)), _p(S), _p(Pinv), _p(gamma), _p(lam), _p(r), _p(p), tol, max_iter,
                  _p(iters), _p(mie), _p(z), _p(w), _p(y), _p(gt), _p(res)))
-        return suf, args, (Ginv, C, g, c) + E + (lo, hi, rho, S, Pinv, gamma, lam, r, p, iters, mie, z, w, y, gt, res)
+        return suf, args, (Ginv, C, g, c) + E + (lo, hi) + soft + (rho, S, Pinv, gamma, lam, r, p, iters, mie, z, w, y, gt, res)
 
     def _admm_step(self, name, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, r, p, tol,
-                   max_iter, iters, max_iter_exit, stream, rows=None, cones=None):
+                   max_iter, iters, max_iter_exit, stream, rows=None, cones=None, kappa=None):
         import torch
         if iters is None:
             iters = torch.zeros(batch, dtype=torch.int32, device=g.device)
@@ -682,14 +693,14 @@ class Solver:
         if res is None:
             res = torch.empty(batch, 2, dtype=g.dtype, device=g.device)
         suf, args, _ = self._admm_step_args(name, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter,
-                                            iters, max_iter_exit, z, w, y, gt, res, rows, cones)
+                                            iters, max_iter_exit, z, w, y, gt, res, rows, cones, kappa)
         self._check(getattr(self.lib, f"gbdpcg_{name}_{suf}")(*args, self._stream(stream)), name)
         return iters, max_iter_exit, res.view(batch, 2)
 
     def _graph_admm_step(self, name, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
-                         max_iter_exit, z, w, y, gt, res, rows=None, cones=None):
+                         max_iter_exit, z, w, y, gt, res, rows=None, cones=None, kappa=None):
         suf, args, keep = self._admm_step_args(name, nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
-                                               max_iter, iters, max_iter_exit, z, w, y, gt, res, rows, cones)
+                                               max_iter, iters, max_iter_exit, z, w, y, gt, res, rows, cones, kappa)
         gr = ctypes.c_void_p()
         self._check(getattr(self.lib, f"gbdpcg_graph_create_{name}_{suf}")(*args, ctypes.byref(gr)), f"graph_create_{name}")
         return Graph(self, gr, keep=keep)
@@ -882,12 +893,13 @@ class Solver:
         return expo
 
     def _rows_rebalance(self, name, sizes, nx, nu, mx, mu, N, batch, g, E, lo, hi, res, rho, w, y, gt, expo, ratio, shift, rho_min, rho_max,
-                        stream):
+                        stream, kappa=None):
         suf, _ = _suffix(g)
-        self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y), (g, gt))
+        soft = () if kappa is None else (kappa,)
+        self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y) + soft, (g, gt))
         expo = self._expo(expo, batch, g)
         fn = getattr(self.lib, f"gbdpcg_{name}_{suf}")
-        self._check(fn(self.h, nx, nu, *sizes, N, batch, _p(g), _p(E), _p(lo), _p(hi), _p(self._res(res, batch, g)),
+        self._check(fn(self.h, nx, nu, *sizes, N, batch, _p(g), _p(E), _p(lo), _p(hi), *(_p(t) for t in soft), _p(self._res(res, batch, g)),
                        _p(self._rho(rho, batch, g)), _p(w), _p(y), _p(gt), ratio, shift, rho_min, rho_max, _p(expo), self._stream(stream)),
                     name)
         return expo
@@ -906,30 +918,31 @@ class Solver:
                                     res, rho, w, y, gt, expo, ratio, shift, rho_min, rho_max, stream)
 
     def _admm_restep_args(self, nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, kind, gamma, lam, r, p, tol, max_iter, iters,
-                          mie, z, w, y, gt, res, expo, ratio, shift, rho_min, rho_max, rows=None, cones=None):
+                          mie, z, w, y, gt, res, expo, ratio, shift, rho_min, rho_max, rows=None, cones=None, kappa=None):
         """(suffix, the argument tuple up to d_expo, the tensors a graph has to keep alive); Gt is None for the box."""
         suf, _ = _suffix(g)
         self._res(res, batch, g)
         sizes, E, mats = (), (), (G,)
+        soft = () if kappa is None else (kappa,)
         if rows is None:
             assert cones is None and Gt is None
-            self._box(g, batch, lo, hi, z, w, y, gt)
+            self._box(g, batch, lo, hi, z, w, y, gt, *soft)
         else:
             mx, mu, E = rows
-            self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y), (g, z, gt))
+            self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, w, y) + soft, (g, z, gt))
             assert Gt is not None and Gt.numel() == G.numel() and Gt.dtype == G.dtype and Gt.is_cuda and Gt.is_contiguous()
             sizes, E, mats = (mx, mu), (E,), (G, Gt)
             if cones is not None:
                 assert len(cones) == 4
                 sizes += tuple(int(v) for v in cones)
         args = ((self.h, nx, nu) + sizes + (N, batch) + tuple(_p(t) for t in mats) + (_p(Ginv), _p(C), _p(g), _p(c)) +
-                tuple(_p(t) for t in E) + (_p(lo), _p(hi), _p(self._rho(rho, batch, g)), _p(S), _p(Pinv), kind, _p(gamma), _p(lam), _p(r),
-                                           _p(p), tol, max_iter, _p(iters), _p(mie), _p(z), _p(w), _p(y), _p(gt), _p(res), ratio, shift,
-                                           rho_min, rho_max, _p(expo)))
-        return suf, args, mats + (Ginv, C, g, c) + E + (lo, hi, rho, S, Pinv, gamma, lam, r, p, iters, mie, z, w, y, gt, res, expo)
+                tuple(_p(t) for t in E) + (_p(lo), _p(hi)) + tuple(_p(t) for t in soft) +
+                (_p(self._rho(rho, batch, g)), _p(S), _p(Pinv), kind, _p(gamma), _p(lam), _p(r), _p(p), tol, max_iter, _p(iters), _p(mie),
+                 _p(z), _p(w), _p(y), _p(gt), _p(res), ratio, shift, rho_min, rho_max, _p(expo)))
+        return suf, args, mats + (Ginv, C, g, c) + E + (lo, hi) + soft + (rho, S, Pinv, gamma, lam, r, p, iters, mie, z, w, y, gt, res, expo)
 
     def _admm_restep(self, name, nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, expo, kind, r, p,
-                     tol, max_iter, iters, max_iter_exit, ratio, shift, rho_min, rho_max, stream, rows=None, cones=None):
+                     tol, max_iter, iters, max_iter_exit, ratio, shift, rho_min, rho_max, stream, rows=None, cones=None, kappa=None):
         import torch
         if iters is None:
             iters = torch.zeros(batch, dtype=torch.int32, device=g.device)
@@ -938,15 +951,15 @@ class Solver:
         expo = self._expo(expo, batch, g)
         suf, args, _ = self._admm_restep_args(nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, kind, gamma, lam, r, p, tol,
                                               max_iter, iters, max_iter_exit, z, w, y, gt, res, expo, ratio, shift, rho_min, rho_max,
-                                              rows, cones)
+                                              rows, cones, kappa)
         self._check(getattr(self.lib, f"gbdpcg_{name}_{suf}")(*args, self._stream(stream)), name)
         return iters, max_iter_exit, res.view(batch, 2), expo
 
     def _graph_admm_restep(self, name, nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
-                           max_iter_exit, z, w, y, gt, res, expo, kind, ratio, shift, rho_min, rho_max, rows=None, cones=None):
+                           max_iter_exit, z, w, y, gt, res, expo, kind, ratio, shift, rho_min, rho_max, rows=None, cones=None, kappa=None):
         suf, args, keep = self._admm_restep_args(nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, kind, gamma, lam, r, p, tol,
                                                  max_iter, iters, max_iter_exit, z, w, y, gt, res, self._expo(expo, batch, g), ratio,
-                                                 shift, rho_min, rho_max, rows, cones)
+                                                 shift, rho_min, rho_max, rows, cones, kappa)
         gr = ctypes.c_void_p()
         self._check(getattr(self.lib, f"gbdpcg_graph_create_{name}_{suf}")(*args, ctypes.byref(gr)), f"graph_create_{name}")
         return Graph(self, gr, keep=keep)
@@ -997,6 +1010,146 @@ class Solver:
         return self._graph_admm_restep("admm_soc_restep", nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
                                        max_iter, iters, max_iter_exit, z, w, y, gt, res, expo, kind, ratio, shift, rho_min, rho_max,
                                        rows=(mx, mu, E), cones=cones)
+
+    # ---- soft (L1-penalised) bounds (include/gbdpcg.h): the box and the linear rows with the weights kappa, laid out like lo and hi
+    # and passed directly behind hi; +Inf keeps a row hard, 0 frees it.  Everything else mirrors the hard methods.  The rebalance of
+    # the soft box is admm_rebalance.
+    def admm_soft_init(self, nx, nu, N, batch, g, lo, hi, kappa, rho, w, y, gt=None, stream=None):
+        """gbdpcg_admm_soft_init_*: w <- clip(w, lo, hi) where kappa = +Inf only, gt <- g - rho (w - y); y is left alone.  Returns gt."""
+        import torch
+        suf, _ = _suffix(g)
+        if gt is None:
+            gt = torch.empty_like(g)
+        self._box(g, batch, lo, hi, kappa, w, y, gt)
+        fn = getattr(self.lib, f"gbdpcg_admm_soft_init_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(g), _p(lo), _p(hi), _p(kappa), _p(self._rho(rho, batch, g)), _p(w), _p(y), _p(gt),
+                       self._stream(stream)), "admm_soft_init")
+        return gt
+
+    def admm_soft_update(self, nx, nu, N, batch, g, lo, hi, kappa, rho, z, w, y, gt, res=None, stream=None):
+        """gbdpcg_admm_soft_update_*: the soft update behind a solve that wrote z; returns the [batch, 2] tensor of residual norms."""
+        import torch
+        suf, _ = _suffix(g)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=g.dtype, device=g.device)
+        self._res(res, batch, g)
+        self._box(g, batch, lo, hi, kappa, z, w, y, gt)
+        fn = getattr(self.lib, f"gbdpcg_admm_soft_update_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(g), _p(lo), _p(hi), _p(kappa), _p(self._rho(rho, batch, g)), _p(z), _p(w), _p(y),
+                       _p(gt), _p(res), self._stream(stream)), "admm_soft_update")
+        return res.view(batch, 2)
+
+    def admm_soft_step(self, nx, nu, N, batch, Ginv, C, g, c, lo, hi, kappa, rho, S, Pinv, gamma, lam, z, w, y, gt, res=None, r=None, p=None,
+                       tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_admm_soft_step_*: kkt_resolve with gt in the place of g, then admm_soft_update.  Returns (iters, flags, res)."""
+        return self._admm_step("admm_soft_step", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, r, p,
+                               tol, max_iter, iters, max_iter_exit, stream, kappa=kappa)
+
+    def graph_admm_soft_step(self, nx, nu, N, batch, Ginv, C, g, c, lo, hi, kappa, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                             max_iter_exit, z, w, y, gt, res):
+        """Capture one soft iteration into a hipGraph (gbdpcg_graph_create_admm_soft_step_*)."""
+        return self._graph_admm_step("admm_soft_step", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                     max_iter, iters, max_iter_exit, z, w, y, gt, res, kappa=kappa)
+
+    def admm_soft_step_shared(self, nx, nu, N, batch, Ginv, C, g, c, lo, hi, kappa, rho, S, Pinv, gamma, lam, z, w, y, gt, res=None, r=None,
+                              p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_admm_soft_step_shared_*: ONE Ginv, C, S, Pinv; bounds, kappa, rho and the state stay per problem."""
+        return self._admm_step("admm_soft_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt,
+                               res, r, p, tol, max_iter, iters, max_iter_exit, stream, kappa=kappa)
+
+    def graph_admm_soft_step_shared(self, nx, nu, N, batch, Ginv, C, g, c, lo, hi, kappa, rho, S, Pinv, gamma, lam, r, p, tol, max_iter,
+                                    iters, max_iter_exit, z, w, y, gt, res):
+        """Capture the shared-matrix soft iteration into a hipGraph (gbdpcg_graph_create_admm_soft_step_shared_*)."""
+        return self._graph_admm_step("admm_soft_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                     max_iter, iters, max_iter_exit, z, w, y, gt, res, kappa=kappa)
+
+    def admm_soft_restep(self, nx, nu, N, batch, G, Ginv, C, g, c, lo, hi, kappa, rho, S, Pinv, gamma, lam, z, w, y, gt, res, expo=None,
+                         kind=PINV_STAIR, r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, *, ratio=10.0, shift=1,
+                         rho_min, rho_max, stream=None):
+        """gbdpcg_admm_soft_restep_*: admm_rebalance, kkt_step_reg with gt in the place of g, admm_soft_update.
+        Returns (iters, flags, res [batch, 2], expo)."""
+        return self._admm_restep("admm_soft_restep", nx, nu, N, batch, G, None, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt,
+                                 res, expo, kind, r, p, tol, max_iter, iters, max_iter_exit, ratio, shift, rho_min, rho_max, stream,
+                                 kappa=kappa)
+
+    def graph_admm_soft_restep(self, nx, nu, N, batch, G, Ginv, C, g, c, lo, hi, kappa, rho, S, Pinv, gamma, lam, r, p, tol, max_iter, iters,
+                               max_iter_exit, z, w, y, gt, res, expo, kind=PINV_STAIR, *, ratio=10.0, shift=1, rho_min, rho_max):
+        """Capture gbdpcg_admm_soft_restep_* into a hipGraph; it keeps the pointers of rho, res and expo."""
+        return self._graph_admm_restep("admm_soft_restep", nx, nu, N, batch, G, None, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p,
+                                       tol, max_iter, iters, max_iter_exit, z, w, y, gt, res, expo, kind, ratio, shift, rho_min, rho_max,
+                                       kappa=kappa)
+
+    def admm_lin_soft_init(self, nx, nu, mx, mu, N, batch, g, E, lo, hi, kappa, rho, w, y, gt=None, stream=None):
+        """gbdpcg_admm_lin_soft_init_*: w <- clip(w) where kappa = +Inf only, gt <- g - rho E'(w - y); y is left alone.  Returns gt."""
+        import torch
+        suf, _ = _suffix(g)
+        if gt is None:
+            gt = torch.empty_like(g)
+        self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, kappa, w, y), (g, gt))
+        fn = getattr(self.lib, f"gbdpcg_admm_lin_soft_init_{suf}")
+        self._check(fn(self.h, nx, nu, mx, mu, N, batch, _p(g), _p(E), _p(lo), _p(hi), _p(kappa), _p(self._rho(rho, batch, g)), _p(w),
+                       _p(y), _p(gt), self._stream(stream)), "admm_lin_soft_init")
+        return gt
+
+    def admm_lin_soft_update(self, nx, nu, mx, mu, N, batch, g, E, lo, hi, kappa, rho, z, w, y, gt, res=None, stream=None):
+        """gbdpcg_admm_lin_soft_update_*: the soft update of the rows behind a solve that wrote z; returns res [batch, 2]."""
+        import torch
+        suf, _ = _suffix(g)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=g.dtype, device=g.device)
+        self._res(res, batch, g)
+        self._lin(g, batch, nx, nu, mx, mu, N, E, (lo, hi, kappa, w, y), (g, z, gt))
+        fn = getattr(self.lib, f"gbdpcg_admm_lin_soft_update_{suf}")
+        self._check(fn(self.h, nx, nu, mx, mu, N, batch, _p(g), _p(E), _p(lo), _p(hi), _p(kappa), _p(self._rho(rho, batch, g)), _p(z),
+                       _p(w), _p(y), _p(gt), _p(res), self._stream(stream)), "admm_lin_soft_update")
+        return res.view(batch, 2)
+
+    def admm_lin_soft_step(self, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, kappa, rho, S, Pinv, gamma, lam, z, w, y, gt, res=None,
+                           r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_admm_lin_soft_step_*: kkt_resolve with gt in the place of g, then admm_lin_soft_update.  Returns (iters, flags, res)."""
+        return self._admm_step("admm_lin_soft_step", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res, r,
+                               p, tol, max_iter, iters, max_iter_exit, stream, rows=(mx, mu, E), kappa=kappa)
+
+    def graph_admm_lin_soft_step(self, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, kappa, rho, S, Pinv, gamma, lam, r, p, tol,
+                                 max_iter, iters, max_iter_exit, z, w, y, gt, res):
+        """Capture one soft iteration with rows into a hipGraph (gbdpcg_graph_create_admm_lin_soft_step_*)."""
+        return self._graph_admm_step("admm_lin_soft_step", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p, tol,
+                                     max_iter, iters, max_iter_exit, z, w, y, gt, res, rows=(mx, mu, E), kappa=kappa)
+
+    def admm_lin_soft_step_shared(self, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, kappa, rho, S, Pinv, gamma, lam, z, w, y, gt,
+                                  res=None, r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_admm_lin_soft_step_shared_*: ONE Ginv, C, S, Pinv and E; bounds, kappa, rho and the state stay per problem."""
+        return self._admm_step("admm_lin_soft_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt,
+                               res, r, p, tol, max_iter, iters, max_iter_exit, stream, rows=(mx, mu, E), kappa=kappa)
+
+    def graph_admm_lin_soft_step_shared(self, nx, nu, mx, mu, N, batch, Ginv, C, g, c, E, lo, hi, kappa, rho, S, Pinv, gamma, lam, r, p,
+                                        tol, max_iter, iters, max_iter_exit, z, w, y, gt, res):
+        """Capture the shared-matrix soft iteration with rows into a hipGraph (gbdpcg_graph_create_admm_lin_soft_step_shared_*)."""
+        return self._graph_admm_step("admm_lin_soft_step_shared", nx, nu, N, batch, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r, p,
+                                     tol, max_iter, iters, max_iter_exit, z, w, y, gt, res, rows=(mx, mu, E), kappa=kappa)
+
+    def admm_lin_soft_rebalance(self, nx, nu, mx, mu, N, batch, g, E, lo, hi, kappa, res, rho, w, y, gt, expo=None, *, ratio=10.0, shift=1,
+                                rho_min, rho_max, stream=None):
+        """gbdpcg_admm_lin_soft_rebalance_*: rho and y in place, then admm_lin_soft_init rebuilds gt.  Returns expo."""
+        return self._rows_rebalance("admm_lin_soft_rebalance", (mx, mu), nx, nu, mx, mu, N, batch, g, E, lo, hi, res, rho, w, y, gt, expo,
+                                    ratio, shift, rho_min, rho_max, stream, kappa=kappa)
+
+    def admm_lin_soft_restep(self, nx, nu, mx, mu, N, batch, G, Gt, Ginv, C, g, c, E, lo, hi, kappa, rho, S, Pinv, gamma, lam, z, w, y, gt,
+                             res, expo=None, kind=PINV_STAIR, r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, *,
+                             ratio=10.0, shift=1, rho_min, rho_max, stream=None):
+        """gbdpcg_admm_lin_soft_restep_*: admm_lin_soft_rebalance, admm_lin_form into Gt, kkt_step on Gt, admm_lin_soft_update.
+        Returns (iters, flags, res [batch, 2], expo)."""
+        return self._admm_restep("admm_lin_soft_restep", nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y,
+                                 gt, res, expo, kind, r, p, tol, max_iter, iters, max_iter_exit, ratio, shift, rho_min, rho_max, stream,
+                                 rows=(mx, mu, E), kappa=kappa)
+
+    def graph_admm_lin_soft_restep(self, nx, nu, mx, mu, N, batch, G, Gt, Ginv, C, g, c, E, lo, hi, kappa, rho, S, Pinv, gamma, lam, r, p,
+                                   tol, max_iter, iters, max_iter_exit, z, w, y, gt, res, expo, kind=PINV_STAIR, *, ratio=10.0, shift=1,
+                                   rho_min, rho_max):
+        """Capture gbdpcg_admm_lin_soft_restep_* into a hipGraph; it keeps the pointers of rho, res and expo."""
+        return self._graph_admm_restep("admm_lin_soft_restep", nx, nu, N, batch, G, Gt, Ginv, C, g, c, lo, hi, rho, S, Pinv, gamma, lam, r,
+                                       p, tol, max_iter, iters, max_iter_exit, z, w, y, gt, res, expo, kind, ratio, shift, rho_min,
+                                       rho_max, rows=(mx, mu, E), kappa=kappa)
 
     # ---- the backward pass (include/gbdpcg.h): gradients of a scalar in G and C from the forward point (z, lam) and the adjoint pair
     # (az, alam), which is kkt_resolve with g := dl/dz, c := -dl/dlambda on the kept factorisation

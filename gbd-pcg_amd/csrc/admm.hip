@@ -12,6 +12,14 @@
 //     res[2b+1] = max |rho (w+ - w)|                 dual residual rho ||w+ - w||_inf
 // INIT (gbdpcg_admm_init_*): w <- clip(w), y unchanged (not written), gt = fma(-rho, w - y, g); z and res are not looked at.
 // The maxima are those of the KKT residual norms (norm_fold.hpp): over the bit pattern of |entry|, exact in any order, NaN on top.
+// SOFT (gbdpcg_admm_soft_*; a compile-time switch next to INIT): element i pays kappa_i dist(z_i, [lo_i, hi_i]) instead of being
+// bounded.  Only the two lines of w+ and y+ change (soft_clip in ieee_once.hpp):
+//     p = clip(v);  e = v - p;  theta = kappa / rho              / correctly rounded
+//     w+ = e > theta ? v - theta : (e < -theta ? v + theta : p);   y+ = e > theta ? theta : (e < -theta ? -theta : e)
+// kappa = +Inf: the third branch, the operations of the hard update, the hard bits.  INIT: w <- (kappa == +Inf) ? clip(w) : w.
+// kappa is an eighth array at the same offset b nz, loaded by the same head / body / tail scheme and part of the host's alignment
+// test: 10 element accesses per element of z (INIT: 6 + 2).  It is not validated: negative or NaN is the caller's error.  The hard
+// instantiations take no kappa argument (an empty parameter pack) and compile to the code of a kernel that knows nothing of it.
 //
 // Shape: ONE WORKGROUP PER PROBLEM (the two norms are per problem: nothing crosses a workgroup, no atomics, no memset, nothing
 // read from res), one wave when nz <= 256, otherwise four.  9 element accesses per element of z (6 reads, 3 writes; INIT: 5 + 2),
@@ -38,18 +46,26 @@ template <> struct AdmmVec<double> {
     typedef double type __attribute__((ext_vector_type(2)));
 };
 
-// One element.  w, y: in / out (INIT leaves y alone); mp, md: the running maxima of the two norms (not INIT).
-template <typename T, bool INIT, typename U>
-__device__ __forceinline__ T admm_element(T z, T &w, T &y, T lo, T hi, T g, T rho, U &mp, U &md)
+// One element.  w, y: in / out (INIT leaves y alone); mp, md: the running maxima of the two norms (not INIT); kap: read where SOFT.
+template <typename T, bool INIT, bool SOFT, typename U>
+__device__ __forceinline__ T admm_element(T z, T &w, T &y, T lo, T hi, T kap, T g, T rho, U &mp, U &md)
 {
     if constexpr (INIT) {
-        w = clip(w, lo, hi);
+        if constexpr (SOFT)
+            w = soft_init(w, lo, hi, kap);
+        else
+            w = clip(w, lo, hi);
         const T t = w - y;
         return fma_once(-rho, t, g);
     } else {
         const T v = z + y;
-        const T wn = clip(v, lo, hi);
-        const T yn = v - wn;
+        T wn, yn;
+        if constexpr (SOFT) {
+            soft_clip(v, lo, hi, kap, rho, wn, yn);
+        } else {
+            wn = clip(v, lo, hi);
+            yn = v - wn;
+        }
         const T t = wn - yn;
         mp = umax(mp, abs_bits(z - wn));
         md = umax(md, abs_bits(rho * (wn - w)));
@@ -61,11 +77,13 @@ __device__ __forceinline__ T admm_element(T z, T &w, T &y, T lo, T hi, T g, T rh
 
 }  // namespace
 
-template <typename T, bool INIT>
+template <typename T, bool INIT, bool SOFT, typename... K>
 __global__ __launch_bounds__(256) void admm_update_kernel(uint64_t nz, uint32_t vec, const T *__restrict__ g, const T *__restrict__ lo,
                                                           const T *__restrict__ hi, const T *__restrict__ rho, const T *__restrict__ z,
-                                                          T *__restrict__ w, T *__restrict__ y, T *__restrict__ gt, T *__restrict__ res)
+                                                          T *__restrict__ w, T *__restrict__ y, T *__restrict__ gt, T *__restrict__ res,
+                                                          K... kappa_arg)
 {
+    static_assert(sizeof...(K) == (SOFT ? 1 : 0), "kappa is an argument of the soft instantiations alone");
     using U = decltype(abs_bits(T(0)));
     using V = typename AdmmVec<T>::type;
     constexpr uint32_t VN = AdmmVec<T>::N;
@@ -74,13 +92,17 @@ __global__ __launch_bounds__(256) void admm_update_kernel(uint64_t nz, uint32_t 
     const uint64_t off = (uint64_t)prob * nz;   // 64-bit problem stride
     g += off, lo += off, hi += off, w += off, y += off, gt += off;
     if constexpr (!INIT) z += off;
+    [[maybe_unused]] const T *__restrict__ kappa = nullptr;
+    if constexpr (SOFT) kappa = kappa_of<T>(kappa_arg...) + off;
     const T r = rho[prob];
     U mp = 0, md = 0;
 
     auto scalar = [&](uint64_t i) {
         T wi = w[i], yi = y[i];
         const T zi = INIT ? T(0) : z[i];
-        gt[i] = admm_element<T, INIT>(zi, wi, yi, lo[i], hi[i], g[i], r, mp, md);
+        T ki = T(0);
+        if constexpr (SOFT) ki = kappa[i];
+        gt[i] = admm_element<T, INIT, SOFT>(zi, wi, yi, lo[i], hi[i], ki, g[i], r, mp, md);
         w[i] = wi;
         if constexpr (!INIT) y[i] = yi;
     };
@@ -99,11 +121,13 @@ __global__ __launch_bounds__(256) void admm_update_kernel(uint64_t nz, uint32_t 
         const V gv = *reinterpret_cast<const V *>(g + i);
         V zv = {};
         if constexpr (!INIT) zv = *reinterpret_cast<const V *>(z + i);
+        V kv = {};
+        if constexpr (SOFT) kv = *reinterpret_cast<const V *>(kappa + i);
         V tv;
 #pragma unroll
         for (uint32_t e = 0; e < VN; ++e) {
             T we = wv[e], ye = yv[e];
-            tv[e] = admm_element<T, INIT>(zv[e], we, ye, lv[e], hv[e], gv[e], r, mp, md);
+            tv[e] = admm_element<T, INIT, SOFT>(zv[e], we, ye, lv[e], hv[e], kv[e], gv[e], r, mp, md);
             wv[e] = we;
             yv[e] = ye;
         }
@@ -119,25 +143,33 @@ __global__ __launch_bounds__(256) void admm_update_kernel(uint64_t nz, uint32_t 
 
 template <typename T>
 hipError_t launch_admm_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *g, const T *lo, const T *hi, const T *rho,
-                              const T *z, T *w, T *y, T *gt, T *res, hipStream_t s, bool init)
+                              const T *z, T *w, T *y, T *gt, T *res, hipStream_t s, bool init, const T *kappa)
 {
     if (batch > 0x7fffffffu) return hipErrorInvalidValue;   // one workgroup per problem
     const uint64_t nz = ((uint64_t)nx + nu) * N - nu;
-    const void *ptrs[] = {g, lo, hi, w, y, gt, init ? (const void *)g : (const void *)z};
+    const void *ptrs[] = {g, lo, hi, w, y, gt, init ? (const void *)g : (const void *)z, kappa ? (const void *)kappa : (const void *)g};
     uint32_t vec = 1;
     for (const void *p : ptrs)
         if (reinterpret_cast<uintptr_t>(p) % 16) vec = 0;
     const uint32_t threads = nz <= 256 ? 64 : 256;
-    if (init)
-        hipLaunchKernelGGL((admm_update_kernel<T, true>), dim3(batch), dim3(threads), 0, s, nz, vec, g, lo, hi, rho, z, w, y, gt, res);
+    if (kappa && init)   // the soft family: its own instantiations
+        hipLaunchKernelGGL((admm_update_kernel<T, true, true, const T *>), dim3(batch), dim3(threads), 0, s, nz, vec, g, lo, hi, rho, z, w,
+                           y, gt, res, kappa);
+    else if (kappa)
+        hipLaunchKernelGGL((admm_update_kernel<T, false, true, const T *>), dim3(batch), dim3(threads), 0, s, nz, vec, g, lo, hi, rho, z, w,
+                           y, gt, res, kappa);
+    else if (init)
+        hipLaunchKernelGGL((admm_update_kernel<T, true, false>), dim3(batch), dim3(threads), 0, s, nz, vec, g, lo, hi, rho, z, w, y, gt, res);
     else
-        hipLaunchKernelGGL((admm_update_kernel<T, false>), dim3(batch), dim3(threads), 0, s, nz, vec, g, lo, hi, rho, z, w, y, gt, res);
+        hipLaunchKernelGGL((admm_update_kernel<T, false, false>), dim3(batch), dim3(threads), 0, s, nz, vec, g, lo, hi, rho, z, w, y, gt, res);
     return hipGetLastError();
 }
 
 template hipError_t launch_admm_update<float>(uint32_t, uint32_t, uint32_t, uint32_t, const float *, const float *, const float *,
-                                              const float *, const float *, float *, float *, float *, float *, hipStream_t, bool);
+                                              const float *, const float *, float *, float *, float *, float *, hipStream_t, bool,
+                                              const float *);
 template hipError_t launch_admm_update<double>(uint32_t, uint32_t, uint32_t, uint32_t, const double *, const double *, const double *,
-                                               const double *, const double *, double *, double *, double *, double *, hipStream_t, bool);
+                                               const double *, const double *, double *, double *, double *, double *, hipStream_t, bool,
+                                               const double *);
 
 }  // namespace gbdpcg

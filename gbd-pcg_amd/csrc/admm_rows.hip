@@ -22,6 +22,13 @@
 //           y+ = s - w+;  t = (w+ - y+) - f;  d = w+ - w;  u, e, gt, res as above
 //   INIT    w <- projection of w by the same lines with s := w, y not written, t = (w - y) - f.
 // A NaN fails both comparisons and stays NaN through the third branch; q = 1 is the half-line s_0 >= 0 (an empty chain, a = +0).
+// SOFT (the gbdpcg_admm_lin_soft_* calls; never together with CONES: cone rows stay hard) replaces the constraint on row r by the
+// penalty kappa_r dist((E z)_r, [lo_r, hi_r]).  Only the lines of w+ and y+ change (soft_clip in ieee_once.hpp):
+//   UPDATE  p = clip(s);  e = s - p;  theta = kappa / rho;  w+ = e > theta ? s - theta : (e < -theta ? s + theta : p)
+//           y+ = e > theta ? theta : (e < -theta ? -theta : e)             kappa = +Inf: the third branch, the hard bits
+//   INIT    w <- (kappa == +Inf) ? clip(w) : w
+// kappa has the layout of lo and is read in phase A by the lane that owns the row, one more scalar global read per row; no LDS slot
+// is added and phase B is untouched.  The hard instantiations take no kappa argument (an empty parameter pack).
 //
 // admm_lin_form_kernel: one lane per entry of Gt, 256 consecutive entries of one problem per workgroup; the entry is read and
 // written by the same lane, so Gt may be G.  E is read through the caches (2 m values per entry against one element in, one out);
@@ -103,12 +110,14 @@ __global__ __launch_bounds__(256) void admm_lin_form_kernel(uint32_t nx, uint32_
     Gt[at] = fma_once(rho[prob], p, G[at]);
 }
 
-template <typename T, bool INIT, bool CONES>
+template <typename T, bool INIT, bool CONES, bool SOFT, typename... K>
 __global__ __launch_bounds__(256) void admm_rows_update_kernel(RowsShape<CONES> s, const T *__restrict__ g, const T *__restrict__ E,
                                                                const T *__restrict__ lo, const T *__restrict__ hi,
                                                                const T *__restrict__ rho, const T *__restrict__ z, T *__restrict__ w,
-                                                               T *__restrict__ y, T *__restrict__ gt, T *__restrict__ res)
+                                                               T *__restrict__ y, T *__restrict__ gt, T *__restrict__ res, K... kappa_arg)
 {
+    static_assert(!(SOFT && CONES), "cone rows stay hard");
+    static_assert(sizeof...(K) == (SOFT ? 1 : 0), "kappa is an argument of the soft instantiations alone");
     using U = decltype(abs_bits(T(0)));
     extern __shared__ __attribute__((aligned(16))) unsigned char rows_lds[];
     __shared__ U slots[8];   // two words per wave
@@ -120,6 +129,8 @@ __global__ __launch_bounds__(256) void admm_rows_update_kernel(RowsShape<CONES> 
     const uint64_t nz = (uint64_t)sv * N - nu, nw = (uint64_t)sw * N - mu, ne = (uint64_t)se * N - mu * nu;
     g += prob * nz, gt += prob * nz, lo += prob * nw, hi += prob * nw, w += prob * nw, y += prob * nw;
     if constexpr (!INIT) z += prob * nz;
+    [[maybe_unused]] const T *__restrict__ kappa = nullptr;
+    if constexpr (SOFT) kappa = kappa_of<T>(kappa_arg...) + prob * nw;
     if (!s.shared) E += prob * ne;
     const T r = rho[prob];
     U mp = 0, md = 0;
@@ -140,9 +151,13 @@ __global__ __launch_bounds__(256) void admm_rows_update_kernel(RowsShape<CONES> 
             // phase A: row q of the chunk
             for (uint32_t q = tid; q < wc; q += threads) {
                 const T wo = w[w0 + q], yo = y[w0 + q], l = lo[w0 + q], h = hi[w0 + q];
-                T wn, t;
+                T wn, t, kap = T(0);
+                if constexpr (SOFT) kap = kappa[w0 + q];
                 if constexpr (INIT) {
-                    wn = clip(wo, l, h);
+                    if constexpr (SOFT)
+                        wn = soft_init(wo, l, h, kap);
+                    else
+                        wn = clip(wo, l, h);
                     t = wn - yo;
                 } else {
                     const uint32_t kk = q / sw;
@@ -152,8 +167,13 @@ __global__ __launch_bounds__(256) void admm_rows_update_kernel(RowsShape<CONES> 
                     T v = T(0);
                     for (uint32_t j = 0; j < cols; ++j) v = fma_once(blk[j * ld + row], zz[j], v);
                     const T sum = v + yo;
-                    wn = clip(sum, l, h);
-                    const T yn = sum - wn;
+                    T yn;
+                    if constexpr (SOFT) {
+                        soft_clip(sum, l, h, kap, r, wn, yn);
+                    } else {
+                        wn = clip(sum, l, h);
+                        yn = sum - wn;
+                    }
                     t = wn - yn;
                     sd[q] = wn - wo;
                     mp = umax(mp, abs_bits(v - wn));
@@ -287,24 +307,31 @@ hipError_t launch_admm_lin_form(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t 
 template <typename T>
 hipError_t launch_admm_rows_update(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *g,
                                    const T *E, const T *lo, const T *hi, const T *rho, const T *z, T *w, T *y, T *gt, T *res,
-                                   hipStream_t s, bool init, bool shared, const RowClasses *cones)
+                                   hipStream_t s, bool init, bool shared, const RowClasses *cones, const T *kappa)
 {
-    if (batch > 0x7fffffffu || !admm_rows_shape_ok<T>(nx, nu, mx, mu) || (cones && !admm_rows_classes_ok(mx, mu, *cones)))
-        return hipErrorInvalidValue;   // one workgroup per problem
+    if (batch > 0x7fffffffu || !admm_rows_shape_ok<T>(nx, nu, mx, mu) || (cones && !admm_rows_classes_ok(mx, mu, *cones)) ||
+        (cones && kappa))
+        return hipErrorInvalidValue;   // one workgroup per problem; cone rows stay hard
     const RowsDims dims{nx, nu, mx, mu};
     RowsWalk walk{N, admm_rows_knot_chunk(nx, nu, mx, mu), shared ? 1u : 0u};
     if (walk.kch > N) walk.kch = N;
     const uint64_t nz = ((uint64_t)nx + nu) * N - nu, nw = ((uint64_t)mx + mu) * N - mu;
     const uint32_t threads = (nz > nw ? nz : nw) <= 256 ? 64 : 256;
     const size_t lds = (size_t)walk.kch * rows_per_knot(nx, nu, mx, mu) * sizeof(T);
-    auto launch = [&](auto kernel, auto sh) { hipLaunchKernelGGL(kernel, dim3(batch), dim3(threads), lds, s, sh, g, E, lo, hi, rho, z, w, y, gt, res); };
+    auto launch = [&](auto kernel, auto sh, auto... kap) {
+        hipLaunchKernelGGL(kernel, dim3(batch), dim3(threads), lds, s, sh, g, E, lo, hi, rho, z, w, y, gt, res, kap...);
+    };
     if (cones) {   // (q is ignored where there is no cone row)
         const RowClasses c{cones->lx, cones->lx < mx ? cones->qx : 1u, cones->lu, cones->lu < mu ? cones->qu : 1u};
         const RowsShape<true> sh{dims, c, walk};
-        init ? launch(admm_rows_update_kernel<T, true, true>, sh) : launch(admm_rows_update_kernel<T, false, true>, sh);
+        init ? launch(&admm_rows_update_kernel<T, true, true, false>, sh) : launch(&admm_rows_update_kernel<T, false, true, false>, sh);
+    } else if (kappa) {   // the soft family: its own instantiations
+        const RowsShape<false> sh{dims, {}, walk};
+        init ? launch(&admm_rows_update_kernel<T, true, false, true, const T *>, sh, kappa)
+             : launch(&admm_rows_update_kernel<T, false, false, true, const T *>, sh, kappa);
     } else {
         const RowsShape<false> sh{dims, {}, walk};
-        init ? launch(admm_rows_update_kernel<T, true, false>, sh) : launch(admm_rows_update_kernel<T, false, false>, sh);
+        init ? launch(&admm_rows_update_kernel<T, true, false, false>, sh) : launch(&admm_rows_update_kernel<T, false, false, false>, sh);
     }
     return hipGetLastError();
 }
@@ -317,9 +344,11 @@ template hipError_t launch_admm_lin_form<double>(uint32_t, uint32_t, uint32_t, u
                                                  const double *, const double *, double *, hipStream_t);
 template hipError_t launch_admm_rows_update<float>(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const float *,
                                                    const float *, const float *, const float *, const float *, const float *, float *,
-                                                   float *, float *, float *, hipStream_t, bool, bool, const RowClasses *);
+                                                   float *, float *, float *, hipStream_t, bool, bool, const RowClasses *,
+                                                   const float *);
 template hipError_t launch_admm_rows_update<double>(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const double *,
                                                     const double *, const double *, const double *, const double *, const double *,
-                                                    double *, double *, double *, double *, hipStream_t, bool, bool, const RowClasses *);
+                                                    double *, double *, double *, double *, hipStream_t, bool, bool, const RowClasses *,
+                                                    const double *);
 
 }  // namespace gbdpcg

@@ -68,7 +68,8 @@ gbdpcg_status kkt_residual_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uin
 // The set and the splitting state of the gbdpcg_admm*_step_* calls: rho [batch], res [2 batch].  Box (gbdpcg_admm_step_*): mx = mu = 0
 // and no E, every array has the layout of g.  rows (gbdpcg_admm_lin_step_*): the bounds are on E z -- lo, hi, w, y have the layout
 // of the rows, E is one problem's in the shared form.  cones (gbdpcg_admm_soc_step_*, with rows): the rows behind the first lx / lu
-// of a block are cones of dimension qx / qu, lo holds their offsets.
+// of a block are cones of dimension qx / qu, lo holds their offsets.  soft (gbdpcg_admm_soft_*, gbdpcg_admm_lin_soft_*): the bounds are
+// L1-penalised with the weights kappa, which have the layout of lo; a hard family leaves kappa null, a soft one is refused without it.
 template <typename T> struct AdmmOperands {
     const T *lo, *hi, *rho;
     T *w, *y, *gt, *res;
@@ -76,6 +77,8 @@ template <typename T> struct AdmmOperands {
     const T *E = nullptr;
     uint32_t mx = 0, mu = 0;
     const RowClasses *cones = nullptr;
+    const T *kappa = nullptr;
+    bool soft = false;
 };
 
 // The forward point and the outputs of gbdpcg_kkt_backward_*: z has the layout of g, lambda that of c, gG / gC those of G / C (one
@@ -179,16 +182,18 @@ gbdpcg_status kkt_resolve_impl(gbdpcg_handle_t h, const KktOperands<T> &k, const
 }
 
 // The splitting update (admm.hip), one launch.  init: gbdpcg_admm_init_* -- d_z and d_res are not arguments.  No shape is refused:
-// the kernel is elementwise over the layout of g.
+// the kernel is elementwise over the layout of g.  soft: the gbdpcg_admm_soft_* calls, which need d_kappa.
 template <typename T>
 gbdpcg_status admm_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_g, const T *d_lo,
-                               const T *d_hi, const T *d_rho, const T *d_z, T *d_w, T *d_y, T *d_gt, T *d_res, void *stream, bool init)
+                               const T *d_hi, const T *d_rho, const T *d_z, T *d_w, T *d_y, T *d_gt, T *d_res, void *stream, bool init,
+                               const T *d_kappa = nullptr, bool soft = false)
 {
     if (!h || !d_g || !d_lo || !d_hi || !d_rho || !d_w || !d_y || !d_gt || (!init && (!d_z || !d_res)) || nx == 0 || nu == 0 ||
-        N == 0 || batch == 0)
+        N == 0 || batch == 0 || (soft && !d_kappa))
         return GBDPCG_ERR_INVALID;
     DEVICE_SCOPE(h);
-    HIP_TRY(h, launch_admm_update<T>(nx, nu, N, batch, d_g, d_lo, d_hi, d_rho, d_z, d_w, d_y, d_gt, d_res, (hipStream_t)stream, init));
+    HIP_TRY(h, launch_admm_update<T>(nx, nu, N, batch, d_g, d_lo, d_hi, d_rho, d_z, d_w, d_y, d_gt, d_res, (hipStream_t)stream, init,
+                                     soft ? d_kappa : nullptr));
     return GBDPCG_OK;
 }
 
@@ -224,13 +229,13 @@ gbdpcg_status admm_rows_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu,
                                     const AdmmOperands<T> &a, const T *d_z, void *stream, bool init, bool shared = false)
 {
     if (!h || !d_g || !a.E || !a.lo || !a.hi || !a.rho || !a.w || !a.y || !a.gt || (!init && (!d_z || !a.res)) || nx == 0 ||
-        nu == 0 || N == 0 || batch == 0)
+        nu == 0 || N == 0 || batch == 0 || (a.soft && (!a.kappa || a.cones)))
         return GBDPCG_ERR_INVALID;
     const gbdpcg_status st = admm_rows_status<T>(nx, nu, a, N);
     if (st != GBDPCG_OK) return st;
     DEVICE_SCOPE(h);
     HIP_TRY(h, launch_admm_rows_update<T>(nx, nu, a.mx, a.mu, N, batch, d_g, a.E, a.lo, a.hi, a.rho, d_z, a.w, a.y, a.gt, a.res,
-                                          (hipStream_t)stream, init, shared, a.cones));
+                                          (hipStream_t)stream, init, shared, a.cones, a.soft ? a.kappa : nullptr));
     return GBDPCG_OK;
 }
 
@@ -243,7 +248,8 @@ gbdpcg_status admm_step_refusal(gbdpcg_handle_t h, const KktOperands<T> &k, cons
                                 bool solve_limits = true)
 {
     if (!h || !k.Ginv || !k.g || !k.c || !a.lo || !a.hi || !a.rho || !p.S || !p.gamma || !p.lambda || !p.iters || !k.z || !a.w ||
-        !a.y || !a.gt || !a.res || (!k.C && p.N > 1) || k.nu == 0 || !shape_ok(p.n, p.N, p.batch) || (a.rows && !a.E))
+        !a.y || !a.gt || !a.res || (!k.C && p.N > 1) || k.nu == 0 || !shape_ok(p.n, p.N, p.batch) || (a.rows && !a.E) ||
+        (a.soft && (!a.kappa || a.cones)))
         return GBDPCG_ERR_INVALID;
     const gbdpcg_status rows = a.rows ? admm_rows_status<T>(p.n, k.nu, a, p.N) : GBDPCG_OK;
     if (rows == GBDPCG_ERR_INVALID) return rows;
@@ -265,7 +271,8 @@ gbdpcg_status admm_step_impl(gbdpcg_handle_t h, const KktOperands<T> &k, const A
     st = kkt_resolve_impl<T>(h, shifted, p, stream);
     if (st != GBDPCG_OK) return st;
     if (a.rows) return admm_rows_update_impl<T>(h, p.n, k.nu, p.N, p.batch, k.g, a, k.z, stream, false, k.shared);
-    return admm_update_impl<T>(h, p.n, k.nu, p.N, p.batch, k.g, a.lo, a.hi, a.rho, k.z, a.w, a.y, a.gt, a.res, stream, false);
+    return admm_update_impl<T>(h, p.n, k.nu, p.N, p.batch, k.g, a.lo, a.hi, a.rho, k.z, a.w, a.y, a.gt, a.res, stream, false, a.kappa,
+                               a.soft);
 }
 
 // ---- adaptive rho (admm_rebalance.hip): residual balancing in powers of two, and the iteration that refactors with the new rho
@@ -297,14 +304,15 @@ gbdpcg_status admm_rebalance_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, u
     return GBDPCG_OK;
 }
 
-// The rows form (admm_lin, admm_soc): rho, y over the rows of a, expo; then the family's init launch rebuilds gt (and re-projects w).
+// The rows form (admm_lin, admm_soc, admm_lin_soft): rho, y over the rows of a, expo; then the family's init launch rebuilds gt (and
+// re-projects w; the soft init clips only the rows with kappa = +Inf).
 // a.rho is rule.rho.  Whatever the init launch refuses is refused here before the first launch.
 template <typename T>
 gbdpcg_status admm_rows_rebalance_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_g,
                                        const AdmmOperands<T> &a, const RhoRule<T> &rule, void *stream)
 {
     if (!h || !d_g || !a.E || !a.lo || !a.hi || !a.res || !a.w || !a.y || !a.gt || nx == 0 || nu == 0 || N == 0 || batch == 0 ||
-        !rho_rule_ok<T>(rule))
+        !rho_rule_ok<T>(rule) || (a.soft && (!a.kappa || a.cones)))
         return GBDPCG_ERR_INVALID;
     const gbdpcg_status st = admm_rows_status<T>(nx, nu, a, N);
     if (st != GBDPCG_OK) return st;
@@ -364,7 +372,7 @@ gbdpcg_status admm_restep_impl(gbdpcg_handle_t h, const Refactor<T> &f, const Kk
     st = kkt_step_impl<T>(h, f.formed(a), shifted, p, stream);
     if (st != GBDPCG_OK) return st;
     if (a.rows) return admm_rows_update_impl<T>(h, nx, k.nu, N, batch, k.g, a, k.z, stream, false);
-    return admm_update_impl<T>(h, nx, k.nu, N, batch, k.g, a.lo, a.hi, a.rho, k.z, a.w, a.y, a.gt, a.res, stream, false);
+    return admm_update_impl<T>(h, nx, k.nu, N, batch, k.g, a.lo, a.hi, a.rho, k.z, a.w, a.y, a.gt, a.res, stream, false, a.kappa, a.soft);
 }
 
 // The gradient launch (kkt_grad.hip), no handle state.  shared: gG, gC are one problem's worth, summed over the batch.
@@ -606,6 +614,7 @@ GBDPCG_PAIR_BOTH(kkt_resolve_shared, true, RESOLVE_PARAMS, RESOLVE_SETUP, RESOLV
 //   admm       box lo <= z <= hi, the matrices of G + rho I
 //   admm_lin   stage-wise linear rows lo <= E z <= hi, the matrices of G + rho E'E (gbdpcg_admm_lin_form_*)
 //   admm_soc   second-order cone rows next to the linear ones, the same matrices
+// admm and admm_lin have soft twins (admm_soft, admm_lin_soft, behind admm_soc below): L1-penalised bounds, d_kappa behind d_hi.
 // Each has init, update, step and graph_create_step, the last two with a _shared twin on one problem's Ginv, C, S, Pinv (and E);
 // the set, rho and the splitting state stay per problem.  Adaptive rho: rebalance, restep and graph_create_restep, per problem only.
 // A family is described by these macros, defined in front of its entries:
@@ -755,8 +764,56 @@ GBDPCG_ADMM_RESTEPS(admm_soc_restep)
 #undef ADMM_SIZES
 #undef ADMM_SET
 #undef ADMM_CONES
+#undef ADMM_ROWS_OPERANDS
+
+// ---- soft (L1-penalised) bounds: the box and the linear rows with the weights d_kappa, in the layout of d_lo, directly behind d_hi.
+// kappa = +Inf everywhere gives the bits of the hard family; cone rows stay hard (there is no admm_soc_soft).
+// (admm_lin_soft: ADMM_OPERANDS, ADMM_MATS and ADMM_GT stay those of admm_lin; its rebalance rebuilds gt with the SOFT init)
+#define ADMM_SIZES uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu
+#define ADMM_SET(TYPE) const TYPE *d_E, const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_kappa
+#define ADMM_CONES
+#define ADMM_ROWS_OPERANDS true, d_E, mx, mu, nullptr, d_kappa, true
+GBDPCG_ADMM_ROWS(admm_lin_soft, f32, float)
+GBDPCG_ADMM_ROWS(admm_lin_soft, f64, double)
+GBDPCG_ADMM_STEPS(admm_lin_soft_step)
+GBDPCG_ADMM_RESTEPS(admm_lin_soft_restep)
+#undef ADMM_SIZES
+#undef ADMM_SET
 #undef ADMM_OPERANDS
 #undef ADMM_ROWS_OPERANDS
+#undef ADMM_MATS
+#undef ADMM_GT
+
+// (admm_soft: the box.  gbdpcg_admm_rebalance_* is its rebalance too: that launch never looks at the bounds and does not clip w)
+#define ADMM_SIZES uint32_t nx, uint32_t nu
+#define ADMM_SET(TYPE) const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_kappa
+#define ADMM_OPERANDS d_lo, d_hi, d_rho, d_w, d_y, d_gt, d_res, false, nullptr, 0, 0, nullptr, d_kappa, true
+#define ADMM_MATS(TYPE) const TYPE *d_G
+#define ADMM_GT nullptr
+#define GBDPCG_ADMM_SOFT(SUF, TYPE)                                                                                                 \
+    gbdpcg_status gbdpcg_admm_soft_init_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,              \
+                                              const TYPE *d_g, ADMM_SET(TYPE), const TYPE *d_rho, TYPE *d_w, TYPE *d_y, TYPE *d_gt, \
+                                              void *stream)                                                                         \
+    {                                                                                                                               \
+        return admm_update_impl<TYPE>(h, nx, nu, N, batch, d_g, d_lo, d_hi, d_rho, nullptr, d_w, d_y, d_gt, nullptr, stream, true,  \
+                                      d_kappa, true);                                                                               \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_soft_update_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,            \
+                                                const TYPE *d_g, ADMM_SET(TYPE), const TYPE *d_rho, const TYPE *d_z, TYPE *d_w,     \
+                                                TYPE *d_y, TYPE *d_gt, TYPE *d_res, void *stream)                                   \
+    {                                                                                                                               \
+        return admm_update_impl<TYPE>(h, nx, nu, N, batch, d_g, d_lo, d_hi, d_rho, d_z, d_w, d_y, d_gt, d_res, stream, false,       \
+                                      d_kappa, true);                                                                               \
+    }
+GBDPCG_ADMM_SOFT(f32, float)
+GBDPCG_ADMM_SOFT(f64, double)
+GBDPCG_ADMM_STEPS(admm_soft_step)
+GBDPCG_ADMM_RESTEPS(admm_soft_restep)
+#undef GBDPCG_ADMM_SOFT
+#undef ADMM_SIZES
+#undef ADMM_SET
+#undef ADMM_CONES
+#undef ADMM_OPERANDS
 #undef ADMM_MATS
 #undef ADMM_GT
 #undef GBDPCG_ADMM_ROWS

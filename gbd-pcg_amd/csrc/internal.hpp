@@ -256,9 +256,11 @@ hipError_t launch_kkt_residual(const DeviceInfo &dev, uint32_t nx, uint32_t nu, 
 // Every array has the layout of g ((nx + nu) N - nu elements per problem), rho [batch], res [2 batch]:
 //     w <- clip(z + y, lo, hi), y <- (z + y) - w, gt <- fma(-rho_b, w - y, g), res[2b] = ||z - w||_inf, res[2b+1] = rho_b ||w - w_old||_inf
 // init: w <- clip(w, lo, hi), gt <- fma(-rho_b, w - y, g); y is not written, z and res are not looked at (may be null).
+// kappa (the gbdpcg_admm_soft_* calls; null: the hard box): the layout of lo, the weight of the L1 penalty on leaving the bound --
+// the kernel's SOFT instantiation, whose lines are in the head of admm.hip; kappa = +Inf everywhere gives the hard bits.
 template <typename T>
 hipError_t launch_admm_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *g, const T *lo, const T *hi, const T *rho,
-                              const T *z, T *w, T *y, T *gt, T *res, hipStream_t s, bool init);
+                              const T *z, T *w, T *y, T *gt, T *res, hipStream_t s, bool init, const T *kappa = nullptr);
 
 // ---- admm_rebalance.hip : adaptive rho by residual balancing in powers of two, one launch, one workgroup per problem.  From
 // r = res[2b], s = res[2b+1] and rho_b: rho_b <- rho_b 2^e with e in {+shift, -shift, 0} (the rule is in the head of the file and in
@@ -276,6 +278,8 @@ hipError_t launch_admm_rebalance(uint64_t len, uint32_t batch, const T *g, const
 // shared: E is one problem's blocks, used by every problem of the batch.
 // cones (the gbdpcg_admm_soc_* calls; null: every row is linear): the rows behind the first lx / lu of a block are cones of
 // dimension qx / qu, lo holds their offsets.  With cones the launch is the kernel's CONES instantiation, whatever the classes say.
+// kappa (the gbdpcg_admm_lin_soft_* calls; null: hard rows): the layout of lo, the L1 weights -- the kernel's SOFT instantiation.
+// Never with cones (refused): cone rows stay hard.
 struct RowClasses {
     uint32_t lx, qx, lu, qu;
 };
@@ -285,7 +289,8 @@ hipError_t launch_admm_lin_form(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t 
 template <typename T>
 hipError_t launch_admm_rows_update(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *g,
                                    const T *E, const T *lo, const T *hi, const T *rho, const T *z, T *w, T *y, T *gt, T *res,
-                                   hipStream_t s, bool init, bool shared = false, const RowClasses *cones = nullptr);
+                                   hipStream_t s, bool init, bool shared = false, const RowClasses *cones = nullptr,
+                                   const T *kappa = nullptr);
 // (mx, mu <= 64 and one knot's E blocks, z, t, d within the kernel's LDS)
 template <typename T> bool admm_rows_shape_ok(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu);
 uint32_t admm_rows_knot_chunk(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu);

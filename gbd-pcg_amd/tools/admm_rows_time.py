@@ -95,6 +95,14 @@ def one_shape(s, nx, nu, N, B, mx, mu, cones, dtype, a):
                                   it, fl, z, L["w"], L["y"], L["gt"], L["res"])
     g_soc = s.graph_admm_soc_step(nx, nu, mx, mu, cones, N, B, Ginv, C, g, c, E, slo, hi, rho, S, Pinv, gamma, lam, None, None, a.tol,
                                   a.max_iter, it, fl, z, Q["w"], Q["y"], Q["gt"], Q["res"])
+    # the soft twin of the linear rows on a state of its own: kappa = +Inf for the first half of the batch, 0.1 for the second
+    kappa = torch.full((B, nw), float("inf"), dtype=td, device="cuda")
+    kappa[B // 2:] = 0.1
+    kappa = kappa.reshape(-1).contiguous()
+    F = dict(w=torch.zeros_like(lo), y=torch.zeros_like(lo), res=torch.empty(B, 2, dtype=td, device="cuda"))
+    F["gt"] = s.admm_lin_soft_init(nx, nu, mx, mu, N, B, g, E, lo, hi, kappa, rho, F["w"], F["y"])
+    g_soft = s.graph_admm_lin_soft_step(nx, nu, mx, mu, N, B, Ginv, C, g, c, E, lo, hi, kappa, rho, S, Pinv, gamma, lam, None, None, a.tol,
+                                        a.max_iter, it, fl, z, F["w"], F["y"], F["gt"], F["res"])
     # the box update of the same run, on buffers of its own in the layout of z
     blo, bhi = torch.full_like(g, -1.0), torch.full_like(g, 1.0)
     bw, by, bgt, bres = torch.zeros_like(g), torch.zeros_like(g), torch.empty_like(g), torch.empty(B, 2, dtype=td, device="cuda")
@@ -107,10 +115,14 @@ def one_shape(s, nx, nu, N, B, mx, mu, cones, dtype, a):
              "lin update": lambda: s.admm_lin_update(nx, nu, mx, mu, N, B, g, E, lo, hi, rho, z, L["w"], L["y"], L["gt"], res=L["res"]),
              "lin form": lambda: s.admm_lin_form(nx, nu, mx, mu, N, B, G, E, rho, Gt=Gt),
              "box update": lambda: s.admm_update(nx, nu, N, B, g, blo, bhi, rho, z, bw, by, bgt, res=bres),
-             "resolve replay": lambda: replay(g_res), "lin step replay": lambda: replay(g_lin), "soc step replay": lambda: replay(g_soc)}
+             "resolve replay": lambda: replay(g_res), "lin step replay": lambda: replay(g_lin), "soc step replay": lambda: replay(g_soc),
+             "lin soft update": lambda: s.admm_lin_soft_update(nx, nu, mx, mu, N, B, g, E, lo, hi, kappa, rho, z, F["w"], F["y"], F["gt"],
+                                                               res=F["res"]),
+             "lin soft step replay": lambda: replay(g_soft)}
     for _ in range(30):      # a few iterations first: the loops do what they are for
         g_lin.launch()
         g_soc.launch()
+        g_soft.launch()
     torch.cuda.synchronize()
     for kind, d in st.items():
         print(f"  {kind} after 30 iterations: max primal residual {float(d['res'][:, 0].max()):.2e}, max dual residual "
@@ -137,7 +149,13 @@ def one_shape(s, nx, nu, N, B, mx, mu, cones, dtype, a):
     bl, bb = must["lin update"] / med["lin update"], must["box update"] / med["box update"]
     print(f"  lin update / box update: time {med['lin update'] / med['box update']:.2f} x, bytes {must['lin update'] / must['box update']:.2f} x, "
           f"bytes over time {bl / bb:.2f} x;  lin update alone / resolve replay {100.0 * med['lin update'] / med['resolve replay']:.1f} %")
-    for gr in (g_res, g_lin, g_soc):
+    # the soft twin of the same run: one more read per row ((5 + 2) / (4 + 2) of the per-row traffic) and one division per row
+    must["lin soft update"] = must["lin update"] + nw * es * B
+    print(f"  {'lin soft update launch alone':30s} {stat(t['lin soft update'])}; algorithmic bytes {rate(must['lin soft update'], med['lin soft update'])}; "
+          f"{med['lin soft update'] / med['lin update']:.3f} of the hard update launch (bytes {must['lin soft update'] / must['lin update']:.3f})")
+    print(f"  {'admm_lin_soft_step graph replay':30s} {stat(t['lin soft step replay'])}; "
+          f"{med['lin soft step replay'] / med['lin step replay']:.3f} of the hard step replay")
+    for gr in (g_res, g_lin, g_soc, g_soft):
         gr.close()
 
 

@@ -1105,6 +1105,271 @@ gbdpcg_status gbdpcg_graph_create_admm_soc_restep_f64(gbdpcg_handle_t h, uint32_
                                                       double *d_res, double ratio, uint32_t shift, double rho_min, double rho_max,
                                                       int32_t *d_expo, gbdpcg_graph_t *out);
 
+/* Soft (L1-penalised) bounds for the box and the linear-row families: gbdpcg_admm_soft_* and gbdpcg_admm_lin_soft_*.  Every bound of
+ * the hard families is a constraint; after a disturbance a state bound can contradict Cz = c, the hard problem then has no feasible
+ * point, d_res[2b] stalls at the distance between the affine set and the box and y grows without bound.  The soft families replace
+ * the constraint on row r by the exact penalty kappa_r dist(v_r, [lo_r, hi_r]) in the cost, v = z (box) or v = E z (rows): always
+ * feasible, and equal to the hard solution wherever kappa_r exceeds the hard multiplier |mu_r| = rho |y_r| of that row, which the
+ * caller can read from d_y of a hard (or sufficiently weighted soft) run.  d_kappa has the layout of d_lo and d_hi and stands
+ * directly behind d_hi in every argument list, which otherwise is the hard family's; kappa_r in [0, +Inf] per row and per problem
+ * (also in the _shared twins), in the call's precision.  Only the projection line of the update changes; with s = fl(v + y), every
+ * line one IEEE operation or a comparison, / correctly rounded:
+ *     p     = s < lo ? lo : (s > hi ? hi : s)                    the clip of the hard update
+ *     e     = fl(s - p)                                          exactly 0 inside the bounds
+ *     theta = fl(kappa / rho_b)
+ *     w+    = e > theta ? fl(s - theta) : (e < -theta ? fl(s + theta) : p)
+ *     y+    = e > theta ? theta         : (e < -theta ? -theta        : e)
+ * and gt+, d_res[2b], d_res[2b+1] follow from w+, y+ and the old w exactly as in the hard update.  So |y_r| <= fl(kappa_r / rho_b):
+ * the multiplier mu = rho y is bounded by the weight.
+ *  - kappa = +Inf: the third branch, whose operations w+ = p, y+ = fl(s - p) are those of the hard update -- with +Inf everywhere
+ *    every output of every gbdpcg_admm_soft_* / gbdpcg_admm_lin_soft_* call has the bits of the hard call.  Inputs are kept hard
+ *    this way (or with a large finite kappa), states get a finite kappa.
+ *  - kappa = 0: the row is free (w+ = s, y+ = 0).  A tie e = +-theta takes the third branch.  A NaN s fails every comparison and
+ *    stays NaN, inside its own problem.
+ *  - init (gbdpcg_admm_soft_init_*, gbdpcg_admm_lin_soft_init_*): w <- (kappa == +Inf) ? clip(w, lo, hi) : w -- a soft row admits any
+ *    w, so the init is idempotent and a restep does not move w; y is not written; gt is computed from w - y as in the hard init.
+ *  - step, the _shared twins, the graphs: the hard family's composition with the soft update launch, the same bits as the calls they
+ *    are made of.
+ *  - adaptive rho.  gbdpcg_admm_rebalance_* IS the rebalance of the soft box family: it never looks at the bounds and does not clip
+ *    w.  gbdpcg_admm_lin_soft_rebalance_* is the launch of gbdpcg_admm_lin_rebalance_* followed by gbdpcg_admm_lin_soft_init_*.
+ *    gbdpcg_admm_soft_restep_* = gbdpcg_admm_rebalance_*, gbdpcg_kkt_step_reg_*, gbdpcg_admm_soft_update_*;
+ *    gbdpcg_admm_lin_soft_restep_* = its rebalance, gbdpcg_admm_lin_form_*, gbdpcg_kkt_step_*, gbdpcg_admm_lin_soft_update_*.  The
+ *    scaling of y is a power of two and so is that of theta: |y| <= fl(kappa / rho') holds after a rebalance (short of subnormals).
+ *  - d_kappa, like d_rho, d_lo and d_hi, is NOT validated on the device: a negative or NaN kappa is the caller's error and gives
+ *    what the formulas give, inside its own problem.
+ *  - not provided: soft cone rows (the prox of a distance-to-cone penalty is another closed form; gbdpcg_admm_soc_* stay hard),
+ *    quadratic penalties, per-side weights, a _shared restep.
+ * Refused: a NULL d_kappa with GBDPCG_ERR_INVALID before anything is written; everything else as the hard family refuses it, in the
+ * same order. */
+gbdpcg_status gbdpcg_admm_soft_init_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_g,
+                                        const float *d_lo, const float *d_hi, const float *d_kappa, const float *d_rho, float *d_w,
+                                        float *d_y, float *d_gt, void *stream);
+gbdpcg_status gbdpcg_admm_soft_init_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_g,
+                                        const double *d_lo, const double *d_hi, const double *d_kappa, const double *d_rho,
+                                        double *d_w, double *d_y, double *d_gt, void *stream);
+gbdpcg_status gbdpcg_admm_soft_update_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_g,
+                                          const float *d_lo, const float *d_hi, const float *d_kappa, const float *d_rho,
+                                          const float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_soft_update_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                          const double *d_g, const double *d_lo, const double *d_hi, const double *d_kappa,
+                                          const double *d_rho, const double *d_z, double *d_w, double *d_y, double *d_gt,
+                                          double *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_soft_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                        const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                        const float *d_lo, const float *d_hi, const float *d_kappa, const float *d_rho,
+                                        const float *d_S, const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r,
+                                        float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                        float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_soft_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                        const double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                        const double *d_lo, const double *d_hi, const double *d_kappa, const double *d_rho,
+                                        const double *d_S, const double *d_Pinv, double *d_gamma, double *d_lambda, double *d_r,
+                                        double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                        double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_soft_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                     const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                                     const float *d_lo, const float *d_hi, const float *d_kappa, const float *d_rho,
+                                                     const float *d_S, const float *d_Pinv, float *d_gamma, float *d_lambda,
+                                                     float *d_r, float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                                     uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y, float *d_gt,
+                                                     float *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_soft_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                     const double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                                     const double *d_lo, const double *d_hi, const double *d_kappa,
+                                                     const double *d_rho, const double *d_S, const double *d_Pinv, double *d_gamma,
+                                                     double *d_lambda, double *d_r, double *d_p, double tol, uint32_t max_iter,
+                                                     uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z, double *d_w,
+                                                     double *d_y, double *d_gt, double *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_admm_soft_step_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                               const float *d_Ginv, const float *d_C, const float *d_g, const float *d_c,
+                                               const float *d_lo, const float *d_hi, const float *d_kappa, const float *d_rho,
+                                               const float *d_S, const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r,
+                                               float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                               uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y, float *d_gt,
+                                               float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_soft_step_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                               const double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                               const double *d_lo, const double *d_hi, const double *d_kappa, const double *d_rho,
+                                               const double *d_S, const double *d_Pinv, double *d_gamma, double *d_lambda,
+                                               double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                               uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y, double *d_gt,
+                                               double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_soft_step_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                            const float *d_Ginv, const float *d_C, const float *d_g,
+                                                            const float *d_c, const float *d_lo, const float *d_hi,
+                                                            const float *d_kappa, const float *d_rho, const float *d_S,
+                                                            const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r,
+                                                            float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                                            uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y,
+                                                            float *d_gt, float *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_soft_step_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                            const double *d_Ginv, const double *d_C, const double *d_g,
+                                                            const double *d_c, const double *d_lo, const double *d_hi,
+                                                            const double *d_kappa, const double *d_rho, const double *d_S,
+                                                            const double *d_Pinv, double *d_gamma, double *d_lambda, double *d_r,
+                                                            double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                            uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y,
+                                                            double *d_gt, double *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_admm_soft_restep_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_G,
+                                          float *d_Ginv, const float *d_C, const float *d_g, const float *d_c, const float *d_lo,
+                                          const float *d_hi, const float *d_kappa, float *d_rho, float *d_S, float *d_Pinv,
+                                          gbdpcg_pinv_kind kind, float *d_gamma, float *d_lambda, float *d_r, float *d_p, float tol,
+                                          uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_z, float *d_w,
+                                          float *d_y, float *d_gt, float *d_res, float ratio, uint32_t shift, float rho_min,
+                                          float rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_admm_soft_restep_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                          const double *d_G, double *d_Ginv, const double *d_C, const double *d_g,
+                                          const double *d_c, const double *d_lo, const double *d_hi, const double *d_kappa,
+                                          double *d_rho, double *d_S, double *d_Pinv, gbdpcg_pinv_kind kind, double *d_gamma,
+                                          double *d_lambda, double *d_r, double *d_p, double tol, uint32_t max_iter,
+                                          uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y,
+                                          double *d_gt, double *d_res, double ratio, uint32_t shift, double rho_min, double rho_max,
+                                          int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_soft_restep_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                       const float *d_G, float *d_Ginv, const float *d_C, const float *d_g,
+                                                       const float *d_c, const float *d_lo, const float *d_hi, const float *d_kappa,
+                                                       float *d_rho, float *d_S, float *d_Pinv, gbdpcg_pinv_kind kind,
+                                                       float *d_gamma, float *d_lambda, float *d_r, float *d_p, float tol,
+                                                       uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_z,
+                                                       float *d_w, float *d_y, float *d_gt, float *d_res, float ratio,
+                                                       uint32_t shift, float rho_min, float rho_max, int32_t *d_expo,
+                                                       gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_soft_restep_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                       const double *d_G, double *d_Ginv, const double *d_C, const double *d_g,
+                                                       const double *d_c, const double *d_lo, const double *d_hi,
+                                                       const double *d_kappa, double *d_rho, double *d_S, double *d_Pinv,
+                                                       gbdpcg_pinv_kind kind, double *d_gamma, double *d_lambda, double *d_r,
+                                                       double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                       uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y,
+                                                       double *d_gt, double *d_res, double ratio, uint32_t shift, double rho_min,
+                                                       double rho_max, int32_t *d_expo, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_admm_lin_soft_init_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                            uint32_t batch, const float *d_g, const float *d_E, const float *d_lo,
+                                            const float *d_hi, const float *d_kappa, const float *d_rho, float *d_w, float *d_y,
+                                            float *d_gt, void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_init_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                            uint32_t batch, const double *d_g, const double *d_E, const double *d_lo,
+                                            const double *d_hi, const double *d_kappa, const double *d_rho, double *d_w,
+                                            double *d_y, double *d_gt, void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_update_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                              uint32_t batch, const float *d_g, const float *d_E, const float *d_lo,
+                                              const float *d_hi, const float *d_kappa, const float *d_rho, const float *d_z,
+                                              float *d_w, float *d_y, float *d_gt, float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_update_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                              uint32_t batch, const double *d_g, const double *d_E, const double *d_lo,
+                                              const double *d_hi, const double *d_kappa, const double *d_rho, const double *d_z,
+                                              double *d_w, double *d_y, double *d_gt, double *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                            uint32_t batch, const float *d_Ginv, const float *d_C, const float *d_g,
+                                            const float *d_c, const float *d_E, const float *d_lo, const float *d_hi,
+                                            const float *d_kappa, const float *d_rho, const float *d_S, const float *d_Pinv,
+                                            float *d_gamma, float *d_lambda, float *d_r, float *d_p, float tol, uint32_t max_iter,
+                                            uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y,
+                                            float *d_gt, float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                            uint32_t batch, const double *d_Ginv, const double *d_C, const double *d_g,
+                                            const double *d_c, const double *d_E, const double *d_lo, const double *d_hi,
+                                            const double *d_kappa, const double *d_rho, const double *d_S, const double *d_Pinv,
+                                            double *d_gamma, double *d_lambda, double *d_r, double *d_p, double tol,
+                                            uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z,
+                                            double *d_w, double *d_y, double *d_gt, double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_lin_soft_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                         uint32_t N, uint32_t batch, const float *d_Ginv, const float *d_C,
+                                                         const float *d_g, const float *d_c, const float *d_E, const float *d_lo,
+                                                         const float *d_hi, const float *d_kappa, const float *d_rho,
+                                                         const float *d_S, const float *d_Pinv, float *d_gamma, float *d_lambda,
+                                                         float *d_r, float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                                         uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y, float *d_gt,
+                                                         float *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_lin_soft_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                         uint32_t N, uint32_t batch, const double *d_Ginv, const double *d_C,
+                                                         const double *d_g, const double *d_c, const double *d_E,
+                                                         const double *d_lo, const double *d_hi, const double *d_kappa,
+                                                         const double *d_rho, const double *d_S, const double *d_Pinv,
+                                                         double *d_gamma, double *d_lambda, double *d_r, double *d_p, double tol,
+                                                         uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                                         double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res,
+                                                         gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_admm_lin_soft_step_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                   uint32_t N, uint32_t batch, const float *d_Ginv, const float *d_C,
+                                                   const float *d_g, const float *d_c, const float *d_E, const float *d_lo,
+                                                   const float *d_hi, const float *d_kappa, const float *d_rho, const float *d_S,
+                                                   const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r, float *d_p,
+                                                   float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                                   float *d_z, float *d_w, float *d_y, float *d_gt, float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_step_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                   uint32_t N, uint32_t batch, const double *d_Ginv, const double *d_C,
+                                                   const double *d_g, const double *d_c, const double *d_E, const double *d_lo,
+                                                   const double *d_hi, const double *d_kappa, const double *d_rho,
+                                                   const double *d_S, const double *d_Pinv, double *d_gamma, double *d_lambda,
+                                                   double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                   uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y, double *d_gt,
+                                                   double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_lin_soft_step_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx,
+                                                                uint32_t mu, uint32_t N, uint32_t batch, const float *d_Ginv,
+                                                                const float *d_C, const float *d_g, const float *d_c,
+                                                                const float *d_E, const float *d_lo, const float *d_hi,
+                                                                const float *d_kappa, const float *d_rho, const float *d_S,
+                                                                const float *d_Pinv, float *d_gamma, float *d_lambda, float *d_r,
+                                                                float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                                                uint8_t *d_max_iter_exit, float *d_z, float *d_w, float *d_y,
+                                                                float *d_gt, float *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_lin_soft_step_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx,
+                                                                uint32_t mu, uint32_t N, uint32_t batch, const double *d_Ginv,
+                                                                const double *d_C, const double *d_g, const double *d_c,
+                                                                const double *d_E, const double *d_lo, const double *d_hi,
+                                                                const double *d_kappa, const double *d_rho, const double *d_S,
+                                                                const double *d_Pinv, double *d_gamma, double *d_lambda,
+                                                                double *d_r, double *d_p, double tol, uint32_t max_iter,
+                                                                uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_z,
+                                                                double *d_w, double *d_y, double *d_gt, double *d_res,
+                                                                gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_admm_lin_soft_rebalance_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                                 uint32_t batch, const float *d_g, const float *d_E, const float *d_lo,
+                                                 const float *d_hi, const float *d_kappa, const float *d_res, float *d_rho,
+                                                 float *d_w, float *d_y, float *d_gt, float ratio, uint32_t shift, float rho_min,
+                                                 float rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_rebalance_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                                 uint32_t batch, const double *d_g, const double *d_E, const double *d_lo,
+                                                 const double *d_hi, const double *d_kappa, const double *d_res, double *d_rho,
+                                                 double *d_w, double *d_y, double *d_gt, double ratio, uint32_t shift,
+                                                 double rho_min, double rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_restep_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                              uint32_t batch, const float *d_G, float *d_Gt, float *d_Ginv, const float *d_C,
+                                              const float *d_g, const float *d_c, const float *d_E, const float *d_lo,
+                                              const float *d_hi, const float *d_kappa, float *d_rho, float *d_S, float *d_Pinv,
+                                              gbdpcg_pinv_kind kind, float *d_gamma, float *d_lambda, float *d_r, float *d_p,
+                                              float tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_z,
+                                              float *d_w, float *d_y, float *d_gt, float *d_res, float ratio, uint32_t shift,
+                                              float rho_min, float rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_restep_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                              uint32_t batch, const double *d_G, double *d_Gt, double *d_Ginv, const double *d_C,
+                                              const double *d_g, const double *d_c, const double *d_E, const double *d_lo,
+                                              const double *d_hi, const double *d_kappa, double *d_rho, double *d_S, double *d_Pinv,
+                                              gbdpcg_pinv_kind kind, double *d_gamma, double *d_lambda, double *d_r, double *d_p,
+                                              double tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
+                                              double *d_z, double *d_w, double *d_y, double *d_gt, double *d_res, double ratio,
+                                              uint32_t shift, double rho_min, double rho_max, int32_t *d_expo, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_lin_soft_restep_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                           uint32_t N, uint32_t batch, const float *d_G, float *d_Gt, float *d_Ginv,
+                                                           const float *d_C, const float *d_g, const float *d_c, const float *d_E,
+                                                           const float *d_lo, const float *d_hi, const float *d_kappa, float *d_rho,
+                                                           float *d_S, float *d_Pinv, gbdpcg_pinv_kind kind, float *d_gamma,
+                                                           float *d_lambda, float *d_r, float *d_p, float tol, uint32_t max_iter,
+                                                           uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_z, float *d_w,
+                                                           float *d_y, float *d_gt, float *d_res, float ratio, uint32_t shift,
+                                                           float rho_min, float rho_max, int32_t *d_expo, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_lin_soft_restep_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                           uint32_t N, uint32_t batch, const double *d_G, double *d_Gt,
+                                                           double *d_Ginv, const double *d_C, const double *d_g, const double *d_c,
+                                                           const double *d_E, const double *d_lo, const double *d_hi,
+                                                           const double *d_kappa, double *d_rho, double *d_S, double *d_Pinv,
+                                                           gbdpcg_pinv_kind kind, double *d_gamma, double *d_lambda, double *d_r,
+                                                           double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                           uint8_t *d_max_iter_exit, double *d_z, double *d_w, double *d_y,
+                                                           double *d_gt, double *d_res, double ratio, uint32_t shift,
+                                                           double rho_min, double rho_max, int32_t *d_expo, gbdpcg_graph_t *out);
+
 /* The backward pass: gradients of a scalar through (G, C, g, c) -> (z, lambda), on the device.  Forward convention as above:
  * G z + g + C' lambda = 0, C z = c.  For a scalar l with upstream gradients gz = dl/dz (layout of d_g) and glam = dl/dlambda (layout
  * of d_c) let (a_z, a_lambda) solve the SAME KKT matrix with the right-hand side (-gz, -glam).  The matrix is symmetric, so this
