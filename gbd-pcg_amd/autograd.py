@@ -6,6 +6,10 @@ Phi^-1 and G^-1 the forward pass left behind -- one adjoint solve and one gradie
 shared-matrix batch the two are gbdpcg_kkt_resolve_shared_* and gbdpcg_kkt_grad_shared_*, with the adjoint pairs of problems outside
 the loss zeroed in between.  Nothing here computes a gradient in torch except dl/drho = a_z' z, one dot product per problem, and the
 selects that give problems with zero cotangents zero gradients.  There is no CPU path.
+
+box_qp_solve adds the hard box lo <= z <= hi: the forward pass is gbdpcg_kkt_step_reg_* followed by a fixed number of
+gbdpcg_admm_step_*, the backward pass the same ADMM iteration on the adjoint QP (gbdpcg_admm_adjoint_*: the forward y is the mask of
+the active set), gbdpcg_admm_grad_bounds_* and gbdpcg_kkt_grad_*; (G, C, g, c, lo, hi) -> (w, lambda).
 """
 from __future__ import annotations
 
@@ -81,6 +85,103 @@ class _KktSolve(torch.autograd.Function):
         grho = keep((az.view(batch, -1) * z.view(batch, -1)).sum(1)) if has_rho and ctx.needs_input_grad[4] else None
         grads = [t if t is None else t.view(s) for t, s in zip((gG, gC, az, -alam), ctx.shapes)]
         return (*grads, grho) + (None,) * 8
+
+
+class _BoxQpSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, G, C, g, c, lo, hi, rho, solver, nx, nu, N, batch, iters, adj_iters, tol, max_iter):
+        sz = _sizes(nx, nu, N)
+        kw = dict(dtype=g.dtype, device=g.device)
+        S = torch.empty(batch * 3 * nx * nx * N, **kw)
+        Pinv, Ginv = torch.empty_like(S), torch.empty(batch * sz["G"], **kw)
+        gamma = torch.empty(batch * sz["c"], **kw)
+        lam, z = torch.zeros(batch * sz["c"], **kw), torch.empty(batch * sz["g"], **kw)
+        w, y = torch.zeros(batch * sz["g"], **kw), torch.zeros(batch * sz["g"], **kw)
+        res = torch.zeros(batch, 2, **kw)
+        ctx.shapes = tuple(t.shape for t in (G, C, g, c, lo, hi))
+        G, C, g, c, lo, hi, rho = (t.detach().reshape(-1) for t in (G, C, g, c, lo, hi, rho))
+        Cp = C if N > 1 else None
+        solver.kkt_step_reg(nx, nu, N, batch, G, Cp, g, c, rho, S, gamma, Ginv, Pinv, lam, z, tol=tol, max_iter=max_iter)
+        gt = solver.admm_init(nx, nu, N, batch, g, lo, hi, rho, w, y)
+        for _ in range(iters):
+            solver.admm_step(nx, nu, N, batch, Ginv, Cp, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=res, tol=tol,
+                             max_iter=max_iter)
+        ctx.save_for_backward(Ginv, S, Pinv, C, w, lam, y, rho)
+        ctx.args = (solver, nx, nu, N, batch, adj_iters, tol, max_iter)
+        ctx.mark_non_differentiable(res)
+        return w, lam, res
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gw, glam, _gres):
+        Ginv, S, Pinv, C, w, lam, yf, rho = ctx.saved_tensors
+        solver, nx, nu, N, batch, adj_iters, tol, max_iter = ctx.args
+        sz = _sizes(nx, nu, N)
+        Cp = C if N > 1 else None
+        gz = torch.zeros_like(w) if gw is None else gw.contiguous().view(-1)
+        nglam = torch.zeros_like(lam) if glam is None else -glam.contiguous().view(-1)
+        gamma, alam, az = torch.empty_like(lam), torch.zeros_like(lam), torch.empty_like(w)
+        wa, ya = torch.zeros_like(w), torch.zeros_like(w)
+        res = torch.empty(batch, 2, dtype=w.dtype, device=w.device)
+        need_G, need_C = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and N > 1
+        # (a problem with exactly zero cotangents: as in _KktSolve.backward -- its adjoint solves return NaN, its gradients are
+        # exactly zero; the mask and the selects run in stream order)
+        live = ((gz.view(batch, -1) != 0).any(1) | (nglam.view(batch, -1) != 0).any(1)).view(batch, 1)
+
+        def keep(t):
+            return None if t is None else torch.where(live, t.view(batch, -1), t.new_zeros(())).view(-1)
+
+        gta = solver.admm_adjoint_init(nx, nu, N, batch, gz, yf, rho, wa, ya)
+        for _ in range(adj_iters):
+            solver.admm_adjoint_step(nx, nu, N, batch, Ginv, Cp, gz, nglam, yf, rho, S, Pinv, gamma, alam, az, wa, ya, gta, res=res,
+                                     tol=tol, max_iter=max_iter)
+        glo, ghi = solver.admm_grad_bounds(nx, nu, N, batch, yf, rho, ya)
+        gG = gC = None
+        if need_G or need_C:
+            gG = torch.empty(batch * sz["G"], dtype=w.dtype, device=w.device) if need_G else None
+            gC = torch.empty(batch * sz["C"], dtype=w.dtype, device=w.device) if need_C else None
+            solver.kkt_grad(nx, nu, N, batch, w, lam, wa, alam, gG=gG, gC=gC, want="")
+        out = [keep(t) for t in (gG, gC, wa, -alam, glo, ghi)]
+        if ctx.needs_input_grad[1] and N == 1:
+            out[1] = torch.zeros(batch * sz["C"], dtype=w.dtype, device=w.device)
+        grads = [t if t is None else t.view(s) for t, s in zip(out, ctx.shapes)]
+        return (*grads, None) + (None,) * 9
+
+
+def box_qp_solve(solver, nx, nu, N, G, C, g, c, lo, hi, rho, iters, adj_iters, tol=1e-6, max_iter=25):
+    """(w, lambda, res) of  min 1/2 z'Gz + g'z  subject to  Cz = c, lo <= z <= hi  for a batch of problems, differentiable in G, C, g,
+    c, lo and hi; res [batch, 2] (the ADMM residuals of the last iteration) is not differentiable, and rho gets no gradient (the
+    solution does not depend on it).
+
+    Flat contiguous device tensors of one dtype in the packed layouts of include/gbdpcg.h; lo, hi have the layout of g (-Inf / +Inf:
+    no bound), rho [batch] > 0 is the ADMM penalty.  Forward: gbdpcg_kkt_step_reg_*, gbdpcg_admm_init_* from w = y = 0, then `iters`
+    gbdpcg_admm_step_*; w lies in the box exactly.  Backward: gbdpcg_admm_adjoint_init_* from zeros, `adj_iters`
+    gbdpcg_admm_adjoint_step_* on the kept factorisation, gbdpcg_admm_grad_bounds_*, gbdpcg_kkt_grad_*.  Both counts are fixed: nothing
+    waits for the device, and the gradients are only as converged as the two loops -- read res to judge the forward one.
+
+    The active set is the sign pattern of the forward y: entry i is clamped iff y_i != 0 (no threshold), its dl/dg_i is exactly 0 and
+    dl/dlo_i or dl/dhi_i carries the adjoint's multiplier.  An entry that sits on its bound with y_i = 0 (weakly active) counts as
+    free.  A forward loop that has not converged leaves whatever mask y holds.  tol, max_iter: the PCG settings of every solve.
+    A problem whose rows of dl/dw and dl/dlambda are exactly zero gets exactly zero gradients (as in kkt_solve)."""
+    if not isinstance(solver, binding.Solver):
+        raise TypeError("box_qp_solve: solver is a binding.Solver")
+    sz = _sizes(nx, nu, N)
+    for name, t in (("G", G), ("C", C), ("g", g), ("c", c), ("lo", lo), ("hi", hi), ("rho", rho)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == g.dtype):
+            raise ValueError(f"box_qp_solve: {name} must be a contiguous device tensor of g's dtype")
+    if g.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"box_qp_solve: unsupported dtype {g.dtype}")
+    if g.numel() == 0 or g.numel() % sz["g"]:
+        raise ValueError("box_qp_solve: g is not a whole number of problems")
+    batch = g.numel() // sz["g"]
+    want = {"G": batch * sz["G"], "C": batch * sz["C"], "g": batch * sz["g"], "c": batch * sz["c"], "lo": batch * sz["g"],
+            "hi": batch * sz["g"], "rho": batch}
+    for name, t in (("G", G), ("C", C), ("c", c), ("lo", lo), ("hi", hi), ("rho", rho)):
+        if t.numel() != want[name]:
+            raise ValueError(f"box_qp_solve: {name} has {t.numel()} elements, the layout takes {want[name]}")
+    if int(iters) < 1 or int(adj_iters) < 1:
+        raise ValueError("box_qp_solve: iters and adj_iters are at least 1")
+    return _BoxQpSolve.apply(G, C, g, c, lo, hi, rho, solver, nx, nu, N, batch, int(iters), int(adj_iters), tol, max_iter)
 
 
 def kkt_solve(solver, nx, nu, N, G, C, g, c, rho=None, shared=False, tol=1e-6, max_iter=25):

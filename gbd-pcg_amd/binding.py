@@ -73,6 +73,9 @@ SYMBOLS = [
     "gbdpcg_kkt_backward_f32", "gbdpcg_kkt_backward_f64", "gbdpcg_kkt_backward_shared_f32", "gbdpcg_kkt_backward_shared_f64",
     "gbdpcg_graph_create_kkt_backward_f32", "gbdpcg_graph_create_kkt_backward_f64",
     "gbdpcg_graph_create_kkt_backward_shared_f32", "gbdpcg_graph_create_kkt_backward_shared_f64",
+    # the backward pass of the hard box QP: the forward y where lo, hi stand
+    *[f"gbdpcg_{name}_{suf}" for name in ("admm_adjoint_init", "admm_adjoint_update", "admm_adjoint_step",
+                                          "graph_create_admm_adjoint_step", "admm_grad_bounds") for suf in ("f32", "f64")],
     "gbdpcg_demote_f32", "gbdpcg_kkt_defect_mixed", "gbdpcg_kkt_refine_apply", "gbdpcg_kkt_refine_step",
     "gbdpcg_graph_create_kkt_refine_step",
     "gbdpcg_kkt_defect_mixed_reg", "gbdpcg_kkt_defect_mixed_shared", "gbdpcg_kkt_refine_step_reg", "gbdpcg_kkt_refine_step_shared",
@@ -145,6 +148,17 @@ def _resolve_argtypes(lib):
         for name in ("kkt_backward", "kkt_backward_shared"):
             getattr(lib, f"gbdpcg_{name}_{suf}").argtypes = back + [vp]
             getattr(lib, f"gbdpcg_graph_create_{name}_{suf}").argtypes = back + [ctypes.POINTER(vp)]
+        # the backward pass of the hard box QP: the box family with yf where lo, hi stand
+        #   init    h, nx, nu, N, batch | gz | yf, rho | wa, ya, gta | stream
+        #   update  ...                 | gz | yf, rho | az, wa, ya, gta, res | stream
+        #   step    ...   | Ginv, C, gz, nglam | yf, rho | the solve's arguments (lambda := alambda, z := az) | wa, ya, gta, res |
+        #   grad_bounds ...             | yf, rho, ya | glo, ghi | stream
+        getattr(lib, f"gbdpcg_admm_adjoint_init_{suf}").argtypes = sizes + [vp] + [vp, vp] + [vp, vp, vp] + [vp]
+        getattr(lib, f"gbdpcg_admm_adjoint_update_{suf}").argtypes = sizes + [vp] + [vp, vp] + [vp, vp, vp, vp, vp] + [vp]
+        adj = sizes + [vp, vp, vp, vp] + [vp, vp] + solve + [vp, vp, vp, vp]
+        getattr(lib, f"gbdpcg_admm_adjoint_step_{suf}").argtypes = adj + [vp]
+        getattr(lib, f"gbdpcg_graph_create_admm_adjoint_step_{suf}").argtypes = adj + [ctypes.POINTER(vp)]
+        getattr(lib, f"gbdpcg_admm_grad_bounds_{suf}").argtypes = sizes + [vp, vp, vp] + [vp, vp] + [vp]
 
     # mixed-precision refinement (no suffix: fp64 data and point, fp32 solve)
     head = [vp, u32, u32, u32, u32, vp, vp, vp, vp]                # h, nx, nu, N, batch, G, C, g, c (fp64)
@@ -1238,6 +1252,84 @@ class Solver:
         """Capture the shared-matrix backward pass into one hipGraph (gbdpcg_graph_create_kkt_backward_shared_*)."""
         return self._graph_kkt_backward("kkt_backward_shared", nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam,
                                         r, p, tol, max_iter, iters, max_iter_exit, gG, gC)
+
+    # ---- the backward pass of the hard box QP (include/gbdpcg.h): the box family with yf, the forward y, where lo, hi stand; gz =
+    # dl/dz in the place of g, nglam = -dl/dlambda in the place of c; wa, ya, gta the adjoint's splitting state, in the layout of g
+    def admm_adjoint_init(self, nx, nu, N, batch, gz, yf, rho, wa, ya, gta=None, stream=None):
+        """gbdpcg_admm_adjoint_init_*: wa <- 0 where yf != 0, gta <- gz - rho (wa - ya); ya is left alone.  Returns gta."""
+        import torch
+        suf, _ = _suffix(gz)
+        if gta is None:
+            gta = torch.empty_like(gz)
+        self._box(gz, batch, yf, wa, ya, gta)
+        fn = getattr(self.lib, f"gbdpcg_admm_adjoint_init_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(gz), _p(yf), _p(self._rho(rho, batch, gz)), _p(wa), _p(ya), _p(gta),
+                       self._stream(stream)), "admm_adjoint_init")
+        return gta
+
+    def admm_adjoint_update(self, nx, nu, N, batch, gz, yf, rho, az, wa, ya, gta, res=None, stream=None):
+        """gbdpcg_admm_adjoint_update_*: the update behind an adjoint solve that wrote az -- wa, ya, gta in place; returns the
+        [batch, 2] tensor of (||az - wa||_inf, rho ||wa - wa_old||_inf) per problem."""
+        import torch
+        suf, _ = _suffix(gz)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=gz.dtype, device=gz.device)
+        assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == gz.dtype
+        self._box(gz, batch, yf, az, wa, ya, gta)
+        fn = getattr(self.lib, f"gbdpcg_admm_adjoint_update_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(gz), _p(yf), _p(self._rho(rho, batch, gz)), _p(az), _p(wa), _p(ya), _p(gta),
+                       _p(res), self._stream(stream)), "admm_adjoint_update")
+        return res.view(batch, 2)
+
+    def _adjoint_step_args(self, nx, nu, N, batch, Ginv, C, gz, nglam, yf, rho, S, Pinv, gamma, alam, r, p, tol, max_iter, iters, mie,
+                           az, wa, ya, gta, res):
+        suf, _ = _suffix(gz)
+        assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == gz.dtype
+        self._box(gz, batch, yf, az, wa, ya, gta)
+        args = (self.h, nx, nu, N, batch, _p(Ginv), _p(C), _p(gz), _p(nglam), _p(yf), _p(self._rho(rho, batch, gz)), _p(S), _p(Pinv),
+                _p(gamma), _p(alam), _p(r), _p(p), tol, max_iter, _p(iters), _p(mie), _p(az), _p(wa), _p(ya), _p(gta), _p(res))
+        return suf, args, (Ginv, C, gz, nglam, yf, rho, S, Pinv, gamma, alam, r, p, iters, mie, az, wa, ya, gta, res)
+
+    def admm_adjoint_step(self, nx, nu, N, batch, Ginv, C, gz, nglam, yf, rho, S, Pinv, gamma, alam, az, wa, ya, gta, res=None, r=None,
+                          p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_admm_adjoint_step_*: kkt_resolve with g := gta, c := nglam (warm start from alam, writing alam and az), then
+        admm_adjoint_update, one call.  Returns (iters, flags, res [batch, 2])."""
+        import torch
+        if iters is None:
+            iters = torch.zeros(batch, dtype=torch.int32, device=gz.device)
+        if max_iter_exit is None:
+            max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=gz.device)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=gz.dtype, device=gz.device)
+        suf, args, _ = self._adjoint_step_args(nx, nu, N, batch, Ginv, C, gz, nglam, yf, rho, S, Pinv, gamma, alam, r, p, tol, max_iter,
+                                               iters, max_iter_exit, az, wa, ya, gta, res)
+        self._check(getattr(self.lib, f"gbdpcg_admm_adjoint_step_{suf}")(*args, self._stream(stream)), "admm_adjoint_step")
+        return iters, max_iter_exit, res.view(batch, 2)
+
+    def graph_admm_adjoint_step(self, nx, nu, N, batch, Ginv, C, gz, nglam, yf, rho, S, Pinv, gamma, alam, r, p, tol, max_iter, iters,
+                                max_iter_exit, az, wa, ya, gta, res):
+        """Capture one adjoint iteration into a hipGraph (gbdpcg_graph_create_admm_adjoint_step_*): replay it once per iteration;
+        the graph keeps rho's pointer."""
+        suf, args, keep = self._adjoint_step_args(nx, nu, N, batch, Ginv, C, gz, nglam, yf, rho, S, Pinv, gamma, alam, r, p, tol,
+                                                  max_iter, iters, max_iter_exit, az, wa, ya, gta, res)
+        gr = ctypes.c_void_p()
+        self._check(getattr(self.lib, f"gbdpcg_graph_create_admm_adjoint_step_{suf}")(*args, ctypes.byref(gr)),
+                    "graph_create_admm_adjoint_step")
+        return Graph(self, gr, keep=keep)
+
+    def admm_grad_bounds(self, nx, nu, N, batch, yf, rho, ya, glo=None, ghi=None, stream=None):
+        """gbdpcg_admm_grad_bounds_*: (dl/dlo, dl/dhi) = -rho ya where yf < 0 / yf > 0, +0 elsewhere, in the layout of g."""
+        import torch
+        suf, _ = _suffix(yf)
+        if glo is None:
+            glo = torch.empty_like(yf)
+        if ghi is None:
+            ghi = torch.empty_like(yf)
+        self._box(yf, batch, ya, glo, ghi)
+        fn = getattr(self.lib, f"gbdpcg_admm_grad_bounds_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(yf), _p(self._rho(rho, batch, yf)), _p(ya), _p(glo), _p(ghi), self._stream(stream)),
+                    "admm_grad_bounds")
+        return glo, ghi
 
 
     # ---- mixed-precision refinement: fp64 problem data and point, fp32 solves on a kept fp32 factorisation (include/gbdpcg.h)

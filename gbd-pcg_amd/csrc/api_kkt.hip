@@ -275,6 +275,48 @@ gbdpcg_status admm_step_impl(gbdpcg_handle_t h, const KktOperands<T> &k, const A
                                a.soft);
 }
 
+// ---- the backward pass of the hard box QP (admm_adjoint.hip): the box family with the forward y (yf) where lo, hi stand
+// The adjoint update, one launch.  init: gbdpcg_admm_adjoint_init_* -- d_az and d_res are not arguments.  Elementwise: no shape is
+// refused.
+template <typename T>
+gbdpcg_status admm_adjoint_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_gz,
+                                       const T *d_yf, const T *d_rho, const T *d_az, T *d_wa, T *d_ya, T *d_gta, T *d_res, void *stream,
+                                       bool init)
+{
+    if (!h || !d_gz || !d_yf || !d_rho || !d_wa || !d_ya || !d_gta || (!init && (!d_az || !d_res)) || nx == 0 || nu == 0 || N == 0 ||
+        batch == 0)
+        return GBDPCG_ERR_INVALID;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_admm_adjoint_update<T>(nx, nu, N, batch, d_gz, d_yf, d_rho, d_az, d_wa, d_ya, d_gta, d_res, (hipStream_t)stream, init));
+    return GBDPCG_OK;
+}
+
+// The gradients in the bounds from the adjoint's y, one launch, elementwise.
+template <typename T>
+gbdpcg_status admm_grad_bounds_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_yf, const T *d_rho,
+                                    const T *d_ya, T *d_glo, T *d_ghi, void *stream)
+{
+    if (!h || !d_yf || !d_rho || !d_ya || !d_glo || !d_ghi || nx == 0 || nu == 0 || N == 0 || batch == 0) return GBDPCG_ERR_INVALID;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_admm_grad_bounds<T>(nx, nu, N, batch, d_yf, d_rho, d_ya, d_glo, d_ghi, (hipStream_t)stream));
+    return GBDPCG_OK;
+}
+
+// One adjoint iteration: admm_step_impl with the adjoint update behind the solve.  k.g is gz, k.c is nglam, k.z is az; a.lo is yf
+// (a.hi too: the refusal of the box step is the refusal here), a.w, a.y, a.gt, a.res the adjoint's splitting state.
+template <typename T>
+gbdpcg_status admm_adjoint_step_impl(gbdpcg_handle_t h, const KktOperands<T> &k, const AdmmOperands<T> &a, const PcgArgs<T> &p,
+                                     hipStream_t stream)
+{
+    gbdpcg_status st = admm_step_refusal<T>(h, k, a, p);
+    if (st != GBDPCG_OK) return st;
+    KktOperands<T> shifted = k;
+    shifted.g = a.gt;
+    st = kkt_resolve_impl<T>(h, shifted, p, stream);
+    if (st != GBDPCG_OK) return st;
+    return admm_adjoint_update_impl<T>(h, p.n, k.nu, p.N, p.batch, k.g, a.lo, a.rho, k.z, a.w, a.y, a.gt, a.res, stream, false);
+}
+
 // ---- adaptive rho (admm_rebalance.hip): residual balancing in powers of two, and the iteration that refactors with the new rho
 // The rule of gbdpcg_admm*_rebalance_* and what it writes next to y: rho [batch] in place, expo [batch].
 template <typename T> struct RhoRule {
@@ -823,6 +865,50 @@ GBDPCG_ADMM_RESTEPS(admm_soft_restep)
 #undef ADMM_RESTEP_PARAMS
 #undef ADMM_RESTEP_SETUP
 #undef ADMM_RESTEP_REFUSE
+
+// ---- the backward pass of the hard box QP: the adjoint iteration of gbdpcg_admm_step_* with the forward y (d_yf) where d_lo, d_hi
+// stand, g := d_gz = dl/dz, c := d_nglam = -dl/dlambda, and the launch that turns the adjoint's y into dl/dlo, dl/dhi.  No _shared twin.
+#define ADJOINT_STEP_PARAMS(TYPE)                                                                                                   \
+    gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_gz, \
+        const TYPE *d_nglam, const TYPE *d_yf, const TYPE *d_rho, const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma,               \
+        TYPE *d_alambda, TYPE *d_r, TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,            \
+        TYPE *d_az, TYPE *d_wa, TYPE *d_ya, TYPE *d_gta, TYPE *d_res
+#define ADJOINT_STEP_SETUP(TYPE, SHARED)                                                                                            \
+    const AdmmOperands<TYPE> ad{d_yf, d_yf, d_rho, d_wa, d_ya, d_gta, d_res};                                                       \
+    const KktOperands<TYPE> k{nu, d_Ginv, d_C, d_gz, d_nglam, d_gamma, d_az, SHARED};                                               \
+    const PcgArgs<TYPE> a = pcg_args<TYPE>(nx, N, batch, d_S, d_Pinv, d_gamma, d_alambda, d_r, d_p, tol, max_iter, d_iters, d_max_iter_exit);\
+    auto body = [&](hipStream_t s) { return admm_adjoint_step_impl<TYPE>(h, k, ad, a, s); };
+#define ADJOINT_STEP_REFUSE(TYPE)                                                                                                   \
+    if (!out) return GBDPCG_ERR_INVALID;                                                                                            \
+    *out = nullptr;                                                                                                                 \
+    if (const gbdpcg_status st = admm_step_refusal<TYPE>(h, k, ad, a, false)) return st;
+#define GBDPCG_ADMM_ADJOINT(SUF, TYPE)                                                                                              \
+    gbdpcg_status gbdpcg_admm_adjoint_init_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,           \
+                                                 const TYPE *d_gz, const TYPE *d_yf, const TYPE *d_rho, TYPE *d_wa, TYPE *d_ya,     \
+                                                 TYPE *d_gta, void *stream)                                                         \
+    {                                                                                                                               \
+        return admm_adjoint_update_impl<TYPE>(h, nx, nu, N, batch, d_gz, d_yf, d_rho, nullptr, d_wa, d_ya, d_gta, nullptr, stream,  \
+                                              true);                                                                                \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_adjoint_update_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,         \
+                                                   const TYPE *d_gz, const TYPE *d_yf, const TYPE *d_rho, const TYPE *d_az,         \
+                                                   TYPE *d_wa, TYPE *d_ya, TYPE *d_gta, TYPE *d_res, void *stream)                  \
+    {                                                                                                                               \
+        return admm_adjoint_update_impl<TYPE>(h, nx, nu, N, batch, d_gz, d_yf, d_rho, d_az, d_wa, d_ya, d_gta, d_res, stream, false);\
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_grad_bounds_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,            \
+                                                const TYPE *d_yf, const TYPE *d_rho, const TYPE *d_ya, TYPE *d_glo, TYPE *d_ghi,    \
+                                                void *stream)                                                                       \
+    {                                                                                                                               \
+        return admm_grad_bounds_impl<TYPE>(h, nx, nu, N, batch, d_yf, d_rho, d_ya, d_glo, d_ghi, stream);                           \
+    }
+GBDPCG_ADMM_ADJOINT(f32, float)
+GBDPCG_ADMM_ADJOINT(f64, double)
+GBDPCG_PAIR_BOTH(admm_adjoint_step, false, ADJOINT_STEP_PARAMS, ADJOINT_STEP_SETUP, ADJOINT_STEP_REFUSE)
+#undef GBDPCG_ADMM_ADJOINT
+#undef ADJOINT_STEP_PARAMS
+#undef ADJOINT_STEP_SETUP
+#undef ADJOINT_STEP_REFUSE
 
 // ---- the KKT backward pass: the adjoint solve + gradient launch as one call / one graph (the gradient launch alone is with the
 // single launches).  shared: one problem's Ginv, C, S, Pinv, and gG, gC summed over the batch.

@@ -262,6 +262,18 @@ template <typename T>
 hipError_t launch_admm_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *g, const T *lo, const T *hi, const T *rho,
                               const T *z, T *w, T *y, T *gt, T *res, hipStream_t s, bool init, const T *kappa = nullptr);
 
+// ---- admm_adjoint.hip : the backward pass of the hard box QP, the launch shape of admm.hip.  yf is the forward y, read only: the
+// mask m = (yf != 0) stands where lo, hi stand in the update, which then projects onto {0} where m and onto the line elsewhere:
+//     w <- m ? clip(az + y, 0, 0) : az + y, y <- (az + y) - w, gt <- fma(-rho_b, w - y, gz), res as in the update
+// the bits of launch_admm_update on the explicit box lo = hi = +0 where m, -Inf / +Inf elsewhere.  init: as there (az, res may be null).
+// grad_bounds: glo = yf < 0 ? -(rho_b ya) : +0, ghi = yf > 0 ? -(rho_b ya) : +0, elementwise over the layout of g.
+template <typename T>
+hipError_t launch_admm_adjoint_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *gz, const T *yf, const T *rho,
+                                      const T *az, T *w, T *y, T *gt, T *res, hipStream_t s, bool init);
+template <typename T>
+hipError_t launch_admm_grad_bounds(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *yf, const T *rho, const T *ya, T *glo,
+                                   T *ghi, hipStream_t s);
+
 // ---- admm_rebalance.hip : adaptive rho by residual balancing in powers of two, one launch, one workgroup per problem.  From
 // r = res[2b], s = res[2b+1] and rho_b: rho_b <- rho_b 2^e with e in {+shift, -shift, 0} (the rule is in the head of the file and in
 // include/gbdpcg.h), y <- y 2^-e over `len` elements per problem, expo[b] = e.  box: len is that of g and gt <- fma(-rho_b, w - y, g)

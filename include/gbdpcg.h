@@ -1469,6 +1469,86 @@ gbdpcg_status gbdpcg_graph_create_kkt_backward_shared_f64(gbdpcg_handle_t h, uin
                                                           uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,
                                                           double *d_gG, double *d_gC, gbdpcg_graph_t *out);
 
+/* The backward pass of the hard box QP: gradients of a scalar through (G, C, g, c, lo, hi) -> (w, lambda) of the box section
+ * (gbdpcg_admm_step_* run to convergence), on the device.  At a solution with the active set A (the entries held at a bound) the
+ * adjoint pair (a_z, a_lambda) and a multiplier nu supported on A solve
+ *     G a_z + gz + C' a_lambda + nu = 0,      C a_z = -glam,      (a_z)_A = 0              gz = dl/dz, glam = dl/dlambda
+ * These are the optimality conditions of ANOTHER box QP with the same G and C: g := gz, c := -glam (the convention of
+ * gbdpcg_kkt_backward_*: d_nglam holds MINUS dl/dlambda), and the degenerate box lo = hi = 0 on A, (-Inf, +Inf) elsewhere.  So the
+ * adjoint is the ADMM iteration of the box section on the S, Phi^-1, G^-1 of G + rho I the forward pass kept, one
+ * gbdpcg_kkt_resolve_* per adjoint iteration, and it is as converged as its loop is run.
+ * The mask.  The forward pass leaves A defined to the bit: behind any hard update d_y (here d_yf, read only) is exactly 0 where
+ * nothing was clipped, < 0 where w = lo and > 0 where w = hi.  Entry i is active iff yf_i != 0 -- no threshold, nothing to tune; a
+ * NaN yf_i counts as active.  An entry that sits on its bound with yf_i = 0 (weakly active: the bound holds without force) counts
+ * as FREE: the gradient is the one-sided derivative on the side where the bound stays inactive.  d_yf stands where d_lo, d_hi
+ * stand in the box family; no adjoint bound arrays exist.  Per element of problem b, with m = (yf != 0):
+ *     v   = fl(az + ya)
+ *     wa+ = m ? (v < 0 ? 0 : (v > 0 ? 0 : v)) : v                             a NaN v stays NaN, v = -0 stays -0
+ *     ya+ = fl(v - wa+)
+ *     gta+ = fma(-rho_b, fl(wa+ - ya+), gz)                                   one rounding
+ *     d_res[2b] = max_i |fl(az_i - wa+_i)|,   d_res[2b+1] = max_i |fl(rho_b fl(wa+_i - wa_i))|
+ * d_wa, d_ya, d_gta and d_res are THE BITS of gbdpcg_admm_update_* / gbdpcg_admm_init_* called with the explicit box lo = hi = +0
+ * where m and -Inf / +Inf elsewhere, signed zeros and NaN included.
+ *  - gbdpcg_admm_adjoint_init_*: wa <- m ? clip(wa, 0, 0) : wa, ya is left as it is, gta <- fma(-rho_b, fl(wa - ya), gz).  Start from
+ *    wa = ya = 0 (gta = gz), or warm from the adjoint state of the previous backward pass.
+ *  - gbdpcg_admm_adjoint_update_*: everything behind the adjoint solve that wrote d_az, one launch.
+ *  - gbdpcg_admm_adjoint_step_*: gbdpcg_kkt_resolve_* with g := d_gta, c := d_nglam (writing d_alambda, warm-started from it, and
+ *    d_az) followed by gbdpcg_admm_adjoint_update_* on the same stream; same results as the two calls, bit for bit.
+ *  - the graph constructor keeps the POINTER d_rho like the one of gbdpcg_admm_step_* and sets *out to NULL before its first refusal.
+ *  - gbdpcg_admm_grad_bounds_*: from the converged adjoint y (nu = rho ya), one multiplication and one negation per element,
+ *        glo_i = yf_i < 0 ? -fl(rho_b ya_i) : +0            ghi_i = yf_i > 0 ? -fl(rho_b ya_i) : +0
+ * The gradients: dl/dg = a_z, reported as d_wa (EXACTLY zero on A: dl/dg_i = 0 for a clamped entry); dl/dc = -a_lambda; dl/dG and
+ * dl/dC are gbdpcg_kkt_grad_* on (w, lambda, wa, alambda); dl/dlo = d_glo, dl/dhi = d_ghi; dl/drho = 0 (the solution does not depend
+ * on rho).
+ * NOT provided: _shared twins, the soft box, linear and cone rows, and the backward pass of a forward loop that has not
+ * converged (the mask is then whatever d_y holds and the result is the gradient of no particular function).
+ * Null handle or required pointer, nx, nu, N or batch == 0: GBDPCG_ERR_INVALID, nothing is written (d_r, d_p, d_max_iter_exit and
+ * d_Pinv may be NULL as in gbdpcg_kkt_resolve_*, d_C when N == 1).  init, update and grad_bounds are elementwise and refuse no
+ * shape; step inherits every refusal of gbdpcg_kkt_resolve_* and refuses before anything is written. */
+gbdpcg_status gbdpcg_admm_adjoint_init_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_gz,
+                                           const float *d_yf, const float *d_rho, float *d_wa, float *d_ya, float *d_gta,
+                                           void *stream);
+gbdpcg_status gbdpcg_admm_adjoint_init_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                           const double *d_gz, const double *d_yf, const double *d_rho, double *d_wa, double *d_ya,
+                                           double *d_gta, void *stream);
+gbdpcg_status gbdpcg_admm_adjoint_update_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                             const float *d_gz, const float *d_yf, const float *d_rho, const float *d_az,
+                                             float *d_wa, float *d_ya, float *d_gta, float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_adjoint_update_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                             const double *d_gz, const double *d_yf, const double *d_rho, const double *d_az,
+                                             double *d_wa, double *d_ya, double *d_gta, double *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_adjoint_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                           const float *d_Ginv, const float *d_C, const float *d_gz, const float *d_nglam,
+                                           const float *d_yf, const float *d_rho, const float *d_S, const float *d_Pinv,
+                                           float *d_gamma, float *d_alambda, float *d_r, float *d_p, float tol, uint32_t max_iter,
+                                           uint32_t *d_iters, uint8_t *d_max_iter_exit, float *d_az, float *d_wa, float *d_ya,
+                                           float *d_gta, float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_adjoint_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                           const double *d_Ginv, const double *d_C, const double *d_gz, const double *d_nglam,
+                                           const double *d_yf, const double *d_rho, const double *d_S, const double *d_Pinv,
+                                           double *d_gamma, double *d_alambda, double *d_r, double *d_p, double tol,
+                                           uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_az,
+                                           double *d_wa, double *d_ya, double *d_gta, double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_adjoint_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                        const float *d_Ginv, const float *d_C, const float *d_gz,
+                                                        const float *d_nglam, const float *d_yf, const float *d_rho,
+                                                        const float *d_S, const float *d_Pinv, float *d_gamma, float *d_alambda,
+                                                        float *d_r, float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                                        uint8_t *d_max_iter_exit, float *d_az, float *d_wa, float *d_ya,
+                                                        float *d_gta, float *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_adjoint_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                        const double *d_Ginv, const double *d_C, const double *d_gz,
+                                                        const double *d_nglam, const double *d_yf, const double *d_rho,
+                                                        const double *d_S, const double *d_Pinv, double *d_gamma,
+                                                        double *d_alambda, double *d_r, double *d_p, double tol, uint32_t max_iter,
+                                                        uint32_t *d_iters, uint8_t *d_max_iter_exit, double *d_az, double *d_wa,
+                                                        double *d_ya, double *d_gta, double *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_admm_grad_bounds_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_yf,
+                                          const float *d_rho, const float *d_ya, float *d_glo, float *d_ghi, void *stream);
+gbdpcg_status gbdpcg_admm_grad_bounds_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                          const double *d_yf, const double *d_rho, const double *d_ya, double *d_glo, double *d_ghi,
+                                          void *stream);
+
 /* Mixed-precision refinement of a KKT point: fp32 solves on a kept fp32 factorisation, the defect and the point in fp64.
  * For a caller who needs more digits in the step than fp32 carries (SQP close to convergence, an adjoint solve, ADMM on a
  * kept factorisation) without the price of the fp64 pipeline: factor once in fp32 (gbdpcg_demote_f32 of G and C, then
