@@ -10,6 +10,10 @@ selects that give problems with zero cotangents zero gradients.  There is no CPU
 box_qp_solve adds the hard box lo <= z <= hi: the forward pass is gbdpcg_kkt_step_reg_* followed by a fixed number of
 gbdpcg_admm_step_*, the backward pass the same ADMM iteration on the adjoint QP (gbdpcg_admm_adjoint_*: the forward y is the mask of
 the active set), gbdpcg_admm_grad_bounds_* and gbdpcg_kkt_grad_*; (G, C, g, c, lo, hi) -> (w, lambda).
+
+lin_qp_solve adds the stage-wise linear rows lo <= E z <= hi: the forward pass is gbdpcg_admm_lin_form_* into a private Gt,
+gbdpcg_kkt_step_* on it and a fixed number of gbdpcg_admm_lin_step_*, the backward pass the same iteration on the adjoint QP
+(gbdpcg_admm_lin_adjoint_*), gbdpcg_admm_lin_grad_* and gbdpcg_kkt_grad_*; (G, C, g, c, E, lo, hi) -> (z, lambda).
 """
 from __future__ import annotations
 
@@ -182,6 +186,109 @@ def box_qp_solve(solver, nx, nu, N, G, C, g, c, lo, hi, rho, iters, adj_iters, t
     if int(iters) < 1 or int(adj_iters) < 1:
         raise ValueError("box_qp_solve: iters and adj_iters are at least 1")
     return _BoxQpSolve.apply(G, C, g, c, lo, hi, rho, solver, nx, nu, N, batch, int(iters), int(adj_iters), tol, max_iter)
+
+
+class _LinQpSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, G, C, g, c, E, lo, hi, rho, solver, nx, nu, mx, mu, N, batch, iters, adj_iters, tol, max_iter):
+        sz = _sizes(nx, nu, N)
+        nw = (mx + mu) * N - mu
+        kw = dict(dtype=g.dtype, device=g.device)
+        S = torch.empty(batch * 3 * nx * nx * N, **kw)
+        Pinv, Ginv = torch.empty_like(S), torch.empty(batch * sz["G"], **kw)
+        gamma = torch.empty(batch * sz["c"], **kw)
+        lam, z = torch.zeros(batch * sz["c"], **kw), torch.empty(batch * sz["g"], **kw)
+        w, y = torch.zeros(batch * nw, **kw), torch.zeros(batch * nw, **kw)
+        res = torch.zeros(batch, 2, **kw)
+        ctx.shapes = tuple(t.shape for t in (G, C, g, c, E, lo, hi))
+        G, C, g, c, E, lo, hi, rho = (t.detach().reshape(-1) for t in (G, C, g, c, E, lo, hi, rho))
+        Cp = C if N > 1 else None
+        Gt = solver.admm_lin_form(nx, nu, mx, mu, N, batch, G, E, rho)
+        solver.kkt_step(nx, nu, N, batch, Gt, Cp, g, c, S, gamma, Ginv, Pinv, lam, z, tol=tol, max_iter=max_iter)
+        gt = solver.admm_lin_init(nx, nu, mx, mu, N, batch, g, E, lo, hi, rho, w, y)
+        for _ in range(iters):
+            solver.admm_lin_step(nx, nu, mx, mu, N, batch, Ginv, Cp, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=res,
+                                 tol=tol, max_iter=max_iter)
+        ctx.save_for_backward(Ginv, S, Pinv, C, E, z, lam, y, rho)
+        ctx.args = (solver, nx, nu, mx, mu, N, batch, adj_iters, tol, max_iter)
+        ctx.mark_non_differentiable(res)
+        return z, lam, res
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gzz, glam, _gres):
+        Ginv, S, Pinv, C, E, z, lam, yf, rho = ctx.saved_tensors
+        solver, nx, nu, mx, mu, N, batch, adj_iters, tol, max_iter = ctx.args
+        sz = _sizes(nx, nu, N)
+        Cp = C if N > 1 else None
+        gz = torch.zeros_like(z) if gzz is None else gzz.contiguous().view(-1)
+        nglam = torch.zeros_like(lam) if glam is None else -glam.contiguous().view(-1)
+        gamma, alam, az = torch.empty_like(lam), torch.zeros_like(lam), torch.empty_like(z)
+        wa, ya = torch.zeros_like(yf), torch.zeros_like(yf)
+        res = torch.empty(batch, 2, dtype=z.dtype, device=z.device)
+        need_G, need_C = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and N > 1
+        # (a problem with exactly zero cotangents: as in _KktSolve.backward -- its adjoint solves return NaN, its gradients are
+        # exactly zero; the mask and the selects run in stream order)
+        live = ((gz.view(batch, -1) != 0).any(1) | (nglam.view(batch, -1) != 0).any(1)).view(batch, 1)
+
+        def keep(t):
+            return None if t is None else torch.where(live, t.view(batch, -1), t.new_zeros(())).view(-1)
+
+        gta = solver.admm_lin_adjoint_init(nx, nu, mx, mu, N, batch, gz, E, yf, rho, wa, ya)
+        for _ in range(adj_iters):
+            solver.admm_lin_adjoint_step(nx, nu, mx, mu, N, batch, Ginv, Cp, gz, nglam, E, yf, rho, S, Pinv, gamma, alam, az, wa, ya,
+                                         gta, res=res, tol=tol, max_iter=max_iter)
+        glo, ghi, gE = solver.admm_lin_grad(nx, nu, mx, mu, N, batch, z, az, yf, ya, rho)
+        gG = gC = None
+        if need_G or need_C:
+            gG = torch.empty(batch * sz["G"], dtype=z.dtype, device=z.device) if need_G else None
+            gC = torch.empty(batch * sz["C"], dtype=z.dtype, device=z.device) if need_C else None
+            solver.kkt_grad(nx, nu, N, batch, z, lam, az, alam, gG=gG, gC=gC, want="")
+        out = [keep(t) for t in (gG, gC, az, -alam, gE, glo, ghi)]
+        if ctx.needs_input_grad[1] and N == 1:
+            out[1] = torch.zeros(batch * sz["C"], dtype=z.dtype, device=z.device)
+        grads = [t if t is None else t.view(s) for t, s in zip(out, ctx.shapes)]
+        return (*grads, None) + (None,) * 11
+
+
+def lin_qp_solve(solver, nx, nu, mx, mu, N, G, C, g, c, E, lo, hi, rho, iters, adj_iters, tol=1e-6, max_iter=25):
+    """(z, lambda, res) of  min 1/2 z'Gz + g'z  subject to  Cz = c, lo <= Ez <= hi  for a batch of problems, differentiable in G, C, g,
+    c, E, lo and hi; res [batch, 2] (the ADMM residuals of the last iteration) is not differentiable, and rho gets no gradient (the
+    solution does not depend on it).
+
+    Flat contiguous device tensors of one dtype in the packed layouts of include/gbdpcg.h: E = [Ex_0 Eu_0 ... Ex_{N-1}] column-major
+    blocks (mx x nx, mu x nu), lo, hi in the layout of the rows [mx | mu | ... | mx] (-Inf / +Inf: no bound), rho [batch] > 0 the ADMM
+    penalty.  Forward: gbdpcg_admm_lin_form_* into a private Gt = G + rho E'E, gbdpcg_kkt_step_* on it, gbdpcg_admm_lin_init_* from
+    w = y = 0, then `iters` gbdpcg_admm_lin_step_*; z is the last solve's (E z is in the bounds to the residual res[:, 0]).  Backward:
+    gbdpcg_admm_lin_adjoint_init_* from zeros, `adj_iters` gbdpcg_admm_lin_adjoint_step_* on the kept factorisation,
+    gbdpcg_admm_lin_grad_*, gbdpcg_kkt_grad_* (the gradient in G, not in Gt).  Both counts are fixed: nothing waits for the device,
+    and the gradients are only as converged as the two loops -- read res to judge the forward one.
+
+    The active set is the sign pattern of the forward y: row r is active iff y_r != 0 (no threshold); a row that sits on its bound
+    with y_r = 0 (weakly active) counts as free.  A forward loop that has not converged leaves whatever mask y holds.  tol, max_iter:
+    the PCG settings of every solve.  A problem whose rows of dl/dz and dl/dlambda are exactly zero gets exactly zero gradients."""
+    if not isinstance(solver, binding.Solver):
+        raise TypeError("lin_qp_solve: solver is a binding.Solver")
+    sz = _sizes(nx, nu, N)
+    nw, ne = (mx + mu) * N - mu, (mx * nx + mu * nu) * N - mu * nu
+    for name, t in (("G", G), ("C", C), ("g", g), ("c", c), ("E", E), ("lo", lo), ("hi", hi), ("rho", rho)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == g.dtype):
+            raise ValueError(f"lin_qp_solve: {name} must be a contiguous device tensor of g's dtype")
+    if g.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"lin_qp_solve: unsupported dtype {g.dtype}")
+    if nw <= 0:
+        raise ValueError("lin_qp_solve: no rows at all")
+    if g.numel() == 0 or g.numel() % sz["g"]:
+        raise ValueError("lin_qp_solve: g is not a whole number of problems")
+    batch = g.numel() // sz["g"]
+    want = {"G": batch * sz["G"], "C": batch * sz["C"], "c": batch * sz["c"], "E": batch * ne, "lo": batch * nw, "hi": batch * nw,
+            "rho": batch}
+    for name, t in (("G", G), ("C", C), ("c", c), ("E", E), ("lo", lo), ("hi", hi), ("rho", rho)):
+        if t.numel() != want[name]:
+            raise ValueError(f"lin_qp_solve: {name} has {t.numel()} elements, the layout takes {want[name]}")
+    if int(iters) < 1 or int(adj_iters) < 1:
+        raise ValueError("lin_qp_solve: iters and adj_iters are at least 1")
+    return _LinQpSolve.apply(G, C, g, c, E, lo, hi, rho, solver, nx, nu, mx, mu, N, batch, int(iters), int(adj_iters), tol, max_iter)
 
 
 def kkt_solve(solver, nx, nu, N, G, C, g, c, rho=None, shared=False, tol=1e-6, max_iter=25):

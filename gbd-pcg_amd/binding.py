@@ -76,6 +76,9 @@ SYMBOLS = [
     # the backward pass of the hard box QP: the forward y where lo, hi stand
     *[f"gbdpcg_{name}_{suf}" for name in ("admm_adjoint_init", "admm_adjoint_update", "admm_adjoint_step",
                                           "graph_create_admm_adjoint_step", "admm_grad_bounds") for suf in ("f32", "f64")],
+    # the backward pass of the hard linear-row QP: the admm_lin family with yf where lo, hi stand, and the gradients in the rows
+    *[f"gbdpcg_{name}_{suf}" for name in ("admm_lin_adjoint_init", "admm_lin_adjoint_update", "admm_lin_adjoint_step",
+                                          "graph_create_admm_lin_adjoint_step", "admm_lin_grad") for suf in ("f32", "f64")],
     "gbdpcg_demote_f32", "gbdpcg_kkt_defect_mixed", "gbdpcg_kkt_refine_apply", "gbdpcg_kkt_refine_step",
     "gbdpcg_graph_create_kkt_refine_step",
     "gbdpcg_kkt_defect_mixed_reg", "gbdpcg_kkt_defect_mixed_shared", "gbdpcg_kkt_refine_step_reg", "gbdpcg_kkt_refine_step_shared",
@@ -159,6 +162,18 @@ def _resolve_argtypes(lib):
         getattr(lib, f"gbdpcg_admm_adjoint_step_{suf}").argtypes = adj + [vp]
         getattr(lib, f"gbdpcg_graph_create_admm_adjoint_step_{suf}").argtypes = adj + [ctypes.POINTER(vp)]
         getattr(lib, f"gbdpcg_admm_grad_bounds_{suf}").argtypes = sizes + [vp, vp, vp] + [vp, vp] + [vp]
+        # the backward pass of the hard linear-row QP: the admm_lin family with yf where lo, hi stand
+        #   init    h, nx, nu, mx, mu, N, batch | gz | E, yf, rho | wa, ya, gta | stream
+        #   update  ...                         | gz | E, yf, rho | az, wa, ya, gta, res | stream
+        #   step    ...   | Ginv, C, gz, nglam | E, yf, rho | the solve's arguments (lambda := alambda, z := az) | wa, ya, gta, res |
+        #   grad    ...                         | z, az, yf, ya, rho | glo, ghi, gE | stream
+        lsizes = [vp, u32, u32, u32, u32, u32, u32]
+        getattr(lib, f"gbdpcg_admm_lin_adjoint_init_{suf}").argtypes = lsizes + [vp] + [vp, vp, vp] + [vp, vp, vp] + [vp]
+        getattr(lib, f"gbdpcg_admm_lin_adjoint_update_{suf}").argtypes = lsizes + [vp] + [vp, vp, vp] + [vp, vp, vp, vp, vp] + [vp]
+        ladj = lsizes + [vp, vp, vp, vp] + [vp, vp, vp] + solve + [vp, vp, vp, vp]
+        getattr(lib, f"gbdpcg_admm_lin_adjoint_step_{suf}").argtypes = ladj + [vp]
+        getattr(lib, f"gbdpcg_graph_create_admm_lin_adjoint_step_{suf}").argtypes = ladj + [ctypes.POINTER(vp)]
+        getattr(lib, f"gbdpcg_admm_lin_grad_{suf}").argtypes = lsizes + [vp, vp, vp, vp, vp] + [vp, vp, vp] + [vp]
 
     # mixed-precision refinement (no suffix: fp64 data and point, fp32 solve)
     head = [vp, u32, u32, u32, u32, vp, vp, vp, vp]                # h, nx, nu, N, batch, G, C, g, c (fp64)
@@ -1330,6 +1345,93 @@ class Solver:
         self._check(fn(self.h, nx, nu, N, batch, _p(yf), _p(self._rho(rho, batch, yf)), _p(ya), _p(glo), _p(ghi), self._stream(stream)),
                     "admm_grad_bounds")
         return glo, ghi
+
+    # ---- the backward pass of the hard linear-row QP (include/gbdpcg.h): the admm_lin family with yf, the forward y, where lo, hi
+    # stand; gz = dl/dz in the place of g, nglam = -dl/dlambda in the place of c; wa, ya (layout of the rows), gta, az (layout of g)
+    def admm_lin_adjoint_init(self, nx, nu, mx, mu, N, batch, gz, E, yf, rho, wa, ya, gta=None, stream=None):
+        """gbdpcg_admm_lin_adjoint_init_*: wa <- 0 where yf != 0, gta <- gz - rho E'(wa - ya); ya is left alone.  Returns gta."""
+        import torch
+        suf, _ = _suffix(gz)
+        if gta is None:
+            gta = torch.empty_like(gz)
+        self._lin(gz, batch, nx, nu, mx, mu, N, E, (yf, wa, ya), (gz, gta))
+        fn = getattr(self.lib, f"gbdpcg_admm_lin_adjoint_init_{suf}")
+        self._check(fn(self.h, nx, nu, mx, mu, N, batch, _p(gz), _p(E), _p(yf), _p(self._rho(rho, batch, gz)), _p(wa), _p(ya), _p(gta),
+                       self._stream(stream)), "admm_lin_adjoint_init")
+        return gta
+
+    def admm_lin_adjoint_update(self, nx, nu, mx, mu, N, batch, gz, E, yf, rho, az, wa, ya, gta, res=None, stream=None):
+        """gbdpcg_admm_lin_adjoint_update_*: the update behind an adjoint solve that wrote az -- wa, ya, gta in place; returns the
+        [batch, 2] tensor of (||E az - wa||_inf, rho ||E'(wa - wa_old)||_inf) per problem."""
+        import torch
+        suf, _ = _suffix(gz)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=gz.dtype, device=gz.device)
+        assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == gz.dtype
+        self._lin(gz, batch, nx, nu, mx, mu, N, E, (yf, wa, ya), (gz, az, gta))
+        fn = getattr(self.lib, f"gbdpcg_admm_lin_adjoint_update_{suf}")
+        self._check(fn(self.h, nx, nu, mx, mu, N, batch, _p(gz), _p(E), _p(yf), _p(self._rho(rho, batch, gz)), _p(az), _p(wa), _p(ya),
+                       _p(gta), _p(res), self._stream(stream)), "admm_lin_adjoint_update")
+        return res.view(batch, 2)
+
+    def _lin_adjoint_step_args(self, nx, nu, mx, mu, N, batch, Ginv, C, gz, nglam, E, yf, rho, S, Pinv, gamma, alam, r, p, tol, max_iter,
+                               iters, mie, az, wa, ya, gta, res):
+        suf, _ = _suffix(gz)
+        assert res.is_cuda and res.is_contiguous() and res.numel() == 2 * batch and res.dtype == gz.dtype
+        self._lin(gz, batch, nx, nu, mx, mu, N, E, (yf, wa, ya), (gz, az, gta))
+        args = (self.h, nx, nu, mx, mu, N, batch, _p(Ginv), _p(C), _p(gz), _p(nglam), _p(E), _p(yf), _p(self._rho(rho, batch, gz)),
+                _p(S), _p(Pinv), _p(gamma), _p(alam), _p(r), _p(p), tol, max_iter, _p(iters), _p(mie), _p(az), _p(wa), _p(ya), _p(gta),
+                _p(res))
+        return suf, args, (Ginv, C, gz, nglam, E, yf, rho, S, Pinv, gamma, alam, r, p, iters, mie, az, wa, ya, gta, res)
+
+    def admm_lin_adjoint_step(self, nx, nu, mx, mu, N, batch, Ginv, C, gz, nglam, E, yf, rho, S, Pinv, gamma, alam, az, wa, ya, gta,
+                              res=None, r=None, p=None, tol=1e-6, max_iter=25, iters=None, max_iter_exit=None, stream=None):
+        """gbdpcg_admm_lin_adjoint_step_*: kkt_resolve with g := gta, c := nglam (warm start from alam, writing alam and az), then
+        admm_lin_adjoint_update, one call.  Returns (iters, flags, res [batch, 2])."""
+        import torch
+        if iters is None:
+            iters = torch.zeros(batch, dtype=torch.int32, device=gz.device)
+        if max_iter_exit is None:
+            max_iter_exit = torch.zeros(batch, dtype=torch.uint8, device=gz.device)
+        if res is None:
+            res = torch.empty(batch, 2, dtype=gz.dtype, device=gz.device)
+        suf, args, _ = self._lin_adjoint_step_args(nx, nu, mx, mu, N, batch, Ginv, C, gz, nglam, E, yf, rho, S, Pinv, gamma, alam, r, p,
+                                                   tol, max_iter, iters, max_iter_exit, az, wa, ya, gta, res)
+        self._check(getattr(self.lib, f"gbdpcg_admm_lin_adjoint_step_{suf}")(*args, self._stream(stream)), "admm_lin_adjoint_step")
+        return iters, max_iter_exit, res.view(batch, 2)
+
+    def graph_admm_lin_adjoint_step(self, nx, nu, mx, mu, N, batch, Ginv, C, gz, nglam, E, yf, rho, S, Pinv, gamma, alam, r, p, tol,
+                                    max_iter, iters, max_iter_exit, az, wa, ya, gta, res):
+        """Capture one adjoint iteration of the rows into a hipGraph (gbdpcg_graph_create_admm_lin_adjoint_step_*): replay it once
+        per iteration; the graph keeps rho's pointer."""
+        suf, args, keep = self._lin_adjoint_step_args(nx, nu, mx, mu, N, batch, Ginv, C, gz, nglam, E, yf, rho, S, Pinv, gamma, alam, r,
+                                                      p, tol, max_iter, iters, max_iter_exit, az, wa, ya, gta, res)
+        gr = ctypes.c_void_p()
+        self._check(getattr(self.lib, f"gbdpcg_graph_create_admm_lin_adjoint_step_{suf}")(*args, ctypes.byref(gr)),
+                    "graph_create_admm_lin_adjoint_step")
+        return Graph(self, gr, keep=keep)
+
+    def admm_lin_grad(self, nx, nu, mx, mu, N, batch, z, az, yf, ya, rho, glo=None, ghi=None, gE=None, want="lhE", stream=None):
+        """gbdpcg_admm_lin_grad_*: (dl/dlo, dl/dhi) in the layout of the rows and dl/dE in the layout of E from the forward z, yf
+        and the adjoint's az, ya.  want: which of "l", "h", "E" to allocate when the tensor is not passed (the others stay NULL)."""
+        import torch
+        suf, _ = _suffix(z)
+        _, nw, ne, _ = self._lin_sizes(nx, nu, mx, mu, N)
+        kw = dict(dtype=z.dtype, device=z.device)
+        if glo is None and "l" in want:
+            glo = torch.empty(batch * nw, **kw)
+        if ghi is None and "h" in want:
+            ghi = torch.empty(batch * nw, **kw)
+        if gE is None and "E" in want:
+            gE = torch.empty(batch * ne, **kw)
+        nz = (nx + nu) * N - nu
+        for t, cnt in ((z, nz), (az, nz), (yf, nw), (ya, nw), (glo, nw), (ghi, nw), (gE, ne)):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() == batch * cnt and t.dtype == z.dtype)
+        assert None not in (az, yf, ya) and (glo is not None or ghi is not None or gE is not None)
+        fn = getattr(self.lib, f"gbdpcg_admm_lin_grad_{suf}")
+        self._check(fn(self.h, nx, nu, mx, mu, N, batch, _p(z), _p(az), _p(yf), _p(ya), _p(self._rho(rho, batch, z)), _p(glo), _p(ghi),
+                       _p(gE), self._stream(stream)), "admm_lin_grad")
+        return glo, ghi, gE
 
 
     # ---- mixed-precision refinement: fp64 problem data and point, fp32 solves on a kept fp32 factorisation (include/gbdpcg.h)

@@ -45,9 +45,6 @@ template <> struct AdjVec<double> {
     typedef double type __attribute__((ext_vector_type(2)));
 };
 
-// The projection onto the degenerate box of an element: {0} where the forward multiplier is not zero, the whole line elsewhere.
-template <typename T> __device__ __forceinline__ T pin(T v, T yf) { return yf != T(0) ? clip(v, T(0), T(0)) : v; }
-
 // One element.  w, y: in / out (INIT leaves y alone); mp, md: the running maxima of the two norms (not INIT).
 template <typename T, bool INIT, typename U>
 __device__ __forceinline__ T adjoint_element(T az, T &w, T &y, T yf, T gz, T rho, U &mp, U &md)

@@ -1,6 +1,7 @@
 // admm_rows.hip -- ADMM on a kept KKT factorisation with stage-wise rows on E z (gbdpcg_admm_lin_form_*; gbdpcg_admm_lin_init_*,
-// gbdpcg_admm_lin_update_*, gbdpcg_admm_soc_init_*, gbdpcg_admm_soc_update_*, the last launch of gbdpcg_admm_lin_step_* and
-// gbdpcg_admm_soc_step_*).  Problem b minimises 1/2 z'Gz + g'z subject to Cz = c and, row by row, lo <= (E z)_r <= hi (a LINEAR
+// gbdpcg_admm_lin_update_*, gbdpcg_admm_lin_adjoint_init_*, gbdpcg_admm_lin_adjoint_update_*, gbdpcg_admm_soc_init_*,
+// gbdpcg_admm_soc_update_*, the last launch of gbdpcg_admm_lin_step_*, gbdpcg_admm_lin_adjoint_step_* and gbdpcg_admm_soc_step_*).
+// Problem b minimises 1/2 z'Gz + g'z subject to Cz = c and, row by row, lo <= (E z)_r <= hi (a LINEAR
 // row) or (E z + f)_cone in K_q = {(s_0, s_1 .. s_{q-1}) : ||(s_1 .. s_{q-1})||_2 <= s_0} (the rows of a SECOND-ORDER CONE).  E is
 // block-diagonal with the blocks of G: Ex_k (mx x nx) on x_k, Eu_k (mu x nu) on u_k, column-major, packed [Ex_0 Eu_0 Ex_1 ...
 // Ex_{N-1}]; the rows, and with them lo, hi, w, y, are packed [mx | mu | mx | ... | mx].  The matrices of the solve belong to
@@ -27,6 +28,12 @@
 //   UPDATE  p = clip(s);  e = s - p;  theta = kappa / rho;  w+ = e > theta ? s - theta : (e < -theta ? s + theta : p)
 //           y+ = e > theta ? theta : (e < -theta ? -theta : e)             kappa = +Inf: the third branch, the hard bits
 //   INIT    w <- (kappa == +Inf) ? clip(w) : w
+// ADJOINT (the gbdpcg_admm_lin_adjoint_* calls, the backward pass of the hard linear rows; never with CONES or SOFT) projects onto
+// the degenerate rows a forward y (yf, read only) stands for: {0} where yf_r != 0 (a NaN included), the whole line elsewhere.  Only the
+// line of w+ changes (pin in ieee_once.hpp), in UPDATE and INIT alike:
+//   w+ = yf != 0 ? clip(s, +0, +0) : s          the bits of the hard lines with lo = hi = +0 where yf != 0, -Inf / +Inf elsewhere
+// yf is read where lo is read and there is no hi: admm_rows_adjoint_kernel takes one pointer less and makes 3 row reads, not 4.  The
+// body is shared (rows_update, forced inline into both __global__ entries); ADJ is its compile-time switch.
 // kappa has the layout of lo and is read in phase A by the lane that owns the row, one more scalar global read per row; no LDS slot
 // is added and phase B is untouched.  The hard instantiations take no kappa argument (an empty parameter pack).
 //
@@ -110,13 +117,15 @@ __global__ __launch_bounds__(256) void admm_lin_form_kernel(uint32_t nx, uint32_
     Gt[at] = fma_once(rho[prob], p, G[at]);
 }
 
-template <typename T, bool INIT, bool CONES, bool SOFT, typename... K>
-__global__ __launch_bounds__(256) void admm_rows_update_kernel(RowsShape<CONES> s, const T *__restrict__ g, const T *__restrict__ E,
-                                                               const T *__restrict__ lo, const T *__restrict__ hi,
-                                                               const T *__restrict__ rho, const T *__restrict__ z, T *__restrict__ w,
-                                                               T *__restrict__ y, T *__restrict__ gt, T *__restrict__ res, K... kappa_arg)
+// The body of the two kernels below.  ADJ (the adjoint instantiations, never with CONES or SOFT): lo is yf, hi is not looked at.
+template <typename T, bool INIT, bool CONES, bool SOFT, bool ADJ, typename... K>
+__device__ __forceinline__ void rows_update(const RowsShape<CONES> &s, const T *__restrict__ g, const T *__restrict__ E,
+                                            const T *__restrict__ lo, const T *__restrict__ hi, const T *__restrict__ rho,
+                                            const T *__restrict__ z, T *__restrict__ w, T *__restrict__ y, T *__restrict__ gt,
+                                            T *__restrict__ res, K... kappa_arg)
 {
     static_assert(!(SOFT && CONES), "cone rows stay hard");
+    static_assert(!(ADJ && (SOFT || CONES)), "the adjoint rows are hard linear rows");
     static_assert(sizeof...(K) == (SOFT ? 1 : 0), "kappa is an argument of the soft instantiations alone");
     using U = decltype(abs_bits(T(0)));
     extern __shared__ __attribute__((aligned(16))) unsigned char rows_lds[];
@@ -127,7 +136,8 @@ __global__ __launch_bounds__(256) void admm_rows_update_kernel(RowsShape<CONES> 
     T *sz = sE + kch * se, *st = sz + kch * sv, *sd = st + kch * sw;
     const uint32_t prob = blockIdx.x, tid = threadIdx.x, threads = blockDim.x;
     const uint64_t nz = (uint64_t)sv * N - nu, nw = (uint64_t)sw * N - mu, ne = (uint64_t)se * N - mu * nu;
-    g += prob * nz, gt += prob * nz, lo += prob * nw, hi += prob * nw, w += prob * nw, y += prob * nw;
+    g += prob * nz, gt += prob * nz, lo += prob * nw, w += prob * nw, y += prob * nw;
+    if constexpr (!ADJ) hi += prob * nw;
     if constexpr (!INIT) z += prob * nz;
     [[maybe_unused]] const T *__restrict__ kappa = nullptr;
     if constexpr (SOFT) kappa = kappa_of<T>(kappa_arg...) + prob * nw;
@@ -150,12 +160,15 @@ __global__ __launch_bounds__(256) void admm_rows_update_kernel(RowsShape<CONES> 
         if constexpr (!CONES) {
             // phase A: row q of the chunk
             for (uint32_t q = tid; q < wc; q += threads) {
-                const T wo = w[w0 + q], yo = y[w0 + q], l = lo[w0 + q], h = hi[w0 + q];
-                T wn, t, kap = T(0);
+                const T wo = w[w0 + q], yo = y[w0 + q], l = lo[w0 + q];
+                T wn, t, h = T(0), kap = T(0);
+                if constexpr (!ADJ) h = hi[w0 + q];
                 if constexpr (SOFT) kap = kappa[w0 + q];
                 if constexpr (INIT) {
                     if constexpr (SOFT)
                         wn = soft_init(wo, l, h, kap);
+                    else if constexpr (ADJ)
+                        wn = pin(wo, l);
                     else
                         wn = clip(wo, l, h);
                     t = wn - yo;
@@ -171,7 +184,10 @@ __global__ __launch_bounds__(256) void admm_rows_update_kernel(RowsShape<CONES> 
                     if constexpr (SOFT) {
                         soft_clip(sum, l, h, kap, r, wn, yn);
                     } else {
-                        wn = clip(sum, l, h);
+                        if constexpr (ADJ)
+                            wn = pin(sum, l);
+                        else
+                            wn = clip(sum, l, h);
                         yn = sum - wn;
                     }
                     t = wn - yn;
@@ -272,6 +288,25 @@ __global__ __launch_bounds__(256) void admm_rows_update_kernel(RowsShape<CONES> 
         store_norms(mp, md, tid >> 6, tid & 63u, threads >> 6, [&](uint32_t wv) { return slots + 2 * wv; }, res + 2 * (uint64_t)prob);
 }
 
+template <typename T, bool INIT, bool CONES, bool SOFT, typename... K>
+__global__ __launch_bounds__(256) void admm_rows_update_kernel(RowsShape<CONES> s, const T *__restrict__ g, const T *__restrict__ E,
+                                                               const T *__restrict__ lo, const T *__restrict__ hi,
+                                                               const T *__restrict__ rho, const T *__restrict__ z, T *__restrict__ w,
+                                                               T *__restrict__ y, T *__restrict__ gt, T *__restrict__ res, K... kappa_arg)
+{
+    rows_update<T, INIT, CONES, SOFT, false>(s, g, E, lo, hi, rho, z, w, y, gt, res, kappa_arg...);
+}
+
+// The adjoint of the hard linear rows: yf, the forward y, where lo stands, and no hi.
+template <typename T, bool INIT>
+__global__ __launch_bounds__(256) void admm_rows_adjoint_kernel(RowsShape<false> s, const T *__restrict__ gz, const T *__restrict__ E,
+                                                                const T *__restrict__ yf, const T *__restrict__ rho,
+                                                                const T *__restrict__ az, T *__restrict__ w, T *__restrict__ y,
+                                                                T *__restrict__ gt, T *__restrict__ res)
+{
+    rows_update<T, INIT, false, false, true>(s, gz, E, yf, static_cast<const T *>(nullptr), rho, az, w, y, gt, res);
+}
+
 template <typename T> bool admm_rows_shape_ok(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu)
 {
     return mx <= 64 && mu <= 64 && rows_per_knot(nx, nu, mx, mu) * sizeof(T) <= kRowsLdsBytes;
@@ -307,11 +342,11 @@ hipError_t launch_admm_lin_form(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t 
 template <typename T>
 hipError_t launch_admm_rows_update(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *g,
                                    const T *E, const T *lo, const T *hi, const T *rho, const T *z, T *w, T *y, T *gt, T *res,
-                                   hipStream_t s, bool init, bool shared, const RowClasses *cones, const T *kappa)
+                                   hipStream_t s, bool init, bool shared, const RowClasses *cones, const T *kappa, bool adjoint)
 {
     if (batch > 0x7fffffffu || !admm_rows_shape_ok<T>(nx, nu, mx, mu) || (cones && !admm_rows_classes_ok(mx, mu, *cones)) ||
-        (cones && kappa))
-        return hipErrorInvalidValue;   // one workgroup per problem; cone rows stay hard
+        (cones && kappa) || (adjoint && (cones || kappa || shared)))
+        return hipErrorInvalidValue;   // one workgroup per problem; cone rows stay hard; the adjoint rows are hard, linear, per problem
     const RowsDims dims{nx, nu, mx, mu};
     RowsWalk walk{N, admm_rows_knot_chunk(nx, nu, mx, mu), shared ? 1u : 0u};
     if (walk.kch > N) walk.kch = N;
@@ -321,7 +356,13 @@ hipError_t launch_admm_rows_update(uint32_t nx, uint32_t nu, uint32_t mx, uint32
     auto launch = [&](auto kernel, auto sh, auto... kap) {
         hipLaunchKernelGGL(kernel, dim3(batch), dim3(threads), lds, s, sh, g, E, lo, hi, rho, z, w, y, gt, res, kap...);
     };
-    if (cones) {   // (q is ignored where there is no cone row)
+    if (adjoint) {   // lo is yf: the mask stands where the bounds stand, hi is not an argument
+        const RowsShape<false> sh{dims, {}, walk};
+        if (init)
+            hipLaunchKernelGGL((admm_rows_adjoint_kernel<T, true>), dim3(batch), dim3(threads), lds, s, sh, g, E, lo, rho, z, w, y, gt, res);
+        else
+            hipLaunchKernelGGL((admm_rows_adjoint_kernel<T, false>), dim3(batch), dim3(threads), lds, s, sh, g, E, lo, rho, z, w, y, gt, res);
+    } else if (cones) {   // (q is ignored where there is no cone row)
         const RowClasses c{cones->lx, cones->lx < mx ? cones->qx : 1u, cones->lu, cones->lu < mu ? cones->qu : 1u};
         const RowsShape<true> sh{dims, c, walk};
         init ? launch(&admm_rows_update_kernel<T, true, true, false>, sh) : launch(&admm_rows_update_kernel<T, false, true, false>, sh);
@@ -345,10 +386,10 @@ template hipError_t launch_admm_lin_form<double>(uint32_t, uint32_t, uint32_t, u
 template hipError_t launch_admm_rows_update<float>(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const float *,
                                                    const float *, const float *, const float *, const float *, const float *, float *,
                                                    float *, float *, float *, hipStream_t, bool, bool, const RowClasses *,
-                                                   const float *);
+                                                   const float *, bool);
 template hipError_t launch_admm_rows_update<double>(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const double *,
                                                     const double *, const double *, const double *, const double *, const double *,
                                                     double *, double *, double *, double *, hipStream_t, bool, bool, const RowClasses *,
-                                                    const double *);
+                                                    const double *, bool);
 
 }  // namespace gbdpcg

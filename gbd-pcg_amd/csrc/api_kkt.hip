@@ -79,6 +79,7 @@ template <typename T> struct AdmmOperands {
     const RowClasses *cones = nullptr;
     const T *kappa = nullptr;
     bool soft = false;
+    bool adjoint = false;   // gbdpcg_admm_lin_adjoint_*: hard linear rows, lo (and hi) hold yf, the forward y -- the mask of the active rows
 };
 
 // The forward point and the outputs of gbdpcg_kkt_backward_*: z has the layout of g, lambda that of c, gG / gC those of G / C (one
@@ -229,13 +230,13 @@ gbdpcg_status admm_rows_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu,
                                     const AdmmOperands<T> &a, const T *d_z, void *stream, bool init, bool shared = false)
 {
     if (!h || !d_g || !a.E || !a.lo || !a.hi || !a.rho || !a.w || !a.y || !a.gt || (!init && (!d_z || !a.res)) || nx == 0 ||
-        nu == 0 || N == 0 || batch == 0 || (a.soft && (!a.kappa || a.cones)))
+        nu == 0 || N == 0 || batch == 0 || (a.soft && (!a.kappa || a.cones)) || (a.adjoint && (a.soft || a.cones || shared)))
         return GBDPCG_ERR_INVALID;
     const gbdpcg_status st = admm_rows_status<T>(nx, nu, a, N);
     if (st != GBDPCG_OK) return st;
     DEVICE_SCOPE(h);
     HIP_TRY(h, launch_admm_rows_update<T>(nx, nu, a.mx, a.mu, N, batch, d_g, a.E, a.lo, a.hi, a.rho, d_z, a.w, a.y, a.gt, a.res,
-                                          (hipStream_t)stream, init, shared, a.cones, a.soft ? a.kappa : nullptr));
+                                          (hipStream_t)stream, init, shared, a.cones, a.soft ? a.kappa : nullptr, a.adjoint));
     return GBDPCG_OK;
 }
 
@@ -299,6 +300,24 @@ gbdpcg_status admm_grad_bounds_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu,
     if (!h || !d_yf || !d_rho || !d_ya || !d_glo || !d_ghi || nx == 0 || nu == 0 || N == 0 || batch == 0) return GBDPCG_ERR_INVALID;
     DEVICE_SCOPE(h);
     HIP_TRY(h, launch_admm_grad_bounds<T>(nx, nu, N, batch, d_yf, d_rho, d_ya, d_glo, d_ghi, (hipStream_t)stream));
+    return GBDPCG_OK;
+}
+
+// The gradients in the rows of the hard linear-row QP (admm_lin_grad.hip), one launch: glo, ghi in the layout of the rows, gE in that
+// of E, each may be null, not all three.  The refusals of the rows family.
+template <typename T>
+gbdpcg_status admm_lin_grad_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch,
+                                 const T *d_z, const T *d_az, const T *d_yf, const T *d_ya, const T *d_rho, T *d_glo, T *d_ghi, T *d_gE,
+                                 void *stream)
+{
+    if (!h || !d_z || !d_az || !d_yf || !d_ya || !d_rho || (!d_glo && !d_ghi && !d_gE) || nx == 0 || nu == 0 || N == 0 || batch == 0)
+        return GBDPCG_ERR_INVALID;
+    AdmmOperands<T> a{};
+    a.mx = mx, a.mu = mu;
+    const gbdpcg_status st = admm_rows_status<T>(nx, nu, a, N);
+    if (st != GBDPCG_OK) return st;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_admm_lin_grad<T>(nx, nu, mx, mu, N, batch, d_z, d_az, d_yf, d_ya, d_rho, d_glo, d_ghi, d_gE, (hipStream_t)stream));
     return GBDPCG_OK;
 }
 
@@ -909,6 +928,54 @@ GBDPCG_PAIR_BOTH(admm_adjoint_step, false, ADJOINT_STEP_PARAMS, ADJOINT_STEP_SET
 #undef ADJOINT_STEP_PARAMS
 #undef ADJOINT_STEP_SETUP
 #undef ADJOINT_STEP_REFUSE
+
+// ---- the backward pass of the hard linear-row QP: the iteration of gbdpcg_admm_lin_step_* with the forward y (d_yf) where d_lo,
+// d_hi stand (the adjoint instantiations of the rows kernel), g := d_gz, c := d_nglam, on the kept matrices of G + rho E'E; and the
+// launch that turns (z, az, yf, ya) into dl/dlo, dl/dhi, dl/dE.  The step IS admm_step_impl on these operands.  No _shared twin.
+#define LIN_ADJOINT_SIZES gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch
+#define LIN_ADJOINT_OPERANDS d_yf, d_yf, d_rho, d_wa, d_ya, d_gta, d_res, true, d_E, mx, mu, nullptr, nullptr, false, true
+#define LIN_ADJOINT_STEP_PARAMS(TYPE)                                                                                               \
+    LIN_ADJOINT_SIZES, const TYPE *d_Ginv, const TYPE *d_C, const TYPE *d_gz, const TYPE *d_nglam, const TYPE *d_E, const TYPE *d_yf,\
+        const TYPE *d_rho, const TYPE *d_S, const TYPE *d_Pinv, TYPE *d_gamma, TYPE *d_alambda, TYPE *d_r, TYPE *d_p, TYPE tol,     \
+        uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit, TYPE *d_az, TYPE *d_wa, TYPE *d_ya, TYPE *d_gta, TYPE *d_res
+#define LIN_ADJOINT_STEP_SETUP(TYPE, SHARED)                                                                                        \
+    const AdmmOperands<TYPE> ad{LIN_ADJOINT_OPERANDS};                                                                              \
+    const KktOperands<TYPE> k{nu, d_Ginv, d_C, d_gz, d_nglam, d_gamma, d_az, SHARED};                                               \
+    const PcgArgs<TYPE> a = pcg_args<TYPE>(nx, N, batch, d_S, d_Pinv, d_gamma, d_alambda, d_r, d_p, tol, max_iter, d_iters, d_max_iter_exit);\
+    auto body = [&](hipStream_t s) { return admm_step_impl<TYPE>(h, k, ad, a, s); };
+#define LIN_ADJOINT_STEP_REFUSE(TYPE)                                                                                               \
+    if (!out) return GBDPCG_ERR_INVALID;                                                                                            \
+    *out = nullptr;                                                                                                                 \
+    if (const gbdpcg_status st = admm_step_refusal<TYPE>(h, k, ad, a, false)) return st;
+#define GBDPCG_ADMM_LIN_ADJOINT(SUF, TYPE)                                                                                          \
+    gbdpcg_status gbdpcg_admm_lin_adjoint_init_##SUF(LIN_ADJOINT_SIZES, const TYPE *d_gz, const TYPE *d_E, const TYPE *d_yf,        \
+                                                     const TYPE *d_rho, TYPE *d_wa, TYPE *d_ya, TYPE *d_gta, void *stream)          \
+    {                                                                                                                               \
+        TYPE *const d_res = nullptr;                                                                                                \
+        const AdmmOperands<TYPE> a{LIN_ADJOINT_OPERANDS};                                                                           \
+        return admm_rows_update_impl<TYPE>(h, nx, nu, N, batch, d_gz, a, nullptr, stream, true);                                    \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_lin_adjoint_update_##SUF(LIN_ADJOINT_SIZES, const TYPE *d_gz, const TYPE *d_E, const TYPE *d_yf,      \
+                                                       const TYPE *d_rho, const TYPE *d_az, TYPE *d_wa, TYPE *d_ya, TYPE *d_gta,    \
+                                                       TYPE *d_res, void *stream)                                                   \
+    {                                                                                                                               \
+        const AdmmOperands<TYPE> a{LIN_ADJOINT_OPERANDS};                                                                           \
+        return admm_rows_update_impl<TYPE>(h, nx, nu, N, batch, d_gz, a, d_az, stream, false);                                      \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_lin_grad_##SUF(LIN_ADJOINT_SIZES, const TYPE *d_z, const TYPE *d_az, const TYPE *d_yf,                \
+                                             const TYPE *d_ya, const TYPE *d_rho, TYPE *d_glo, TYPE *d_ghi, TYPE *d_gE, void *stream)\
+    {                                                                                                                               \
+        return admm_lin_grad_impl<TYPE>(h, nx, nu, mx, mu, N, batch, d_z, d_az, d_yf, d_ya, d_rho, d_glo, d_ghi, d_gE, stream);      \
+    }
+GBDPCG_ADMM_LIN_ADJOINT(f32, float)
+GBDPCG_ADMM_LIN_ADJOINT(f64, double)
+GBDPCG_PAIR_BOTH(admm_lin_adjoint_step, false, LIN_ADJOINT_STEP_PARAMS, LIN_ADJOINT_STEP_SETUP, LIN_ADJOINT_STEP_REFUSE)
+#undef GBDPCG_ADMM_LIN_ADJOINT
+#undef LIN_ADJOINT_SIZES
+#undef LIN_ADJOINT_OPERANDS
+#undef LIN_ADJOINT_STEP_PARAMS
+#undef LIN_ADJOINT_STEP_SETUP
+#undef LIN_ADJOINT_STEP_REFUSE
 
 // ---- the KKT backward pass: the adjoint solve + gradient launch as one call / one graph (the gradient launch alone is with the
 // single launches).  shared: one problem's Ginv, C, S, Pinv, and gG, gC summed over the batch.

@@ -15,6 +15,10 @@ __device__ __forceinline__ double sqrt_once(double a) { return __builtin_sqrt(a)
 // comparisons: a NaN v stays NaN, +-Inf bounds never bind
 template <typename T> __device__ __forceinline__ T clip(T v, T lo, T hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// The projection onto the degenerate set of the adjoint updates (admm_adjoint.hip, the adjoint rows of admm_rows.hip): {0} where the
+// forward multiplier yf is not zero (a NaN included), the whole line elsewhere.  clip(v, +0, +0): a NaN v stays NaN, v = -0 stays -0.
+template <typename T> __device__ __forceinline__ T pin(T v, T yf) { return yf != T(0) ? clip(v, T(0), T(0)) : v; }
+
 // The soft (L1-penalised) bound of the gbdpcg_admm_soft_* / gbdpcg_admm_lin_soft_* calls: the prox of (kappa / rho) dist(., [lo, hi])
 // at s, with the scaled multiplier it leaves.  theta = kappa / rho is ONE correctly rounded division; kappa = +Inf takes the third
 // branch, whose operations (w = clip(s), y = s - w) are those of the hard update: the hard bits.  A tie e = +-theta takes it too;

@@ -292,6 +292,9 @@ hipError_t launch_admm_rebalance(uint64_t len, uint32_t batch, const T *g, const
 // dimension qx / qu, lo holds their offsets.  With cones the launch is the kernel's CONES instantiation, whatever the classes say.
 // kappa (the gbdpcg_admm_lin_soft_* calls; null: hard rows): the layout of lo, the L1 weights -- the kernel's SOFT instantiation.
 // Never with cones (refused): cone rows stay hard.
+// adjoint (the gbdpcg_admm_lin_adjoint_* calls): lo is yf, the forward y, hi is not looked at (may be null), and the projection is
+// yf != 0 ? clip(s, +0, +0) : s -- the bits of the hard linear launch on the explicit rows lo = hi = +0 where yf != 0, -Inf / +Inf
+// elsewhere, with one array read less per row.  Never with cones, kappa or shared (refused).
 struct RowClasses {
     uint32_t lx, qx, lu, qu;
 };
@@ -302,7 +305,7 @@ template <typename T>
 hipError_t launch_admm_rows_update(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *g,
                                    const T *E, const T *lo, const T *hi, const T *rho, const T *z, T *w, T *y, T *gt, T *res,
                                    hipStream_t s, bool init, bool shared = false, const RowClasses *cones = nullptr,
-                                   const T *kappa = nullptr);
+                                   const T *kappa = nullptr, bool adjoint = false);
 // (mx, mu <= 64 and one knot's E blocks, z, t, d within the kernel's LDS)
 template <typename T> bool admm_rows_shape_ok(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu);
 uint32_t admm_rows_knot_chunk(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu);
@@ -316,6 +319,15 @@ bool admm_rows_classes_ok(uint32_t mx, uint32_t mu, const RowClasses &c);
 template <typename T>
 hipError_t launch_kkt_grad(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *z, const T *lam, const T *az, const T *alam,
                            T *gG, T *gC, hipStream_t s, bool shared = false);
+
+// ---- admm_lin_grad.hip : the gradients of a scalar in the rows of the hard linear-row QP from the forward z and y (yf) and the
+// adjoint's z and y (az, ya), one launch, one workgroup per problem.  glo, ghi have the layout of the rows (the bits of
+// launch_admm_grad_bounds over that layout), gE that of E; each may be null (not written), not all three:
+//     gE(r, j) = yf_r != 0 ? rho_b fma(yf_r, az_j, ya_r z_j) : +0
+// (mx, mu <= 64 and a knot within the LDS, as admm_rows_shape_ok; hipErrorInvalidValue otherwise)
+template <typename T>
+hipError_t launch_admm_lin_grad(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *z, const T *az,
+                                const T *yf, const T *ya, const T *rho, T *glo, T *ghi, T *gE, hipStream_t s);
 
 // ---- kkt_refine.hip : mixed-precision refinement around an fp32 solve on a kept factorisation; the lines that define every bit
 // are in the head of the file.  One workgroup per problem in the first two.

@@ -1500,7 +1500,7 @@ gbdpcg_status gbdpcg_graph_create_kkt_backward_shared_f64(gbdpcg_handle_t h, uin
  * The gradients: dl/dg = a_z, reported as d_wa (EXACTLY zero on A: dl/dg_i = 0 for a clamped entry); dl/dc = -a_lambda; dl/dG and
  * dl/dC are gbdpcg_kkt_grad_* on (w, lambda, wa, alambda); dl/dlo = d_glo, dl/dhi = d_ghi; dl/drho = 0 (the solution does not depend
  * on rho).
- * NOT provided: _shared twins, the soft box, linear and cone rows, and the backward pass of a forward loop that has not
+ * NOT provided: _shared twins, the soft box, cone rows (linear rows: gbdpcg_admm_lin_adjoint_* below), and the backward pass of a forward loop that has not
  * converged (the mask is then whatever d_y holds and the result is the gradient of no particular function).
  * Null handle or required pointer, nx, nu, N or batch == 0: GBDPCG_ERR_INVALID, nothing is written (d_r, d_p, d_max_iter_exit and
  * d_Pinv may be NULL as in gbdpcg_kkt_resolve_*, d_C when N == 1).  init, update and grad_bounds are elementwise and refuse no
@@ -1548,6 +1548,92 @@ gbdpcg_status gbdpcg_admm_grad_bounds_f32(gbdpcg_handle_t h, uint32_t nx, uint32
 gbdpcg_status gbdpcg_admm_grad_bounds_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
                                           const double *d_yf, const double *d_rho, const double *d_ya, double *d_glo, double *d_ghi,
                                           void *stream);
+
+/* The backward pass of the hard linear-row QP: gradients of a scalar through (G, C, g, c, E, lo, hi) -> (z, lambda) of the rows
+ * section (gbdpcg_admm_lin_step_* run to convergence), on the device.  At the solution G z + g + C' lambda + rho E' yf = 0, where yf
+ * is the forward d_y (the multiplier of the rows is mu = rho yf).  Row r is ACTIVE iff yf_r != 0: yf_r < 0 where (E z)_r sits at
+ * lo_r, yf_r > 0 where it sits at hi_r -- no threshold; a NaN yf_r counts as active; a row that sits on a bound with yf_r = 0
+ * (weakly active) counts as FREE.  With A the active rows the adjoint triple (a_z, a_lambda, nu) solves
+ *     G a_z + gz + C' a_lambda + E_A' nu = 0,      C a_z = -glam,      (E a_z)_A = 0         gz = dl/dz, glam = dl/dlambda
+ * the optimality conditions of the SAME rows QP with g := gz, c := -glam (d_nglam holds MINUS dl/dlambda) and the degenerate rows
+ * lo = hi = 0 on A, (-Inf, +Inf) elsewhere: the kept S, Phi^-1, G^-1 of Gt = G + rho E'E serve it unchanged, one gbdpcg_kkt_resolve_*
+ * per adjoint iteration.  The calls take the arguments of the gbdpcg_admm_lin_* family with d_yf where d_lo, d_hi stand, d_gz where
+ * d_g and d_nglam where d_c stand; d_wa, d_ya (layout of the rows), d_gta, d_az (layout of g) are the adjoint's splitting state.
+ * Per row the update reads wa, ya, yf (3 arrays, the family's update reads 4) and its projection is
+ *     wa+ = yf_r != 0 ? clip(s, +0, +0) : s              s = fl(v + ya), v the chain of E(r, .) az as in gbdpcg_admm_lin_update_*
+ * every other line is that of gbdpcg_admm_lin_update_* / _init_*: d_wa, d_ya, d_gta, d_res are THE BITS of those calls on the explicit
+ * rows lo = hi = +0 where yf != 0 and -Inf / +Inf elsewhere, signed zeros and NaN included.  From ya = 0 an inactive row's ya stays
+ * exactly 0.
+ *  - gbdpcg_admm_lin_adjoint_init_*: wa <- yf != 0 ? clip(wa, 0, 0) : wa, ya left alone, gta <- gz - rho E'(wa - ya) by the family's chain.
+ *  - gbdpcg_admm_lin_adjoint_update_*: everything behind the adjoint solve that wrote d_az, one launch.
+ *  - gbdpcg_admm_lin_adjoint_step_*: gbdpcg_kkt_resolve_* with g := d_gta, c := d_nglam (writing d_alambda, warm-started from it, and
+ *    d_az) followed by the update on the same stream; the results of the two calls, bit for bit.
+ *  - the graph constructor keeps the POINTER d_rho and sets *out to NULL before its first refusal.
+ *  - gbdpcg_admm_lin_grad_*: from the forward d_z, d_yf and the converged adjoint d_az, d_ya (nu = rho ya), one launch; d_glo, d_ghi
+ *    in the layout of the rows, d_gE in the layout of d_E; each may be NULL (not written), not all three:
+ *        glo_r = yf_r < 0 ? -fl(rho_b ya_r) : +0        ghi_r = yf_r > 0 ? -fl(rho_b ya_r) : +0
+ *        gE(r, j) = yf_r != 0 ? fl(rho_b fma(yf_r, az_j, fl(ya_r z_j))) : +0                  j over the columns of the row's block
+ *    glo, ghi are the bits of gbdpcg_admm_grad_bounds_* called with (mx, mu, N) in the place of (nx, nu, N).
+ * The gradients: dl/dg = d_az (the adjoint's z); dl/dc = -d_alambda; dl/dlo, dl/dhi, dl/dE from gbdpcg_admm_lin_grad_*; dl/dG and
+ * dl/dC are gbdpcg_kkt_grad_* on (z, lambda, az, alambda) -- the gradient in G, not in Gt: nothing flows into E through rho E'E, and
+ * dl/drho = 0, because the solution does not depend on rho.
+ * NOT provided: _shared twins (and a gE summed over the batch for a shared E), cone rows, soft rows, and the backward pass of a
+ * forward loop that has not converged (the mask is then whatever d_y holds).
+ * Refusals, before anything is written: those of the gbdpcg_admm_lin_* family.  Null handle or required pointer, nx, nu, N or batch
+ * == 0, no rows at all: GBDPCG_ERR_INVALID; mx or mu > 64, a knot that does not fit the LDS: GBDPCG_ERR_UNSUPPORTED; a batch of
+ * more than 2^31 - 1 problems: an error of the launch.  step inherits every refusal of gbdpcg_kkt_resolve_* (d_r, d_p,
+ * d_max_iter_exit and d_Pinv may be NULL as there, d_C when N == 1). */
+gbdpcg_status gbdpcg_admm_lin_adjoint_init_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                               uint32_t batch, const float *d_gz, const float *d_E, const float *d_yf,
+                                               const float *d_rho, float *d_wa, float *d_ya, float *d_gta, void *stream);
+gbdpcg_status gbdpcg_admm_lin_adjoint_init_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                               uint32_t batch, const double *d_gz, const double *d_E, const double *d_yf,
+                                               const double *d_rho, double *d_wa, double *d_ya, double *d_gta, void *stream);
+gbdpcg_status gbdpcg_admm_lin_adjoint_update_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                                 uint32_t batch, const float *d_gz, const float *d_E, const float *d_yf,
+                                                 const float *d_rho, const float *d_az, float *d_wa, float *d_ya, float *d_gta,
+                                                 float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_lin_adjoint_update_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                                 uint32_t batch, const double *d_gz, const double *d_E, const double *d_yf,
+                                                 const double *d_rho, const double *d_az, double *d_wa, double *d_ya, double *d_gta,
+                                                 double *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_lin_adjoint_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                               uint32_t batch, const float *d_Ginv, const float *d_C, const float *d_gz,
+                                               const float *d_nglam, const float *d_E, const float *d_yf, const float *d_rho,
+                                               const float *d_S, const float *d_Pinv, float *d_gamma, float *d_alambda, float *d_r,
+                                               float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                               uint8_t *d_max_iter_exit, float *d_az, float *d_wa, float *d_ya, float *d_gta,
+                                               float *d_res, void *stream);
+gbdpcg_status gbdpcg_admm_lin_adjoint_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                               uint32_t batch, const double *d_Ginv, const double *d_C, const double *d_gz,
+                                               const double *d_nglam, const double *d_E, const double *d_yf, const double *d_rho,
+                                               const double *d_S, const double *d_Pinv, double *d_gamma, double *d_alambda,
+                                               double *d_r, double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                               uint8_t *d_max_iter_exit, double *d_az, double *d_wa, double *d_ya, double *d_gta,
+                                               double *d_res, void *stream);
+gbdpcg_status gbdpcg_graph_create_admm_lin_adjoint_step_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                            uint32_t N, uint32_t batch, const float *d_Ginv, const float *d_C,
+                                                            const float *d_gz, const float *d_nglam, const float *d_E,
+                                                            const float *d_yf, const float *d_rho, const float *d_S,
+                                                            const float *d_Pinv, float *d_gamma, float *d_alambda, float *d_r,
+                                                            float *d_p, float tol, uint32_t max_iter, uint32_t *d_iters,
+                                                            uint8_t *d_max_iter_exit, float *d_az, float *d_wa, float *d_ya,
+                                                            float *d_gta, float *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_graph_create_admm_lin_adjoint_step_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu,
+                                                            uint32_t N, uint32_t batch, const double *d_Ginv, const double *d_C,
+                                                            const double *d_gz, const double *d_nglam, const double *d_E,
+                                                            const double *d_yf, const double *d_rho, const double *d_S,
+                                                            const double *d_Pinv, double *d_gamma, double *d_alambda, double *d_r,
+                                                            double *d_p, double tol, uint32_t max_iter, uint32_t *d_iters,
+                                                            uint8_t *d_max_iter_exit, double *d_az, double *d_wa, double *d_ya,
+                                                            double *d_gta, double *d_res, gbdpcg_graph_t *out);
+gbdpcg_status gbdpcg_admm_lin_grad_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                       uint32_t batch, const float *d_z, const float *d_az, const float *d_yf, const float *d_ya,
+                                       const float *d_rho, float *d_glo, float *d_ghi, float *d_gE, void *stream);
+gbdpcg_status gbdpcg_admm_lin_grad_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                       uint32_t batch, const double *d_z, const double *d_az, const double *d_yf,
+                                       const double *d_ya, const double *d_rho, double *d_glo, double *d_ghi, double *d_gE,
+                                       void *stream);
 
 /* Mixed-precision refinement of a KKT point: fp32 solves on a kept fp32 factorisation, the defect and the point in fp64.
  * For a caller who needs more digits in the step than fp32 carries (SQP close to convergence, an adjoint solve, ADMM on a
