@@ -79,6 +79,9 @@ SYMBOLS = [
     # the backward pass of the hard linear-row QP: the admm_lin family with yf where lo, hi stand, and the gradients in the rows
     *[f"gbdpcg_{name}_{suf}" for name in ("admm_lin_adjoint_init", "admm_lin_adjoint_update", "admm_lin_adjoint_step",
                                           "graph_create_admm_lin_adjoint_step", "admm_lin_grad") for suf in ("f32", "f64")],
+    # the backward pass of the soft box and rows QPs: the mask in front of the hard adjoint calls, the gradients with kappa
+    *[f"gbdpcg_{name}_{suf}" for name in ("admm_soft_mask", "admm_lin_soft_mask", "admm_soft_grad_bounds", "admm_lin_soft_grad")
+      for suf in ("f32", "f64")],
     "gbdpcg_demote_f32", "gbdpcg_kkt_defect_mixed", "gbdpcg_kkt_refine_apply", "gbdpcg_kkt_refine_step",
     "gbdpcg_graph_create_kkt_refine_step",
     "gbdpcg_kkt_defect_mixed_reg", "gbdpcg_kkt_defect_mixed_shared", "gbdpcg_kkt_refine_step_reg", "gbdpcg_kkt_refine_step_shared",
@@ -174,6 +177,14 @@ def _resolve_argtypes(lib):
         getattr(lib, f"gbdpcg_admm_lin_adjoint_step_{suf}").argtypes = ladj + [vp]
         getattr(lib, f"gbdpcg_graph_create_admm_lin_adjoint_step_{suf}").argtypes = ladj + [ctypes.POINTER(vp)]
         getattr(lib, f"gbdpcg_admm_lin_grad_{suf}").argtypes = lsizes + [vp, vp, vp, vp, vp] + [vp, vp, vp] + [vp]
+        # the backward pass of the soft QPs
+        #   mask         h, nx, nu, [mx, mu], N, batch | yf, kappa, rho | ym | stream
+        #   grad_bounds  h, nx, nu, N, batch           | yf, kappa, rho, ya, az | glo, ghi, gkappa | stream
+        #   lin grad     h, nx, nu, mx, mu, N, batch   | z, az, E, yf, ya, kappa, rho | glo, ghi, gkappa, gE | stream
+        getattr(lib, f"gbdpcg_admm_soft_mask_{suf}").argtypes = sizes + [vp, vp, vp] + [vp] + [vp]
+        getattr(lib, f"gbdpcg_admm_lin_soft_mask_{suf}").argtypes = lsizes + [vp, vp, vp] + [vp] + [vp]
+        getattr(lib, f"gbdpcg_admm_soft_grad_bounds_{suf}").argtypes = sizes + [vp, vp, vp, vp, vp] + [vp, vp, vp] + [vp]
+        getattr(lib, f"gbdpcg_admm_lin_soft_grad_{suf}").argtypes = lsizes + [vp] * 7 + [vp] * 4 + [vp]
 
     # mixed-precision refinement (no suffix: fp64 data and point, fp32 solve)
     head = [vp, u32, u32, u32, u32, vp, vp, vp, vp]                # h, nx, nu, N, batch, G, C, g, c (fp64)
@@ -1433,6 +1444,78 @@ class Solver:
                        _p(gE), self._stream(stream)), "admm_lin_grad")
         return glo, ghi, gE
 
+    # ---- the backward pass of the soft box and rows QPs (include/gbdpcg.h): the forward y splits the rows into free, held and
+    # saturated; the mask turns it into the yf of the hard adjoint methods above, the gradient launches know of kappa
+    def admm_soft_mask(self, nx, nu, N, batch, yf, kappa, rho, ym=None, stream=None):
+        """gbdpcg_admm_soft_mask_*: ym = |yf| >= kappa / rho ? +0 : yf in the layout of g.  rho is the rho of the update that wrote
+        yf.  Returns ym (never yf itself)."""
+        import torch
+        suf, _ = _suffix(yf)
+        if ym is None:
+            ym = torch.empty_like(yf)
+        self._box(yf, batch, kappa, ym)
+        fn = getattr(self.lib, f"gbdpcg_admm_soft_mask_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(yf), _p(kappa), _p(self._rho(rho, batch, yf)), _p(ym), self._stream(stream)),
+                    "admm_soft_mask")
+        return ym
+
+    def admm_lin_soft_mask(self, nx, nu, mx, mu, N, batch, yf, kappa, rho, ym=None, stream=None):
+        """gbdpcg_admm_lin_soft_mask_*: the mask in the layout of the rows."""
+        import torch
+        suf, _ = _suffix(yf)
+        if ym is None:
+            ym = torch.empty_like(yf)
+        _, nw, _, _ = self._lin_sizes(nx, nu, mx, mu, N)
+        for t in (yf, kappa, ym):
+            assert t.is_cuda and t.is_contiguous() and t.numel() == batch * nw and t.dtype == yf.dtype
+        fn = getattr(self.lib, f"gbdpcg_admm_lin_soft_mask_{suf}")
+        self._check(fn(self.h, nx, nu, mx, mu, N, batch, _p(yf), _p(kappa), _p(self._rho(rho, batch, yf)), _p(ym),
+                       self._stream(stream)), "admm_lin_soft_mask")
+        return ym
+
+    def admm_soft_grad_bounds(self, nx, nu, N, batch, yf, kappa, rho, ya, az, glo=None, ghi=None, gkappa=None, want="lhk", stream=None):
+        """gbdpcg_admm_soft_grad_bounds_*: (dl/dlo, dl/dhi, dl/dkappa) of the soft box from the UNMASKED yf, kappa and the adjoint's ya,
+        az.  want: which of "l", "h", "k" to allocate when the tensor is not passed (the others stay NULL)."""
+        import torch
+        suf, _ = _suffix(yf)
+        if glo is None and "l" in want:
+            glo = torch.empty_like(yf)
+        if ghi is None and "h" in want:
+            ghi = torch.empty_like(yf)
+        if gkappa is None and "k" in want:
+            gkappa = torch.empty_like(yf)
+        self._box(yf, batch, kappa, ya, az, *[t for t in (glo, ghi, gkappa) if t is not None])
+        assert glo is not None or ghi is not None or gkappa is not None
+        fn = getattr(self.lib, f"gbdpcg_admm_soft_grad_bounds_{suf}")
+        self._check(fn(self.h, nx, nu, N, batch, _p(yf), _p(kappa), _p(self._rho(rho, batch, yf)), _p(ya), _p(az), _p(glo), _p(ghi),
+                       _p(gkappa), self._stream(stream)), "admm_soft_grad_bounds")
+        return glo, ghi, gkappa
+
+    def admm_lin_soft_grad(self, nx, nu, mx, mu, N, batch, z, az, E, yf, ya, kappa, rho, glo=None, ghi=None, gkappa=None, gE=None,
+                           want="lhkE", stream=None):
+        """gbdpcg_admm_lin_soft_grad_*: (dl/dlo, dl/dhi, dl/dkappa) in the layout of the rows and dl/dE in the layout of E from the
+        forward z, the UNMASKED yf, kappa and the adjoint's az, ya.  want: which of "l", "h", "k", "E" to allocate when the tensor is
+        not passed (the others stay NULL)."""
+        import torch
+        suf, _ = _suffix(z)
+        _, nw, ne, _ = self._lin_sizes(nx, nu, mx, mu, N)
+        kw = dict(dtype=z.dtype, device=z.device)
+        if glo is None and "l" in want:
+            glo = torch.empty(batch * nw, **kw)
+        if ghi is None and "h" in want:
+            ghi = torch.empty(batch * nw, **kw)
+        if gkappa is None and "k" in want:
+            gkappa = torch.empty(batch * nw, **kw)
+        if gE is None and "E" in want:
+            gE = torch.empty(batch * ne, **kw)
+        nz = (nx + nu) * N - nu
+        for t, cnt in ((z, nz), (az, nz), (E, ne), (yf, nw), (ya, nw), (kappa, nw), (glo, nw), (ghi, nw), (gkappa, nw), (gE, ne)):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() == batch * cnt and t.dtype == z.dtype)
+        assert None not in (az, E, yf, ya, kappa) and any(t is not None for t in (glo, ghi, gkappa, gE))
+        fn = getattr(self.lib, f"gbdpcg_admm_lin_soft_grad_{suf}")
+        self._check(fn(self.h, nx, nu, mx, mu, N, batch, _p(z), _p(az), _p(E), _p(yf), _p(ya), _p(kappa), _p(self._rho(rho, batch, z)),
+                       _p(glo), _p(ghi), _p(gkappa), _p(gE), self._stream(stream)), "admm_lin_soft_grad")
+        return glo, ghi, gkappa, gE
 
     # ---- mixed-precision refinement: fp64 problem data and point, fp32 solves on a kept fp32 factorisation (include/gbdpcg.h)
     def demote(self, src, dst=None, stream=None):

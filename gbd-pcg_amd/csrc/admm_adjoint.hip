@@ -25,25 +25,14 @@
 // Bound gradients (gbdpcg_admm_grad_bounds_*), with ya the adjoint's y (nu = rho ya), one multiplication and one negation:
 //     glo_i = yf_i < 0 ? -(rho_b ya_i) : +0        ghi_i = yf_i > 0 ? -(rho_b ya_i) : +0
 // the same launch shape and head / body / tail scheme over yf, ya, glo, ghi.
+#include "elementwise_split.hpp"
 #include "ieee_once.hpp"
 #include "internal.hpp"
 #include "norm_fold.hpp"
 
-#include <initializer_list>
-
 namespace gbdpcg {
 
 namespace {
-
-template <typename T> struct AdjVec;
-template <> struct AdjVec<float> {
-    static constexpr uint32_t N = 4;
-    typedef float type __attribute__((ext_vector_type(4)));
-};
-template <> struct AdjVec<double> {
-    static constexpr uint32_t N = 2;
-    typedef double type __attribute__((ext_vector_type(2)));
-};
 
 // One element.  w, y: in / out (INIT leaves y alone); mp, md: the running maxima of the two norms (not INIT).
 template <typename T, bool INIT, typename U>
@@ -63,17 +52,6 @@ __device__ __forceinline__ T adjoint_element(T az, T &w, T &y, T yf, T gz, T rho
         w = wn;
         y = yn;
         return fma_once(-rho, t, gz);
-    }
-}
-
-// The head / body / tail split of a problem that starts `off` elements behind 16-byte aligned bases.
-template <uint32_t VN> __device__ __forceinline__ void split(uint32_t vec, uint64_t off, uint64_t nz, uint64_t &head, uint64_t &body)
-{
-    head = 0, body = 0;
-    if (vec) {
-        head = (VN - (uint32_t)(off % VN)) % VN;
-        if (head > nz) head = nz;
-        body = (nz - head) / VN;
     }
 }
 
@@ -174,17 +152,6 @@ __global__ __launch_bounds__(256) void admm_grad_bounds_kernel(uint64_t nz, uint
     }
     for (uint64_t i = head + body * VN + tid; i < nz; i += threads) scalar(i);
 }
-
-namespace {
-
-uint32_t all_aligned(std::initializer_list<const void *> ptrs)
-{
-    for (const void *p : ptrs)
-        if (reinterpret_cast<uintptr_t>(p) % 16) return 0;
-    return 1;
-}
-
-}  // namespace
 
 template <typename T>
 hipError_t launch_admm_adjoint_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *gz, const T *yf, const T *rho,

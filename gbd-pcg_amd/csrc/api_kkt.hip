@@ -321,6 +321,64 @@ gbdpcg_status admm_lin_grad_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, ui
     return GBDPCG_OK;
 }
 
+// ---- the backward pass of the soft box and rows QPs (admm_soft_grad.hip, the SOFT instantiation of admm_lin_grad.hip): the mask
+// that turns the forward y into the yf of the hard adjoint loops above, and the gradient launches that know of kappa.
+// The mask, one launch, elementwise.  rows: (mx, mu) and the rows' refusals; otherwise the layout of g.  d_ym == d_yf is refused
+// here, in front of everything else that could be: the unmasked yf is still needed behind the adjoint loop.
+template <typename T>
+gbdpcg_status admm_soft_mask_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch,
+                                  const T *d_yf, const T *d_kappa, const T *d_rho, T *d_ym, void *stream, bool rows)
+{
+    if (!h || !d_yf || !d_kappa || !d_rho || !d_ym || d_ym == d_yf || nx == 0 || nu == 0 || N == 0 || batch == 0)
+        return GBDPCG_ERR_INVALID;
+    uint64_t len = ((uint64_t)nx + nu) * N - nu;
+    if (rows) {
+        AdmmOperands<T> a{};
+        a.mx = mx, a.mu = mu;
+        const gbdpcg_status st = admm_rows_status<T>(nx, nu, a, N);
+        if (st != GBDPCG_OK) return st;
+        len = ((uint64_t)mx + mu) * N - mu;
+    }
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_admm_soft_mask<T>(len, batch, d_yf, d_kappa, d_rho, d_ym, (hipStream_t)stream));
+    return GBDPCG_OK;
+}
+
+// dl/dlo, dl/dhi, dl/dkappa of the soft box, one launch, elementwise; each output may be null, not all three.
+template <typename T>
+gbdpcg_status admm_soft_grad_bounds_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_yf,
+                                         const T *d_kappa, const T *d_rho, const T *d_ya, const T *d_az, T *d_glo, T *d_ghi,
+                                         T *d_gkappa, void *stream)
+{
+    if (!h || !d_yf || !d_kappa || !d_rho || !d_ya || !d_az || (!d_glo && !d_ghi && !d_gkappa) || nx == 0 || nu == 0 || N == 0 ||
+        batch == 0)
+        return GBDPCG_ERR_INVALID;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_admm_soft_grad_bounds<T>(nx, nu, N, batch, d_yf, d_kappa, d_rho, d_ya, d_az, d_glo, d_ghi, d_gkappa,
+                                               (hipStream_t)stream));
+    return GBDPCG_OK;
+}
+
+// dl/dlo, dl/dhi, dl/dkappa, dl/dE of the soft rows, one launch; each output may be null, not all four.  The refusals of the rows
+// family.
+template <typename T>
+gbdpcg_status admm_lin_soft_grad_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch,
+                                      const T *d_z, const T *d_az, const T *d_E, const T *d_yf, const T *d_ya, const T *d_kappa,
+                                      const T *d_rho, T *d_glo, T *d_ghi, T *d_gkappa, T *d_gE, void *stream)
+{
+    if (!h || !d_z || !d_az || !d_E || !d_yf || !d_ya || !d_kappa || !d_rho || (!d_glo && !d_ghi && !d_gkappa && !d_gE) || nx == 0 ||
+        nu == 0 || N == 0 || batch == 0)
+        return GBDPCG_ERR_INVALID;
+    AdmmOperands<T> a{};
+    a.mx = mx, a.mu = mu;
+    const gbdpcg_status st = admm_rows_status<T>(nx, nu, a, N);
+    if (st != GBDPCG_OK) return st;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_admm_lin_grad<T>(nx, nu, mx, mu, N, batch, d_z, d_az, d_yf, d_ya, d_rho, d_glo, d_ghi, d_gE, (hipStream_t)stream,
+                                       d_E, d_kappa, d_gkappa));
+    return GBDPCG_OK;
+}
+
 // One adjoint iteration: admm_step_impl with the adjoint update behind the solve.  k.g is gz, k.c is nglam, k.z is az; a.lo is yf
 // (a.hi too: the refusal of the box step is the refusal here), a.w, a.y, a.gt, a.res the adjoint's splitting state.
 template <typename T>
@@ -976,6 +1034,39 @@ GBDPCG_PAIR_BOTH(admm_lin_adjoint_step, false, LIN_ADJOINT_STEP_PARAMS, LIN_ADJO
 #undef LIN_ADJOINT_STEP_PARAMS
 #undef LIN_ADJOINT_STEP_SETUP
 #undef LIN_ADJOINT_STEP_REFUSE
+
+// ---- the backward pass of the soft box and rows QPs: the mask in front of the hard adjoint calls above, and the gradient launches
+// with kappa.  No step of their own: the adjoint iteration is gbdpcg_admm_adjoint_step_* / gbdpcg_admm_lin_adjoint_step_* on d_ym.
+#define GBDPCG_ADMM_SOFT_ADJOINT(SUF, TYPE)                                                                                         \
+    gbdpcg_status gbdpcg_admm_soft_mask_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,              \
+                                              const TYPE *d_yf, const TYPE *d_kappa, const TYPE *d_rho, TYPE *d_ym, void *stream)   \
+    {                                                                                                                               \
+        return admm_soft_mask_impl<TYPE>(h, nx, nu, 0, 0, N, batch, d_yf, d_kappa, d_rho, d_ym, stream, false);                     \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_lin_soft_mask_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,\
+                                                  uint32_t batch, const TYPE *d_yf, const TYPE *d_kappa, const TYPE *d_rho,         \
+                                                  TYPE *d_ym, void *stream)                                                         \
+    {                                                                                                                               \
+        return admm_soft_mask_impl<TYPE>(h, nx, nu, mx, mu, N, batch, d_yf, d_kappa, d_rho, d_ym, stream, true);                    \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_soft_grad_bounds_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,       \
+                                                     const TYPE *d_yf, const TYPE *d_kappa, const TYPE *d_rho, const TYPE *d_ya,    \
+                                                     const TYPE *d_az, TYPE *d_glo, TYPE *d_ghi, TYPE *d_gkappa, void *stream)      \
+    {                                                                                                                               \
+        return admm_soft_grad_bounds_impl<TYPE>(h, nx, nu, N, batch, d_yf, d_kappa, d_rho, d_ya, d_az, d_glo, d_ghi, d_gkappa,      \
+                                                stream);                                                                            \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_lin_soft_grad_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,\
+                                                  uint32_t batch, const TYPE *d_z, const TYPE *d_az, const TYPE *d_E,               \
+                                                  const TYPE *d_yf, const TYPE *d_ya, const TYPE *d_kappa, const TYPE *d_rho,       \
+                                                  TYPE *d_glo, TYPE *d_ghi, TYPE *d_gkappa, TYPE *d_gE, void *stream)               \
+    {                                                                                                                               \
+        return admm_lin_soft_grad_impl<TYPE>(h, nx, nu, mx, mu, N, batch, d_z, d_az, d_E, d_yf, d_ya, d_kappa, d_rho, d_glo, d_ghi, \
+                                             d_gkappa, d_gE, stream);                                                               \
+    }
+GBDPCG_ADMM_SOFT_ADJOINT(f32, float)
+GBDPCG_ADMM_SOFT_ADJOINT(f64, double)
+#undef GBDPCG_ADMM_SOFT_ADJOINT
 
 // ---- the KKT backward pass: the adjoint solve + gradient launch as one call / one graph (the gradient launch alone is with the
 // single launches).  shared: one problem's Ginv, C, S, Pinv, and gG, gC summed over the batch.

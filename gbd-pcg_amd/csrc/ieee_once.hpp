@@ -42,6 +42,16 @@ template <typename T> __device__ __forceinline__ T soft_init(T w, T lo, T hi, T 
     return kappa == T(__builtin_huge_val()) ? clip(w, lo, hi) : w;
 }
 
+// The rows a soft update left SATURATED (admm_soft_grad.hip, the SOFT gradients of admm_lin_grad.hip): |yf| >= theta with the theta of
+// soft_clip, the same ONE division -- the update wrote +-theta itself, so the comparison is exact; a NaN yf fails it.
+__device__ __forceinline__ float abs_once(float a) { return __builtin_fabsf(a); }
+__device__ __forceinline__ double abs_once(double a) { return __builtin_fabs(a); }
+template <typename T> __device__ __forceinline__ bool soft_saturated(T yf, T kappa, T rho)
+{
+    const T theta = kappa / rho;
+    return abs_once(yf) >= theta;
+}
+
 // The kappa argument of a kernel with a compile-time SOFT switch is a trailing parameter PACK: one pointer in the soft
 // instantiations, empty in the hard ones, which therefore take the arguments, and compile to the code, of a kernel that knows
 // nothing of kappa (an empty struct in its place would still take a kernel-argument slot and move the hidden arguments).

@@ -325,9 +325,25 @@ hipError_t launch_kkt_grad(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
 // launch_admm_grad_bounds over that layout), gE that of E; each may be null (not written), not all three:
 //     gE(r, j) = yf_r != 0 ? rho_b fma(yf_r, az_j, ya_r z_j) : +0
 // (mx, mu <= 64 and a knot within the LDS, as admm_rows_shape_ok; hipErrorInvalidValue otherwise)
+// kappa (the gbdpcg_admm_lin_soft_grad_* calls; null: the hard rows, E and gkappa not looked at): the kernel's SOFT instantiation --
+// with sat = |yf_r| >= kappa_r / rho_b, glo and ghi are +0 on saturated rows, gE keeps the line above with the unmasked yf, and
+//     gkappa_r = sat ? (yf_r > 0 ? v : -v) : +0,  v the chain of E(r, .) az in ascending j            (may be null like the others)
 template <typename T>
 hipError_t launch_admm_lin_grad(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *z, const T *az,
-                                const T *yf, const T *ya, const T *rho, T *glo, T *ghi, T *gE, hipStream_t s);
+                                const T *yf, const T *ya, const T *rho, T *glo, T *ghi, T *gE, hipStream_t s, const T *E = nullptr,
+                                const T *kappa = nullptr, T *gkappa = nullptr);
+
+// ---- admm_soft_grad.hip : the elementwise launches of the backward pass of the soft box and rows QPs, the launch shape of
+// launch_admm_grad_bounds.  theta = kappa / rho_b is the one division of the soft update, sat = |yf| >= theta (a NaN yf fails):
+//     mask:        ym = sat ? +0 : yf over `len` elements per problem (nz: the box, nw: the rows); ym == yf is refused
+//     grad_bounds: glo = (yf < 0 && !sat) ? -(rho_b ya) : +0, ghi likewise with > 0, gkappa = sat ? (yf > 0 ? az : -az) : +0,
+//                  over the layout of g; each output may be null (not written), not all three
+// rho is the rho of the update that wrote yf.
+template <typename T>
+hipError_t launch_admm_soft_mask(uint64_t len, uint32_t batch, const T *yf, const T *kappa, const T *rho, T *ym, hipStream_t s);
+template <typename T>
+hipError_t launch_admm_soft_grad_bounds(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *yf, const T *kappa, const T *rho,
+                                        const T *ya, const T *az, T *glo, T *ghi, T *gkappa, hipStream_t s);
 
 // ---- kkt_refine.hip : mixed-precision refinement around an fp32 solve on a kept factorisation; the lines that define every bit
 // are in the head of the file.  One workgroup per problem in the first two.

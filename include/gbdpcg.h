@@ -1500,7 +1500,7 @@ gbdpcg_status gbdpcg_graph_create_kkt_backward_shared_f64(gbdpcg_handle_t h, uin
  * The gradients: dl/dg = a_z, reported as d_wa (EXACTLY zero on A: dl/dg_i = 0 for a clamped entry); dl/dc = -a_lambda; dl/dG and
  * dl/dC are gbdpcg_kkt_grad_* on (w, lambda, wa, alambda); dl/dlo = d_glo, dl/dhi = d_ghi; dl/drho = 0 (the solution does not depend
  * on rho).
- * NOT provided: _shared twins, the soft box, cone rows (linear rows: gbdpcg_admm_lin_adjoint_* below), and the backward pass of a forward loop that has not
+ * NOT provided: _shared twins, cone rows (linear rows: gbdpcg_admm_lin_adjoint_* below; the soft box: gbdpcg_admm_soft_mask_* below), and the backward pass of a forward loop that has not
  * converged (the mask is then whatever d_y holds and the result is the gradient of no particular function).
  * Null handle or required pointer, nx, nu, N or batch == 0: GBDPCG_ERR_INVALID, nothing is written (d_r, d_p, d_max_iter_exit and
  * d_Pinv may be NULL as in gbdpcg_kkt_resolve_*, d_C when N == 1).  init, update and grad_bounds are elementwise and refuse no
@@ -1577,7 +1577,8 @@ gbdpcg_status gbdpcg_admm_grad_bounds_f64(gbdpcg_handle_t h, uint32_t nx, uint32
  * The gradients: dl/dg = d_az (the adjoint's z); dl/dc = -d_alambda; dl/dlo, dl/dhi, dl/dE from gbdpcg_admm_lin_grad_*; dl/dG and
  * dl/dC are gbdpcg_kkt_grad_* on (z, lambda, az, alambda) -- the gradient in G, not in Gt: nothing flows into E through rho E'E, and
  * dl/drho = 0, because the solution does not depend on rho.
- * NOT provided: _shared twins (and a gE summed over the batch for a shared E), cone rows, soft rows, and the backward pass of a
+ * NOT provided: _shared twins (and a gE summed over the batch for a shared E), cone rows (soft rows: gbdpcg_admm_lin_soft_mask_*
+ * below), and the backward pass of a
  * forward loop that has not converged (the mask is then whatever d_y holds).
  * Refusals, before anything is written: those of the gbdpcg_admm_lin_* family.  Null handle or required pointer, nx, nu, N or batch
  * == 0, no rows at all: GBDPCG_ERR_INVALID; mx or mu > 64, a knot that does not fit the LDS: GBDPCG_ERR_UNSUPPORTED; a batch of
@@ -1634,6 +1635,67 @@ gbdpcg_status gbdpcg_admm_lin_grad_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t 
                                        uint32_t batch, const double *d_z, const double *d_az, const double *d_yf,
                                        const double *d_ya, const double *d_rho, double *d_glo, double *d_ghi, double *d_gE,
                                        void *stream);
+
+/* The backward pass of the SOFT box and rows QPs (gbdpcg_admm_soft_step_*, gbdpcg_admm_lin_soft_step_* run to convergence):
+ * gradients of a scalar through (G, C, g, c, [E,] lo, hi, kappa) -> (w or z, lambda), on the device.  Behind a soft update the
+ * forward d_y (here d_yf, read only) splits the rows of problem b into three sets, to the bit and with no threshold; theta_r =
+ * fl(kappa_r / rho_b) is the one correctly rounded division of the update:
+ *     free        yf_r == 0                          inside its bounds, mu_r = 0
+ *     held        yf_r != 0 and |yf_r| < theta_r     on a bound with |mu_r| < kappa_r       (a NaN yf_r fails the comparison: held)
+ *     saturated   |yf_r| >= theta_r                  beyond its bound, mu_r = +-kappa_r: the update wrote +-theta_r itself
+ * A row whose excess ties with theta_r takes the third branch of the update with y = +-theta_r and counts as saturated.  The
+ * multiplier of a saturated row is a constant, so in the adjoint problem the row is as free as an inactive one: the adjoint is the
+ * HARD adjoint loop (gbdpcg_admm_adjoint_* / gbdpcg_admm_lin_adjoint_* above) on a MASKED copy of d_yf, and no soft adjoint update
+ * exists.  A saturated row contributes through kappa and E instead:
+ *     dl/dkappa_r = sign(yf_r) (E a_z)_r  on saturated rows, 0 elsewhere        dl/dE(r, j) keeps rho yf_r a_z,j on them
+ *  - gbdpcg_admm_soft_mask_* (nz elements per problem, the layout of g) and gbdpcg_admm_lin_soft_mask_* (the layout of the rows):
+ *        ym_r = |yf_r| >= theta_r ? +0 : yf_r
+ *    kappa = +Inf gives d_ym the bits of d_yf, kappa = 0 gives +0 everywhere.  d_ym == d_yf is GBDPCG_ERR_INVALID whatever else the
+ *    call would answer: the unmasked d_yf is needed by the gradient launch.  d_rho MUST be the rho of the update that wrote d_yf:
+ *    take the mask directly behind an update (or a step), never behind a rebalance with no update after it, which rescales y away
+ *    from +-theta.
+ *  - gbdpcg_admm_soft_grad_bounds_*: from d_yf, d_kappa and the converged adjoint d_ya, d_az (the loop run on d_ym), with
+ *    sat = |yf| >= theta, one launch, each output may be NULL (not written), not all three:
+ *        glo_i = (yf_i < 0 && !sat) ? -fl(rho_b ya_i) : +0        ghi_i = (yf_i > 0 && !sat) ? -fl(rho_b ya_i) : +0
+ *        gkappa_i = sat ? (yf_i > 0 ? az_i : -az_i) : +0
+ *    glo, ghi are the bits of gbdpcg_admm_grad_bounds_* called with d_ym.
+ *  - gbdpcg_admm_lin_soft_grad_*: the rows' launch with kappa, each output may be NULL, not all four:
+ *        glo_r, ghi_r   the lines above over the rows
+ *        gE(r, j)       the line of gbdpcg_admm_lin_grad_* with the UNMASKED yf: its bits on (z, az, yf, ya)
+ *        gkappa_r = sat ? (yf_r > 0 ? v : -v) : +0,   v = the chain fma(E(r, j), az_j, acc) over the block's columns, ascending j, seed +0
+ * Every line is one IEEE operation or a comparison: the outputs are defined to the bit whatever the alignment of the pointers.
+ * The gradients: dl/dg, dl/dc, dl/dG, dl/dC as in the hard sections (gbdpcg_kkt_grad_* on the forward pair and the adjoint pair);
+ * dl/dlo, dl/dhi, dl/dkappa[, dl/dE] from the launches here; dl/drho = 0.  Where kappa = +Inf dl/dkappa is exactly +0 and every
+ * other gradient has the bits of the hard calls.
+ * NOT provided: _shared twins, cone rows, the backward pass of a forward loop that has not converged, and gradients behind a
+ * rebalance with no update after it.
+ * Refusals, before anything is written: null handle or required pointer (every input; at least one output), nx, nu, N or batch
+ * == 0, d_ym == d_yf, no rows at all: GBDPCG_ERR_INVALID; the rows calls: mx or mu > 64, a knot that does not fit the LDS:
+ * GBDPCG_ERR_UNSUPPORTED; a batch of more than 2^31 - 1 problems: an error of the launch. */
+gbdpcg_status gbdpcg_admm_soft_mask_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_yf,
+                                        const float *d_kappa, const float *d_rho, float *d_ym, void *stream);
+gbdpcg_status gbdpcg_admm_soft_mask_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_yf,
+                                        const double *d_kappa, const double *d_rho, double *d_ym, void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_mask_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                            uint32_t batch, const float *d_yf, const float *d_kappa, const float *d_rho, float *d_ym,
+                                            void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_mask_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                            uint32_t batch, const double *d_yf, const double *d_kappa, const double *d_rho,
+                                            double *d_ym, void *stream);
+gbdpcg_status gbdpcg_admm_soft_grad_bounds_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                               const float *d_yf, const float *d_kappa, const float *d_rho, const float *d_ya,
+                                               const float *d_az, float *d_glo, float *d_ghi, float *d_gkappa, void *stream);
+gbdpcg_status gbdpcg_admm_soft_grad_bounds_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                               const double *d_yf, const double *d_kappa, const double *d_rho, const double *d_ya,
+                                               const double *d_az, double *d_glo, double *d_ghi, double *d_gkappa, void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_grad_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                            uint32_t batch, const float *d_z, const float *d_az, const float *d_E, const float *d_yf,
+                                            const float *d_ya, const float *d_kappa, const float *d_rho, float *d_glo, float *d_ghi,
+                                            float *d_gkappa, float *d_gE, void *stream);
+gbdpcg_status gbdpcg_admm_lin_soft_grad_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                            uint32_t batch, const double *d_z, const double *d_az, const double *d_E,
+                                            const double *d_yf, const double *d_ya, const double *d_kappa, const double *d_rho,
+                                            double *d_glo, double *d_ghi, double *d_gkappa, double *d_gE, void *stream);
 
 /* Mixed-precision refinement of a KKT point: fp32 solves on a kept fp32 factorisation, the defect and the point in fp64.
  * For a caller who needs more digits in the step than fp32 carries (SQP close to convergence, an adjoint solve, ADMM on a
