@@ -22,6 +22,8 @@ they are differentiable in kappa as well.
 """
 from __future__ import annotations
 
+from typing import NamedTuple, Optional
+
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -30,6 +32,16 @@ from . import binding
 
 def _sizes(nx, nu, N):
     return {"G": (nx * nx + nu * nu) * N - nu * nu, "C": (nx * nx + nx * nu) * (N - 1), "g": (nx + nu) * N - nu, "c": nx * N}
+
+
+def _keep_live(gz, nglam, batch):
+    """keep(t): t with the rows of the problems whose cotangents gz, nglam are exactly zero replaced by exact zeros (None stays None)."""
+    live = ((gz.view(batch, -1) != 0).any(1) | (nglam.view(batch, -1) != 0).any(1)).view(batch, 1)
+
+    def keep(t):
+        return None if t is None else torch.where(live, t.view(batch, -1), t.new_zeros(())).view(-1)
+
+    return keep
 
 
 class _KktSolve(torch.autograd.Function):
@@ -75,11 +87,7 @@ class _KktSolve(torch.autograd.Function):
         # A problem that does not enter the loss (padding, a mask) has an exactly zero right-hand side: the adjoint solve starts from a
         # zero residual and returns NaN for it (the solve's rule, include/gbdpcg.h), where the gradients are exactly zero.  The mask
         # is a device tensor and the selects are stream-ordered: nothing here waits for the device.
-        live = ((gz.view(batch, -1) != 0).any(1) | (nglam.view(batch, -1) != 0).any(1)).view(batch, 1)
-
-        def keep(t):
-            return None if t is None else torch.where(live, t.view(batch, -1), t.new_zeros(())).view(-1)
-
+        keep = _keep_live(gz, nglam, batch)
         if (need_G or need_C) and not shared:
             solver.kkt_backward(nx, nu, N, batch, Ginv, C, gz, nglam, S, Pinv, gamma, z, lam, az, alam, gG, gC, tol=tol, max_iter=max_iter)
             az, alam, gG, gC = keep(az), keep(alam), keep(gG), keep(gC)
@@ -96,65 +104,139 @@ class _KktSolve(torch.autograd.Function):
         return (*grads, grho) + (None,) * 8
 
 
-class _BoxQpSolve(torch.autograd.Function):
+class _Family(NamedTuple):
+    """One of the four ADMM QPs: what its bounds are on, whether they are soft, and the Solver methods its two loops are made of."""
+    rows: bool            # the bounds are on E z (E is an input, z the output); otherwise on z itself (the output is w)
+    soft: bool            # L1-penalised bounds with the weights kappa (an input)
+    init: str
+    step: str
+    mask: Optional[str]   # soft: what turns the forward y into the yf of the hard adjoint loop
+    adj_init: str
+    adj_step: str
+    grad: str
+
+
+_BOX = _Family(False, False, "admm_init", "admm_step", None, "admm_adjoint_init", "admm_adjoint_step", "admm_grad_bounds")
+_LIN = _Family(True, False, "admm_lin_init", "admm_lin_step", None, "admm_lin_adjoint_init", "admm_lin_adjoint_step", "admm_lin_grad")
+_SOFT_BOX = _Family(False, True, "admm_soft_init", "admm_soft_step", "admm_soft_mask", "admm_adjoint_init", "admm_adjoint_step",
+                    "admm_soft_grad_bounds")
+_SOFT_LIN = _Family(True, True, "admm_lin_soft_init", "admm_lin_soft_step", "admm_lin_soft_mask", "admm_lin_adjoint_init",
+                    "admm_lin_adjoint_step", "admm_lin_soft_grad")
+
+
+class _AdmmQpSolve(torch.autograd.Function):
+    """dims: (nx, nu, N), with rows (nx, nu, mx, mu, N) -- what every Solver call of the family starts with, in front of batch.  E and
+    kappa are None where the family has none."""
+
     @staticmethod
-    def forward(ctx, G, C, g, c, lo, hi, rho, solver, nx, nu, N, batch, iters, adj_iters, tol, max_iter):
+    def forward(ctx, fam, solver, dims, batch, iters, adj_iters, tol, max_iter, G, C, g, c, E, lo, hi, kappa, rho):
+        nx, nu, N = dims[0], dims[1], dims[-1]
         sz = _sizes(nx, nu, N)
         kw = dict(dtype=g.dtype, device=g.device)
         S = torch.empty(batch * 3 * nx * nx * N, **kw)
         Pinv, Ginv = torch.empty_like(S), torch.empty(batch * sz["G"], **kw)
         gamma = torch.empty(batch * sz["c"], **kw)
         lam, z = torch.zeros(batch * sz["c"], **kw), torch.empty(batch * sz["g"], **kw)
-        w, y = torch.zeros(batch * sz["g"], **kw), torch.zeros(batch * sz["g"], **kw)
+        w, y = torch.zeros(lo.numel(), **kw), torch.zeros(lo.numel(), **kw)
         res = torch.zeros(batch, 2, **kw)
-        ctx.shapes = tuple(t.shape for t in (G, C, g, c, lo, hi))
-        G, C, g, c, lo, hi, rho = (t.detach().reshape(-1) for t in (G, C, g, c, lo, hi, rho))
+        ctx.shapes = tuple(None if t is None else t.shape for t in (G, C, g, c, E, lo, hi, kappa))
+        G, C, g, c, E, lo, hi, kappa, rho = (None if t is None else t.detach().reshape(-1)
+                                             for t in (G, C, g, c, E, lo, hi, kappa, rho))
         Cp = C if N > 1 else None
-        solver.kkt_step_reg(nx, nu, N, batch, G, Cp, g, c, rho, S, gamma, Ginv, Pinv, lam, z, tol=tol, max_iter=max_iter)
-        gt = solver.admm_init(nx, nu, N, batch, g, lo, hi, rho, w, y)
+        sizes = (*dims, batch)
+        bounds = ((E,) if fam.rows else ()) + (lo, hi) + ((kappa,) if fam.soft else ())
+        if fam.rows:
+            Gt = solver.admm_lin_form(*sizes, G, E, rho)
+            solver.kkt_step(nx, nu, N, batch, Gt, Cp, g, c, S, gamma, Ginv, Pinv, lam, z, tol=tol, max_iter=max_iter)
+        else:
+            solver.kkt_step_reg(nx, nu, N, batch, G, Cp, g, c, rho, S, gamma, Ginv, Pinv, lam, z, tol=tol, max_iter=max_iter)
+        gt = getattr(solver, fam.init)(*sizes, g, *bounds, rho, w, y)
+        step = getattr(solver, fam.step)
         for _ in range(iters):
-            solver.admm_step(nx, nu, N, batch, Ginv, Cp, g, c, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=res, tol=tol,
-                             max_iter=max_iter)
-        ctx.save_for_backward(Ginv, S, Pinv, C, w, lam, y, rho)
-        ctx.args = (solver, nx, nu, N, batch, adj_iters, tol, max_iter)
+            step(*sizes, Ginv, Cp, g, c, *bounds, rho, S, Pinv, gamma, lam, z, w, y, gt, res=res, tol=tol, max_iter=max_iter)
+        out = z if fam.rows else w
+        ctx.save_for_backward(Ginv, S, Pinv, C, E, out, lam, y, kappa, rho)
+        ctx.args = (fam, solver, dims, batch, adj_iters, tol, max_iter)
         ctx.mark_non_differentiable(res)
-        return w, lam, res
+        return out, lam, res
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, gw, glam, _gres):
-        Ginv, S, Pinv, C, w, lam, yf, rho = ctx.saved_tensors
-        solver, nx, nu, N, batch, adj_iters, tol, max_iter = ctx.args
+    def backward(ctx, gout, glam, _gres):
+        Ginv, S, Pinv, C, E, x, lam, yf, kappa, rho = ctx.saved_tensors      # x: the forward output, w (box) or z (rows)
+        fam, solver, dims, batch, adj_iters, tol, max_iter = ctx.args
+        nx, nu, N = dims[0], dims[1], dims[-1]
         sz = _sizes(nx, nu, N)
         Cp = C if N > 1 else None
-        gz = torch.zeros_like(w) if gw is None else gw.contiguous().view(-1)
+        gz = torch.zeros_like(x) if gout is None else gout.contiguous().view(-1)
         nglam = torch.zeros_like(lam) if glam is None else -glam.contiguous().view(-1)
-        gamma, alam, az = torch.empty_like(lam), torch.zeros_like(lam), torch.empty_like(w)
-        wa, ya = torch.zeros_like(w), torch.zeros_like(w)
-        res = torch.empty(batch, 2, dtype=w.dtype, device=w.device)
-        need_G, need_C = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and N > 1
+        gamma, alam, az = torch.empty_like(lam), torch.zeros_like(lam), torch.empty_like(x)
+        wa, ya = torch.zeros_like(yf), torch.zeros_like(yf)
+        res = torch.empty(batch, 2, dtype=x.dtype, device=x.device)
+        need_G, need_C = ctx.needs_input_grad[8], ctx.needs_input_grad[9] and N > 1
         # (a problem with exactly zero cotangents: as in _KktSolve.backward -- its adjoint solves return NaN, its gradients are
         # exactly zero; the mask and the selects run in stream order)
-        live = ((gz.view(batch, -1) != 0).any(1) | (nglam.view(batch, -1) != 0).any(1)).view(batch, 1)
-
-        def keep(t):
-            return None if t is None else torch.where(live, t.view(batch, -1), t.new_zeros(())).view(-1)
-
-        gta = solver.admm_adjoint_init(nx, nu, N, batch, gz, yf, rho, wa, ya)
+        keep = _keep_live(gz, nglam, batch)
+        sizes = (*dims, batch)
+        rows = (E,) if fam.rows else ()
+        # soft: saturated entries / rows count as free from here on
+        ym = getattr(solver, fam.mask)(*sizes, yf, kappa, rho) if fam.soft else yf
+        gta = getattr(solver, fam.adj_init)(*sizes, gz, *rows, ym, rho, wa, ya)
+        adj_step = getattr(solver, fam.adj_step)
         for _ in range(adj_iters):
-            solver.admm_adjoint_step(nx, nu, N, batch, Ginv, Cp, gz, nglam, yf, rho, S, Pinv, gamma, alam, az, wa, ya, gta, res=res,
-                                     tol=tol, max_iter=max_iter)
-        glo, ghi = solver.admm_grad_bounds(nx, nu, N, batch, yf, rho, ya)
+            adj_step(*sizes, Ginv, Cp, gz, nglam, *rows, ym, rho, S, Pinv, gamma, alam, az, wa, ya, gta, res=res, tol=tol,
+                     max_iter=max_iter)
+        grad, gE, gkappa = getattr(solver, fam.grad), None, None
+        if fam.rows and fam.soft:
+            glo, ghi, gkappa, gE = grad(*sizes, x, az, E, yf, ya, kappa, rho)
+        elif fam.rows:
+            glo, ghi, gE = grad(*sizes, x, az, yf, ya, rho)
+        elif fam.soft:
+            glo, ghi, gkappa = grad(*sizes, yf, kappa, rho, ya, az)
+        else:
+            glo, ghi = grad(*sizes, yf, rho, ya)
+        ax = az if fam.rows else wa      # the adjoint's primal: its z where the output is z, its w where the output is w
         gG = gC = None
         if need_G or need_C:
-            gG = torch.empty(batch * sz["G"], dtype=w.dtype, device=w.device) if need_G else None
-            gC = torch.empty(batch * sz["C"], dtype=w.dtype, device=w.device) if need_C else None
-            solver.kkt_grad(nx, nu, N, batch, w, lam, wa, alam, gG=gG, gC=gC, want="")
-        out = [keep(t) for t in (gG, gC, wa, -alam, glo, ghi)]
-        if ctx.needs_input_grad[1] and N == 1:
-            out[1] = torch.zeros(batch * sz["C"], dtype=w.dtype, device=w.device)
-        grads = [t if t is None else t.view(s) for t, s in zip(out, ctx.shapes)]
-        return (*grads, None) + (None,) * 9
+            gG = torch.empty(batch * sz["G"], dtype=x.dtype, device=x.device) if need_G else None
+            gC = torch.empty(batch * sz["C"], dtype=x.dtype, device=x.device) if need_C else None
+            solver.kkt_grad(nx, nu, N, batch, x, lam, ax, alam, gG=gG, gC=gC, want="")
+        gG, gC, gg, gc, gE, glo, ghi, gkappa = (keep(t) for t in (gG, gC, ax, -alam, gE, glo, ghi, gkappa))
+        if ctx.needs_input_grad[9] and N == 1:
+            gC = torch.zeros(batch * sz["C"], dtype=x.dtype, device=x.device)
+        grads = [t if t is None else t.view(s) for t, s in zip((gG, gC, gg, gc, gE, glo, ghi, gkappa), ctx.shapes)]
+        return (None,) * 8 + (*grads, None)
+
+
+def _check_qp(fn, solver, nx, nu, N, rows, named, iters, adj_iters):
+    """The validation the four ADMM QP functions share; fn: the caller's name, rows: (mx, mu) or None, named: (name, tensor) pairs.
+    Returns the batch."""
+    if not isinstance(solver, binding.Solver):
+        raise TypeError(f"{fn}: solver is a binding.Solver")
+    sz = _sizes(nx, nu, N)
+    g = dict(named)["g"]
+    for name, t in named:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == g.dtype):
+            raise ValueError(f"{fn}: {name} must be a contiguous device tensor of g's dtype")
+    if g.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{fn}: unsupported dtype {g.dtype}")
+    nw, ne = sz["g"], 0
+    if rows is not None:
+        mx, mu = rows
+        nw, ne = (mx + mu) * N - mu, (mx * nx + mu * nu) * N - mu * nu
+        if nw <= 0:
+            raise ValueError(f"{fn}: no rows at all")
+    if g.numel() == 0 or g.numel() % sz["g"]:
+        raise ValueError(f"{fn}: g is not a whole number of problems")
+    batch = g.numel() // sz["g"]
+    want = {"G": batch * sz["G"], "C": batch * sz["C"], "g": batch * sz["g"], "c": batch * sz["c"], "E": batch * ne, "lo": batch * nw,
+            "hi": batch * nw, "kappa": batch * nw, "rho": batch}
+    for name, t in named:
+        if t.numel() != want[name]:
+            raise ValueError(f"{fn}: {name} has {t.numel()} elements, the layout takes {want[name]}")
+    if int(iters) < 1 or int(adj_iters) < 1:
+        raise ValueError(f"{fn}: iters and adj_iters are at least 1")
+    return batch
 
 
 def box_qp_solve(solver, nx, nu, N, G, C, g, c, lo, hi, rho, iters, adj_iters, tol=1e-6, max_iter=25):
@@ -172,88 +254,9 @@ def box_qp_solve(solver, nx, nu, N, G, C, g, c, lo, hi, rho, iters, adj_iters, t
     dl/dlo_i or dl/dhi_i carries the adjoint's multiplier.  An entry that sits on its bound with y_i = 0 (weakly active) counts as
     free.  A forward loop that has not converged leaves whatever mask y holds.  tol, max_iter: the PCG settings of every solve.
     A problem whose rows of dl/dw and dl/dlambda are exactly zero gets exactly zero gradients (as in kkt_solve)."""
-    if not isinstance(solver, binding.Solver):
-        raise TypeError("box_qp_solve: solver is a binding.Solver")
-    sz = _sizes(nx, nu, N)
-    for name, t in (("G", G), ("C", C), ("g", g), ("c", c), ("lo", lo), ("hi", hi), ("rho", rho)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == g.dtype):
-            raise ValueError(f"box_qp_solve: {name} must be a contiguous device tensor of g's dtype")
-    if g.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"box_qp_solve: unsupported dtype {g.dtype}")
-    if g.numel() == 0 or g.numel() % sz["g"]:
-        raise ValueError("box_qp_solve: g is not a whole number of problems")
-    batch = g.numel() // sz["g"]
-    want = {"G": batch * sz["G"], "C": batch * sz["C"], "g": batch * sz["g"], "c": batch * sz["c"], "lo": batch * sz["g"],
-            "hi": batch * sz["g"], "rho": batch}
-    for name, t in (("G", G), ("C", C), ("c", c), ("lo", lo), ("hi", hi), ("rho", rho)):
-        if t.numel() != want[name]:
-            raise ValueError(f"box_qp_solve: {name} has {t.numel()} elements, the layout takes {want[name]}")
-    if int(iters) < 1 or int(adj_iters) < 1:
-        raise ValueError("box_qp_solve: iters and adj_iters are at least 1")
-    return _BoxQpSolve.apply(G, C, g, c, lo, hi, rho, solver, nx, nu, N, batch, int(iters), int(adj_iters), tol, max_iter)
-
-
-class _LinQpSolve(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, G, C, g, c, E, lo, hi, rho, solver, nx, nu, mx, mu, N, batch, iters, adj_iters, tol, max_iter):
-        sz = _sizes(nx, nu, N)
-        nw = (mx + mu) * N - mu
-        kw = dict(dtype=g.dtype, device=g.device)
-        S = torch.empty(batch * 3 * nx * nx * N, **kw)
-        Pinv, Ginv = torch.empty_like(S), torch.empty(batch * sz["G"], **kw)
-        gamma = torch.empty(batch * sz["c"], **kw)
-        lam, z = torch.zeros(batch * sz["c"], **kw), torch.empty(batch * sz["g"], **kw)
-        w, y = torch.zeros(batch * nw, **kw), torch.zeros(batch * nw, **kw)
-        res = torch.zeros(batch, 2, **kw)
-        ctx.shapes = tuple(t.shape for t in (G, C, g, c, E, lo, hi))
-        G, C, g, c, E, lo, hi, rho = (t.detach().reshape(-1) for t in (G, C, g, c, E, lo, hi, rho))
-        Cp = C if N > 1 else None
-        Gt = solver.admm_lin_form(nx, nu, mx, mu, N, batch, G, E, rho)
-        solver.kkt_step(nx, nu, N, batch, Gt, Cp, g, c, S, gamma, Ginv, Pinv, lam, z, tol=tol, max_iter=max_iter)
-        gt = solver.admm_lin_init(nx, nu, mx, mu, N, batch, g, E, lo, hi, rho, w, y)
-        for _ in range(iters):
-            solver.admm_lin_step(nx, nu, mx, mu, N, batch, Ginv, Cp, g, c, E, lo, hi, rho, S, Pinv, gamma, lam, z, w, y, gt, res=res,
-                                 tol=tol, max_iter=max_iter)
-        ctx.save_for_backward(Ginv, S, Pinv, C, E, z, lam, y, rho)
-        ctx.args = (solver, nx, nu, mx, mu, N, batch, adj_iters, tol, max_iter)
-        ctx.mark_non_differentiable(res)
-        return z, lam, res
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gzz, glam, _gres):
-        Ginv, S, Pinv, C, E, z, lam, yf, rho = ctx.saved_tensors
-        solver, nx, nu, mx, mu, N, batch, adj_iters, tol, max_iter = ctx.args
-        sz = _sizes(nx, nu, N)
-        Cp = C if N > 1 else None
-        gz = torch.zeros_like(z) if gzz is None else gzz.contiguous().view(-1)
-        nglam = torch.zeros_like(lam) if glam is None else -glam.contiguous().view(-1)
-        gamma, alam, az = torch.empty_like(lam), torch.zeros_like(lam), torch.empty_like(z)
-        wa, ya = torch.zeros_like(yf), torch.zeros_like(yf)
-        res = torch.empty(batch, 2, dtype=z.dtype, device=z.device)
-        need_G, need_C = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and N > 1
-        # (a problem with exactly zero cotangents: as in _KktSolve.backward -- its adjoint solves return NaN, its gradients are
-        # exactly zero; the mask and the selects run in stream order)
-        live = ((gz.view(batch, -1) != 0).any(1) | (nglam.view(batch, -1) != 0).any(1)).view(batch, 1)
-
-        def keep(t):
-            return None if t is None else torch.where(live, t.view(batch, -1), t.new_zeros(())).view(-1)
-
-        gta = solver.admm_lin_adjoint_init(nx, nu, mx, mu, N, batch, gz, E, yf, rho, wa, ya)
-        for _ in range(adj_iters):
-            solver.admm_lin_adjoint_step(nx, nu, mx, mu, N, batch, Ginv, Cp, gz, nglam, E, yf, rho, S, Pinv, gamma, alam, az, wa, ya,
-                                         gta, res=res, tol=tol, max_iter=max_iter)
-        glo, ghi, gE = solver.admm_lin_grad(nx, nu, mx, mu, N, batch, z, az, yf, ya, rho)
-        gG = gC = None
-        if need_G or need_C:
-            gG = torch.empty(batch * sz["G"], dtype=z.dtype, device=z.device) if need_G else None
-            gC = torch.empty(batch * sz["C"], dtype=z.dtype, device=z.device) if need_C else None
-            solver.kkt_grad(nx, nu, N, batch, z, lam, az, alam, gG=gG, gC=gC, want="")
-        out = [keep(t) for t in (gG, gC, az, -alam, gE, glo, ghi)]
-        if ctx.needs_input_grad[1] and N == 1:
-            out[1] = torch.zeros(batch * sz["C"], dtype=z.dtype, device=z.device)
-        grads = [t if t is None else t.view(s) for t, s in zip(out, ctx.shapes)]
-        return (*grads, None) + (None,) * 11
+    named = (("G", G), ("C", C), ("g", g), ("c", c), ("lo", lo), ("hi", hi), ("rho", rho))
+    batch = _check_qp("box_qp_solve", solver, nx, nu, N, None, named, iters, adj_iters)
+    return _AdmmQpSolve.apply(_BOX, solver, (nx, nu, N), batch, int(iters), int(adj_iters), tol, max_iter, G, C, g, c, None, lo, hi, None, rho)
 
 
 def lin_qp_solve(solver, nx, nu, mx, mu, N, G, C, g, c, E, lo, hi, rho, iters, adj_iters, tol=1e-6, max_iter=25):
@@ -272,90 +275,10 @@ def lin_qp_solve(solver, nx, nu, mx, mu, N, G, C, g, c, E, lo, hi, rho, iters, a
     The active set is the sign pattern of the forward y: row r is active iff y_r != 0 (no threshold); a row that sits on its bound
     with y_r = 0 (weakly active) counts as free.  A forward loop that has not converged leaves whatever mask y holds.  tol, max_iter:
     the PCG settings of every solve.  A problem whose rows of dl/dz and dl/dlambda are exactly zero gets exactly zero gradients."""
-    if not isinstance(solver, binding.Solver):
-        raise TypeError("lin_qp_solve: solver is a binding.Solver")
-    sz = _sizes(nx, nu, N)
-    nw, ne = (mx + mu) * N - mu, (mx * nx + mu * nu) * N - mu * nu
-    for name, t in (("G", G), ("C", C), ("g", g), ("c", c), ("E", E), ("lo", lo), ("hi", hi), ("rho", rho)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == g.dtype):
-            raise ValueError(f"lin_qp_solve: {name} must be a contiguous device tensor of g's dtype")
-    if g.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"lin_qp_solve: unsupported dtype {g.dtype}")
-    if nw <= 0:
-        raise ValueError("lin_qp_solve: no rows at all")
-    if g.numel() == 0 or g.numel() % sz["g"]:
-        raise ValueError("lin_qp_solve: g is not a whole number of problems")
-    batch = g.numel() // sz["g"]
-    want = {"G": batch * sz["G"], "C": batch * sz["C"], "c": batch * sz["c"], "E": batch * ne, "lo": batch * nw, "hi": batch * nw,
-            "rho": batch}
-    for name, t in (("G", G), ("C", C), ("c", c), ("E", E), ("lo", lo), ("hi", hi), ("rho", rho)):
-        if t.numel() != want[name]:
-            raise ValueError(f"lin_qp_solve: {name} has {t.numel()} elements, the layout takes {want[name]}")
-    if int(iters) < 1 or int(adj_iters) < 1:
-        raise ValueError("lin_qp_solve: iters and adj_iters are at least 1")
-    return _LinQpSolve.apply(G, C, g, c, E, lo, hi, rho, solver, nx, nu, mx, mu, N, batch, int(iters), int(adj_iters), tol, max_iter)
-
-
-class _SoftBoxQpSolve(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, G, C, g, c, lo, hi, kappa, rho, solver, nx, nu, N, batch, iters, adj_iters, tol, max_iter):
-        sz = _sizes(nx, nu, N)
-        kw = dict(dtype=g.dtype, device=g.device)
-        S = torch.empty(batch * 3 * nx * nx * N, **kw)
-        Pinv, Ginv = torch.empty_like(S), torch.empty(batch * sz["G"], **kw)
-        gamma = torch.empty(batch * sz["c"], **kw)
-        lam, z = torch.zeros(batch * sz["c"], **kw), torch.empty(batch * sz["g"], **kw)
-        w, y = torch.zeros(batch * sz["g"], **kw), torch.zeros(batch * sz["g"], **kw)
-        res = torch.zeros(batch, 2, **kw)
-        ctx.shapes = tuple(t.shape for t in (G, C, g, c, lo, hi, kappa))
-        G, C, g, c, lo, hi, kappa, rho = (t.detach().reshape(-1) for t in (G, C, g, c, lo, hi, kappa, rho))
-        Cp = C if N > 1 else None
-        solver.kkt_step_reg(nx, nu, N, batch, G, Cp, g, c, rho, S, gamma, Ginv, Pinv, lam, z, tol=tol, max_iter=max_iter)
-        gt = solver.admm_soft_init(nx, nu, N, batch, g, lo, hi, kappa, rho, w, y)
-        for _ in range(iters):
-            solver.admm_soft_step(nx, nu, N, batch, Ginv, Cp, g, c, lo, hi, kappa, rho, S, Pinv, gamma, lam, z, w, y, gt, res=res, tol=tol,
-                                  max_iter=max_iter)
-        ctx.save_for_backward(Ginv, S, Pinv, C, w, lam, y, kappa, rho)
-        ctx.args = (solver, nx, nu, N, batch, adj_iters, tol, max_iter)
-        ctx.mark_non_differentiable(res)
-        return w, lam, res
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gw, glam, _gres):
-        Ginv, S, Pinv, C, w, lam, yf, kappa, rho = ctx.saved_tensors
-        solver, nx, nu, N, batch, adj_iters, tol, max_iter = ctx.args
-        sz = _sizes(nx, nu, N)
-        Cp = C if N > 1 else None
-        gz = torch.zeros_like(w) if gw is None else gw.contiguous().view(-1)
-        nglam = torch.zeros_like(lam) if glam is None else -glam.contiguous().view(-1)
-        gamma, alam, az = torch.empty_like(lam), torch.zeros_like(lam), torch.empty_like(w)
-        wa, ya = torch.zeros_like(w), torch.zeros_like(w)
-        res = torch.empty(batch, 2, dtype=w.dtype, device=w.device)
-        need_G, need_C = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and N > 1
-        # (a problem with exactly zero cotangents: as in _KktSolve.backward -- its adjoint solves return NaN, its gradients are
-        # exactly zero; the mask and the selects run in stream order)
-        live = ((gz.view(batch, -1) != 0).any(1) | (nglam.view(batch, -1) != 0).any(1)).view(batch, 1)
-
-        def keep(t):
-            return None if t is None else torch.where(live, t.view(batch, -1), t.new_zeros(())).view(-1)
-
-        ym = solver.admm_soft_mask(nx, nu, N, batch, yf, kappa, rho)       # saturated entries count as free from here on
-        gta = solver.admm_adjoint_init(nx, nu, N, batch, gz, ym, rho, wa, ya)
-        for _ in range(adj_iters):
-            solver.admm_adjoint_step(nx, nu, N, batch, Ginv, Cp, gz, nglam, ym, rho, S, Pinv, gamma, alam, az, wa, ya, gta, res=res,
-                                     tol=tol, max_iter=max_iter)
-        glo, ghi, gkappa = solver.admm_soft_grad_bounds(nx, nu, N, batch, yf, kappa, rho, ya, az)
-        gG = gC = None
-        if need_G or need_C:
-            gG = torch.empty(batch * sz["G"], dtype=w.dtype, device=w.device) if need_G else None
-            gC = torch.empty(batch * sz["C"], dtype=w.dtype, device=w.device) if need_C else None
-            solver.kkt_grad(nx, nu, N, batch, w, lam, wa, alam, gG=gG, gC=gC, want="")
-        out = [keep(t) for t in (gG, gC, wa, -alam, glo, ghi, gkappa)]
-        if ctx.needs_input_grad[1] and N == 1:
-            out[1] = torch.zeros(batch * sz["C"], dtype=w.dtype, device=w.device)
-        grads = [t if t is None else t.view(s) for t, s in zip(out, ctx.shapes)]
-        return (*grads, None) + (None,) * 9
+    named = (("G", G), ("C", C), ("g", g), ("c", c), ("E", E), ("lo", lo), ("hi", hi), ("rho", rho))
+    batch = _check_qp("lin_qp_solve", solver, nx, nu, N, (mx, mu), named, iters, adj_iters)
+    return _AdmmQpSolve.apply(_LIN, solver, (nx, nu, mx, mu, N), batch, int(iters), int(adj_iters), tol, max_iter, G, C, g, c, E, lo, hi, None,
+                              rho)
 
 
 def soft_box_qp_solve(solver, nx, nu, N, G, C, g, c, lo, hi, kappa, rho, iters, adj_iters, tol=1e-6, max_iter=25):
@@ -371,90 +294,10 @@ def soft_box_qp_solve(solver, nx, nu, N, G, C, g, c, lo, hi, kappa, rho, iters, 
     carries the adjoint's multiplier, dl/dg_i = 0); |y_i| = kappa_i / rho saturated, beyond its bound with the constant multiplier
     +-kappa_i -- free in the adjoint, dl/dkappa_i = sign(y_i) a_z,i, dl/dlo_i = dl/dhi_i = 0.  dl/dkappa is exactly zero everywhere
     else, so where kappa = +Inf.  A problem whose rows of dl/dw and dl/dlambda are exactly zero gets exactly zero gradients."""
-    if not isinstance(solver, binding.Solver):
-        raise TypeError("soft_box_qp_solve: solver is a binding.Solver")
-    sz = _sizes(nx, nu, N)
     named = (("G", G), ("C", C), ("g", g), ("c", c), ("lo", lo), ("hi", hi), ("kappa", kappa), ("rho", rho))
-    for name, t in named:
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == g.dtype):
-            raise ValueError(f"soft_box_qp_solve: {name} must be a contiguous device tensor of g's dtype")
-    if g.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"soft_box_qp_solve: unsupported dtype {g.dtype}")
-    if g.numel() == 0 or g.numel() % sz["g"]:
-        raise ValueError("soft_box_qp_solve: g is not a whole number of problems")
-    batch = g.numel() // sz["g"]
-    want = {"G": batch * sz["G"], "C": batch * sz["C"], "g": batch * sz["g"], "c": batch * sz["c"], "lo": batch * sz["g"],
-            "hi": batch * sz["g"], "kappa": batch * sz["g"], "rho": batch}
-    for name, t in named:
-        if t.numel() != want[name]:
-            raise ValueError(f"soft_box_qp_solve: {name} has {t.numel()} elements, the layout takes {want[name]}")
-    if int(iters) < 1 or int(adj_iters) < 1:
-        raise ValueError("soft_box_qp_solve: iters and adj_iters are at least 1")
-    return _SoftBoxQpSolve.apply(G, C, g, c, lo, hi, kappa, rho, solver, nx, nu, N, batch, int(iters), int(adj_iters), tol, max_iter)
-
-
-class _SoftLinQpSolve(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, G, C, g, c, E, lo, hi, kappa, rho, solver, nx, nu, mx, mu, N, batch, iters, adj_iters, tol, max_iter):
-        sz = _sizes(nx, nu, N)
-        nw = (mx + mu) * N - mu
-        kw = dict(dtype=g.dtype, device=g.device)
-        S = torch.empty(batch * 3 * nx * nx * N, **kw)
-        Pinv, Ginv = torch.empty_like(S), torch.empty(batch * sz["G"], **kw)
-        gamma = torch.empty(batch * sz["c"], **kw)
-        lam, z = torch.zeros(batch * sz["c"], **kw), torch.empty(batch * sz["g"], **kw)
-        w, y = torch.zeros(batch * nw, **kw), torch.zeros(batch * nw, **kw)
-        res = torch.zeros(batch, 2, **kw)
-        ctx.shapes = tuple(t.shape for t in (G, C, g, c, E, lo, hi, kappa))
-        G, C, g, c, E, lo, hi, kappa, rho = (t.detach().reshape(-1) for t in (G, C, g, c, E, lo, hi, kappa, rho))
-        Cp = C if N > 1 else None
-        Gt = solver.admm_lin_form(nx, nu, mx, mu, N, batch, G, E, rho)
-        solver.kkt_step(nx, nu, N, batch, Gt, Cp, g, c, S, gamma, Ginv, Pinv, lam, z, tol=tol, max_iter=max_iter)
-        gt = solver.admm_lin_soft_init(nx, nu, mx, mu, N, batch, g, E, lo, hi, kappa, rho, w, y)
-        for _ in range(iters):
-            solver.admm_lin_soft_step(nx, nu, mx, mu, N, batch, Ginv, Cp, g, c, E, lo, hi, kappa, rho, S, Pinv, gamma, lam, z, w, y, gt,
-                                      res=res, tol=tol, max_iter=max_iter)
-        ctx.save_for_backward(Ginv, S, Pinv, C, E, z, lam, y, kappa, rho)
-        ctx.args = (solver, nx, nu, mx, mu, N, batch, adj_iters, tol, max_iter)
-        ctx.mark_non_differentiable(res)
-        return z, lam, res
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gzz, glam, _gres):
-        Ginv, S, Pinv, C, E, z, lam, yf, kappa, rho = ctx.saved_tensors
-        solver, nx, nu, mx, mu, N, batch, adj_iters, tol, max_iter = ctx.args
-        sz = _sizes(nx, nu, N)
-        Cp = C if N > 1 else None
-        gz = torch.zeros_like(z) if gzz is None else gzz.contiguous().view(-1)
-        nglam = torch.zeros_like(lam) if glam is None else -glam.contiguous().view(-1)
-        gamma, alam, az = torch.empty_like(lam), torch.zeros_like(lam), torch.empty_like(z)
-        wa, ya = torch.zeros_like(yf), torch.zeros_like(yf)
-        res = torch.empty(batch, 2, dtype=z.dtype, device=z.device)
-        need_G, need_C = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and N > 1
-        # (a problem with exactly zero cotangents: as in _KktSolve.backward -- its adjoint solves return NaN, its gradients are
-        # exactly zero; the mask and the selects run in stream order)
-        live = ((gz.view(batch, -1) != 0).any(1) | (nglam.view(batch, -1) != 0).any(1)).view(batch, 1)
-
-        def keep(t):
-            return None if t is None else torch.where(live, t.view(batch, -1), t.new_zeros(())).view(-1)
-
-        ym = solver.admm_lin_soft_mask(nx, nu, mx, mu, N, batch, yf, kappa, rho)       # saturated rows count as free from here on
-        gta = solver.admm_lin_adjoint_init(nx, nu, mx, mu, N, batch, gz, E, ym, rho, wa, ya)
-        for _ in range(adj_iters):
-            solver.admm_lin_adjoint_step(nx, nu, mx, mu, N, batch, Ginv, Cp, gz, nglam, E, ym, rho, S, Pinv, gamma, alam, az, wa, ya,
-                                         gta, res=res, tol=tol, max_iter=max_iter)
-        glo, ghi, gkappa, gE = solver.admm_lin_soft_grad(nx, nu, mx, mu, N, batch, z, az, E, yf, ya, kappa, rho)
-        gG = gC = None
-        if need_G or need_C:
-            gG = torch.empty(batch * sz["G"], dtype=z.dtype, device=z.device) if need_G else None
-            gC = torch.empty(batch * sz["C"], dtype=z.dtype, device=z.device) if need_C else None
-            solver.kkt_grad(nx, nu, N, batch, z, lam, az, alam, gG=gG, gC=gC, want="")
-        out = [keep(t) for t in (gG, gC, az, -alam, gE, glo, ghi, gkappa)]
-        if ctx.needs_input_grad[1] and N == 1:
-            out[1] = torch.zeros(batch * sz["C"], dtype=z.dtype, device=z.device)
-        grads = [t if t is None else t.view(s) for t, s in zip(out, ctx.shapes)]
-        return (*grads, None) + (None,) * 11
+    batch = _check_qp("soft_box_qp_solve", solver, nx, nu, N, None, named, iters, adj_iters)
+    return _AdmmQpSolve.apply(_SOFT_BOX, solver, (nx, nu, N), batch, int(iters), int(adj_iters), tol, max_iter, G, C, g, c, None, lo, hi, kappa,
+                              rho)
 
 
 def soft_lin_qp_solve(solver, nx, nu, mx, mu, N, G, C, g, c, E, lo, hi, kappa, rho, iters, adj_iters, tol=1e-6, max_iter=25):
@@ -471,30 +314,10 @@ def soft_lin_qp_solve(solver, nx, nu, mx, mu, N, G, C, g, c, E, lo, hi, kappa, r
     saturated, beyond its bound with the constant multiplier +-kappa_r -- free in the adjoint, dl/dkappa_r = sign(y_r) (E a_z)_r,
     dl/dE(r, .) = rho y_r a_z', dl/dlo_r = dl/dhi_r = 0.  dl/dkappa is exactly zero everywhere else, so where kappa = +Inf.  A problem
     whose rows of dl/dz and dl/dlambda are exactly zero gets exactly zero gradients."""
-    if not isinstance(solver, binding.Solver):
-        raise TypeError("soft_lin_qp_solve: solver is a binding.Solver")
-    sz = _sizes(nx, nu, N)
-    nw, ne = (mx + mu) * N - mu, (mx * nx + mu * nu) * N - mu * nu
     named = (("G", G), ("C", C), ("g", g), ("c", c), ("E", E), ("lo", lo), ("hi", hi), ("kappa", kappa), ("rho", rho))
-    for name, t in named:
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == g.dtype):
-            raise ValueError(f"soft_lin_qp_solve: {name} must be a contiguous device tensor of g's dtype")
-    if g.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"soft_lin_qp_solve: unsupported dtype {g.dtype}")
-    if nw <= 0:
-        raise ValueError("soft_lin_qp_solve: no rows at all")
-    if g.numel() == 0 or g.numel() % sz["g"]:
-        raise ValueError("soft_lin_qp_solve: g is not a whole number of problems")
-    batch = g.numel() // sz["g"]
-    want = {"G": batch * sz["G"], "C": batch * sz["C"], "g": batch * sz["g"], "c": batch * sz["c"], "E": batch * ne, "lo": batch * nw,
-            "hi": batch * nw, "kappa": batch * nw, "rho": batch}
-    for name, t in named:
-        if t.numel() != want[name]:
-            raise ValueError(f"soft_lin_qp_solve: {name} has {t.numel()} elements, the layout takes {want[name]}")
-    if int(iters) < 1 or int(adj_iters) < 1:
-        raise ValueError("soft_lin_qp_solve: iters and adj_iters are at least 1")
-    return _SoftLinQpSolve.apply(G, C, g, c, E, lo, hi, kappa, rho, solver, nx, nu, mx, mu, N, batch, int(iters), int(adj_iters), tol,
-                                 max_iter)
+    batch = _check_qp("soft_lin_qp_solve", solver, nx, nu, N, (mx, mu), named, iters, adj_iters)
+    return _AdmmQpSolve.apply(_SOFT_LIN, solver, (nx, nu, mx, mu, N), batch, int(iters), int(adj_iters), tol, max_iter, G, C, g, c, E, lo, hi,
+                              kappa, rho)
 
 
 def kkt_solve(solver, nx, nu, N, G, C, g, c, rho=None, shared=False, tol=1e-6, max_iter=25):

@@ -21,7 +21,7 @@
 // what a CU's share of the memory system takes -- so the stores stay the bound and the rows are not re-laid out in LDS.
 //
 // SOFT (gbdpcg_admm_lin_soft_grad_*, a compile-time switch; the hard instantiation holds nothing of it): the rows of the soft QP,
-// whose forward y splits them into free, held and saturated (admm_soft_grad.hip).  With theta_r = kappa_r / rho_b (the division of
+// whose forward y splits them into free, held and saturated (admm_box_grad.hip).  With theta_r = kappa_r / rho_b (the division of
 // soft_clip, once per row into a fifth LDS piece) and sat = |yf_r| >= theta_r:
 //     glo_r = (yf_r < 0 && !sat) ? -(rho_b ya_r) : +0      ghi_r likewise with > 0         the lines of admm_soft_grad_bounds_kernel
 //     gE(r, j): the lines above with the UNMASKED yf -- a saturated row keeps rho yf_r az_j (its ya_r is 0 behind the masked adjoint)

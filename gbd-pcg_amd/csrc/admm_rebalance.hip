@@ -16,35 +16,22 @@
 // problem stride; r, s and rho are uniform loads in front of every store, so they go through the scalar cache.  No LDS, no atomics,
 // nothing initialised beforehand.  One lane writes rho' and e behind a barrier, when every lane that uses rho has stored what it
 // computed from it.  res is read, never written.  The arrays of a problem start at the same offset b len, so they are misaligned
-// alike: with every base 16-byte aligned (vec != 0, decided by the host) a scalar head, 16-byte loads and stores, a scalar tail;
-// otherwise every element goes through the scalar form.  Same operations per element either way: same bits.
+// alike: with every base 16-byte aligned (vec != 0, decided by the host) a scalar head, 16-byte loads and stores, a scalar tail
+// (for_each_split in elementwise_split.hpp); otherwise every element goes through the scalar form.  Same operations per element
+// either way: same bits.
+#include "elementwise_split.hpp"
 #include "ieee_once.hpp"
 #include "internal.hpp"
 
 namespace gbdpcg {
-
-namespace {
-
-template <typename T> struct RebalanceVec;
-template <> struct RebalanceVec<float> {
-    static constexpr uint32_t N = 4;
-    typedef float type __attribute__((ext_vector_type(4)));
-};
-template <> struct RebalanceVec<double> {
-    static constexpr uint32_t N = 2;
-    typedef double type __attribute__((ext_vector_type(2)));
-};
-
-}  // namespace
 
 template <typename T, bool BOX>
 __global__ __launch_bounds__(256) void admm_rebalance_kernel(uint64_t len, uint32_t vec, const T *g, const T *res, T *rho, const T *w,
                                                              T *y, T *gt, T ratio, T tau, T inv_tau, T rho_min, T rho_max,
                                                              int32_t shift, int32_t *expo)
 {
-    using V = typename RebalanceVec<T>::type;
-    constexpr uint32_t VN = RebalanceVec<T>::N;
-    const uint32_t prob = blockIdx.x, tid = threadIdx.x, threads = blockDim.x;
+    using V = typename Vec16<T>::type;
+    const uint32_t prob = blockIdx.x;
     const uint64_t off = (uint64_t)prob * len;   // 64-bit problem stride
     const T r = res[2 * (uint64_t)prob], s = res[2 * (uint64_t)prob + 1], rh = rho[prob];
 
@@ -62,49 +49,41 @@ __global__ __launch_bounds__(256) void admm_rebalance_kernel(uint64_t len, uint3
         if constexpr (BOX) g += off, w += off, gt += off;
         const bool move = e != 0;
 
-        auto scalar = [&](uint64_t i) {
-            T yi = y[i];
-            if (move) {
-                yi = yi * scale;
-                y[i] = yi;
-            }
-            if constexpr (BOX) {
-                const T t = w[i] - yi;
-                gt[i] = fma_once(-rn, t, g[i]);
-            }
-        };
-
-        uint64_t head = 0, body = 0;   // elements in front of the first 16-byte boundary, 16-byte groups behind it
-        if (vec) {
-            head = (VN - (uint32_t)(off % VN)) % VN;
-            if (head > len) head = len;
-            body = (len - head) / VN;
-        }
-        if (tid < head) scalar(tid);
-        for (uint64_t q = tid; q < body; q += threads) {
-            const uint64_t i = head + q * VN;
-            V yv = *reinterpret_cast<const V *>(y + i);
-            if (move) {
-#pragma unroll
-                for (uint32_t k = 0; k < VN; ++k) yv[k] = yv[k] * scale;
-                *reinterpret_cast<V *>(y + i) = yv;
-            }
-            if constexpr (BOX) {
-                const V wv = *reinterpret_cast<const V *>(w + i), gv = *reinterpret_cast<const V *>(g + i);
-                V tv;
-#pragma unroll
-                for (uint32_t k = 0; k < VN; ++k) {
-                    const T t = wv[k] - yv[k];
-                    tv[k] = fma_once(-rn, t, gv[k]);
+        for_each_split<T>(
+            vec, off, len,
+            [&](uint64_t i) {
+                T yi = y[i];
+                if (move) {
+                    yi = yi * scale;
+                    y[i] = yi;
                 }
-                *reinterpret_cast<V *>(gt + i) = tv;
-            }
-        }
-        for (uint64_t i = head + body * VN + tid; i < len; i += threads) scalar(i);   // the tail; all of it without vec
+                if constexpr (BOX) {
+                    const T t = w[i] - yi;
+                    gt[i] = fma_once(-rn, t, g[i]);
+                }
+            },
+            [&](uint64_t i) {
+                V yv = load16(y + i);
+                if (move) {
+#pragma unroll
+                    for (uint32_t k = 0; k < Vec16<T>::N; ++k) yv[k] = yv[k] * scale;
+                    store16(y + i, yv);
+                }
+                if constexpr (BOX) {
+                    const V wv = load16(w + i), gv = load16(g + i);
+                    V tv;
+#pragma unroll
+                    for (uint32_t k = 0; k < Vec16<T>::N; ++k) {
+                        const T t = wv[k] - yv[k];
+                        tv[k] = fma_once(-rn, t, gv[k]);
+                    }
+                    store16(gt + i, tv);
+                }
+            });
     }
 
     __syncthreads();   // every lane's stores, which needed rho, are behind it
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         rho[prob] = rn;
         expo[prob] = e;
     }
@@ -115,10 +94,7 @@ hipError_t launch_admm_rebalance(uint64_t len, uint32_t batch, const T *g, const
                                  uint32_t shift, T rho_min, T rho_max, int32_t *expo, hipStream_t s, bool box)
 {
     if (batch > 0x7fffffffu) return hipErrorInvalidValue;   // one workgroup per problem
-    uint32_t vec = reinterpret_cast<uintptr_t>(y) % 16 ? 0 : 1;
-    if (box)
-        for (const void *p : {(const void *)g, (const void *)w, (const void *)gt})
-            if (reinterpret_cast<uintptr_t>(p) % 16) vec = 0;
+    const uint32_t vec = box ? all_aligned({y, g, w, gt}) : all_aligned({y});
     const uint32_t threads = len <= 256 ? 64 : 256;
     const T tau = (T)(1u << shift), inv_tau = T(1) / tau;   // shift <= 16: both exact
     if (box)

@@ -79,7 +79,7 @@ template <typename T> struct AdmmOperands {
     const RowClasses *cones = nullptr;
     const T *kappa = nullptr;
     bool soft = false;
-    bool adjoint = false;   // gbdpcg_admm_lin_adjoint_*: hard linear rows, lo (and hi) hold yf, the forward y -- the mask of the active rows
+    bool adjoint = false;   // gbdpcg_admm_adjoint_*, gbdpcg_admm_lin_adjoint_*: hard bounds, lo (and hi) hold yf, the forward y -- the mask
 };
 
 // The forward point and the outputs of gbdpcg_kkt_backward_*: z has the layout of g, lambda that of c, gG / gC those of G / C (one
@@ -198,6 +198,21 @@ gbdpcg_status admm_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint
     return GBDPCG_OK;
 }
 
+// The adjoint of that update (the backward pass of the hard box QP: the forward y, yf, where lo, hi stand), one launch.  init:
+// gbdpcg_admm_adjoint_init_* -- d_az and d_res are not arguments.  Elementwise: no shape is refused.
+template <typename T>
+gbdpcg_status admm_adjoint_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_gz,
+                                       const T *d_yf, const T *d_rho, const T *d_az, T *d_wa, T *d_ya, T *d_gta, T *d_res, void *stream,
+                                       bool init)
+{
+    if (!h || !d_gz || !d_yf || !d_rho || !d_wa || !d_ya || !d_gta || (!init && (!d_az || !d_res)) || nx == 0 || nu == 0 || N == 0 ||
+        batch == 0)
+        return GBDPCG_ERR_INVALID;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_admm_adjoint_update<T>(nx, nu, N, batch, d_gz, d_yf, d_rho, d_az, d_wa, d_ya, d_gta, d_res, (hipStream_t)stream, init));
+    return GBDPCG_OK;
+}
+
 // What the stage-wise rows of gbdpcg_admm_lin_* and gbdpcg_admm_soc_* are refused for, before anything is written.  INVALID: no
 // rows at all (mx = mu = 0, or mx = 0 with N = 1), row classes that do not fit the blocks (lx > mx, lu > mu, cone rows with q = 0
 // or not a whole number of cones).  UNSUPPORTED, behind every INVALID: more than 64 rows per block, a knot that does not fit the
@@ -261,7 +276,8 @@ gbdpcg_status admm_step_refusal(gbdpcg_handle_t h, const KktOperands<T> &k, cons
 
 // One iteration of ADMM on a kept factorisation of G + rho I (box) or G + rho E'E (rows): kkt_resolve_impl with the shifted
 // gradient a.gt in the place of g (the gamma launch and the recovery launch read the same gt), then the update, which alone reads
-// k.g, on the same stream.
+// k.g, on the same stream.  a.adjoint: the adjoint iteration -- k.g is gz, k.c is nglam, k.z is az, a.lo is yf (a.hi too: the refusal
+// of the step is the refusal there), a.w, a.y, a.gt, a.res the adjoint's splitting state.
 template <typename T>
 gbdpcg_status admm_step_impl(gbdpcg_handle_t h, const KktOperands<T> &k, const AdmmOperands<T> &a, const PcgArgs<T> &p, hipStream_t stream)
 {
@@ -272,26 +288,12 @@ gbdpcg_status admm_step_impl(gbdpcg_handle_t h, const KktOperands<T> &k, const A
     st = kkt_resolve_impl<T>(h, shifted, p, stream);
     if (st != GBDPCG_OK) return st;
     if (a.rows) return admm_rows_update_impl<T>(h, p.n, k.nu, p.N, p.batch, k.g, a, k.z, stream, false, k.shared);
+    if (a.adjoint) return admm_adjoint_update_impl<T>(h, p.n, k.nu, p.N, p.batch, k.g, a.lo, a.rho, k.z, a.w, a.y, a.gt, a.res, stream, false);
     return admm_update_impl<T>(h, p.n, k.nu, p.N, p.batch, k.g, a.lo, a.hi, a.rho, k.z, a.w, a.y, a.gt, a.res, stream, false, a.kappa,
                                a.soft);
 }
 
-// ---- the backward pass of the hard box QP (admm_adjoint.hip): the box family with the forward y (yf) where lo, hi stand
-// The adjoint update, one launch.  init: gbdpcg_admm_adjoint_init_* -- d_az and d_res are not arguments.  Elementwise: no shape is
-// refused.
-template <typename T>
-gbdpcg_status admm_adjoint_update_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_gz,
-                                       const T *d_yf, const T *d_rho, const T *d_az, T *d_wa, T *d_ya, T *d_gta, T *d_res, void *stream,
-                                       bool init)
-{
-    if (!h || !d_gz || !d_yf || !d_rho || !d_wa || !d_ya || !d_gta || (!init && (!d_az || !d_res)) || nx == 0 || nu == 0 || N == 0 ||
-        batch == 0)
-        return GBDPCG_ERR_INVALID;
-    DEVICE_SCOPE(h);
-    HIP_TRY(h, launch_admm_adjoint_update<T>(nx, nu, N, batch, d_gz, d_yf, d_rho, d_az, d_wa, d_ya, d_gta, d_res, (hipStream_t)stream, init));
-    return GBDPCG_OK;
-}
-
+// ---- the gradient launches of the backward passes (admm_box_grad.hip, admm_lin_grad.hip)
 // The gradients in the bounds from the adjoint's y, one launch, elementwise.
 template <typename T>
 gbdpcg_status admm_grad_bounds_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *d_yf, const T *d_rho,
@@ -321,7 +323,7 @@ gbdpcg_status admm_lin_grad_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, ui
     return GBDPCG_OK;
 }
 
-// ---- the backward pass of the soft box and rows QPs (admm_soft_grad.hip, the SOFT instantiation of admm_lin_grad.hip): the mask
+// ---- the backward pass of the soft box and rows QPs (admm_box_grad.hip, the SOFT instantiation of admm_lin_grad.hip): the mask
 // that turns the forward y into the yf of the hard adjoint loops above, and the gradient launches that know of kappa.
 // The mask, one launch, elementwise.  rows: (mx, mu) and the rows' refusals; otherwise the layout of g.  d_ym == d_yf is refused
 // here, in front of everything else that could be: the unmasked yf is still needed behind the adjoint loop.
@@ -377,21 +379,6 @@ gbdpcg_status admm_lin_soft_grad_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t n
     HIP_TRY(h, launch_admm_lin_grad<T>(nx, nu, mx, mu, N, batch, d_z, d_az, d_yf, d_ya, d_rho, d_glo, d_ghi, d_gE, (hipStream_t)stream,
                                        d_E, d_kappa, d_gkappa));
     return GBDPCG_OK;
-}
-
-// One adjoint iteration: admm_step_impl with the adjoint update behind the solve.  k.g is gz, k.c is nglam, k.z is az; a.lo is yf
-// (a.hi too: the refusal of the box step is the refusal here), a.w, a.y, a.gt, a.res the adjoint's splitting state.
-template <typename T>
-gbdpcg_status admm_adjoint_step_impl(gbdpcg_handle_t h, const KktOperands<T> &k, const AdmmOperands<T> &a, const PcgArgs<T> &p,
-                                     hipStream_t stream)
-{
-    gbdpcg_status st = admm_step_refusal<T>(h, k, a, p);
-    if (st != GBDPCG_OK) return st;
-    KktOperands<T> shifted = k;
-    shifted.g = a.gt;
-    st = kkt_resolve_impl<T>(h, shifted, p, stream);
-    if (st != GBDPCG_OK) return st;
-    return admm_adjoint_update_impl<T>(h, p.n, k.nu, p.N, p.batch, k.g, a.lo, a.rho, k.z, a.w, a.y, a.gt, a.res, stream, false);
 }
 
 // ---- adaptive rho (admm_rebalance.hip): residual balancing in powers of two, and the iteration that refactors with the new rho
@@ -951,10 +938,10 @@ GBDPCG_ADMM_RESTEPS(admm_soft_restep)
         TYPE *d_alambda, TYPE *d_r, TYPE *d_p, TYPE tol, uint32_t max_iter, uint32_t *d_iters, uint8_t *d_max_iter_exit,            \
         TYPE *d_az, TYPE *d_wa, TYPE *d_ya, TYPE *d_gta, TYPE *d_res
 #define ADJOINT_STEP_SETUP(TYPE, SHARED)                                                                                            \
-    const AdmmOperands<TYPE> ad{d_yf, d_yf, d_rho, d_wa, d_ya, d_gta, d_res};                                                       \
+    const AdmmOperands<TYPE> ad{d_yf, d_yf, d_rho, d_wa, d_ya, d_gta, d_res, false, nullptr, 0, 0, nullptr, nullptr, false, true};  \
     const KktOperands<TYPE> k{nu, d_Ginv, d_C, d_gz, d_nglam, d_gamma, d_az, SHARED};                                               \
     const PcgArgs<TYPE> a = pcg_args<TYPE>(nx, N, batch, d_S, d_Pinv, d_gamma, d_alambda, d_r, d_p, tol, max_iter, d_iters, d_max_iter_exit);\
-    auto body = [&](hipStream_t s) { return admm_adjoint_step_impl<TYPE>(h, k, ad, a, s); };
+    auto body = [&](hipStream_t s) { return admm_step_impl<TYPE>(h, k, ad, a, s); };
 #define ADJOINT_STEP_REFUSE(TYPE)                                                                                                   \
     if (!out) return GBDPCG_ERR_INVALID;                                                                                            \
     *out = nullptr;                                                                                                                 \

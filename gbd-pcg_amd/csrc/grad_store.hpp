@@ -1,24 +1,16 @@
-// grad_store.hpp -- what the write-bound gradient launches share (kkt_grad.hip, admm_lin_grad.hip): the 16-byte vector of a type,
-// index divisions as multiplications by reciprocals the host prepared, and the store of one contiguous range of outputs.
+// grad_store.hpp -- what the write-bound gradient launches share (kkt_grad.hip, admm_lin_grad.hip): index divisions as
+// multiplications by reciprocals the host prepared, and the store of one contiguous range of outputs in 16-byte vectors.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "elementwise_split.hpp"
+
 namespace gbdpcg {
 
 namespace {
-
-template <typename T> struct GradVec;
-template <> struct GradVec<float> {
-    static constexpr uint32_t N = 4;
-    typedef float type __attribute__((ext_vector_type(4)));
-};
-template <> struct GradVec<double> {
-    static constexpr uint32_t N = 2;
-    typedef double type __attribute__((ext_vector_type(2)));
-};
 
 // floor(n / d) for every n <= nmax as __umulhi(n, m): m = floor(2^32 / d) + 1, so m d = 2^32 + e with 0 < e <= d, and
 // floor(n m / 2^32) = floor(n / d + n e / (d 2^32)) = floor(n / d) as long as n e < 2^32, which nmax d < 2^32 guarantees.
@@ -34,8 +26,8 @@ __device__ __forceinline__ uint32_t fast_div(uint32_t n, uint32_t d, uint32_t m)
 // `count` elements from `out` on, element f = fn(f): scalar head to the first 16-byte boundary, 16-byte body, scalar tail.
 template <typename T, typename F> __device__ __forceinline__ void store_range(T *out, uint32_t count, uint32_t tid, uint32_t threads, F fn)
 {
-    using V = typename GradVec<T>::type;
-    constexpr uint32_t VN = GradVec<T>::N;
+    using V = typename Vec16<T>::type;
+    constexpr uint32_t VN = Vec16<T>::N;
     uint32_t head = (uint32_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) / (uint32_t)sizeof(T);
     if (head > count) head = count;
     const uint32_t body = (count - head) / VN;

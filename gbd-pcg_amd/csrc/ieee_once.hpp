@@ -15,7 +15,7 @@ __device__ __forceinline__ double sqrt_once(double a) { return __builtin_sqrt(a)
 // comparisons: a NaN v stays NaN, +-Inf bounds never bind
 template <typename T> __device__ __forceinline__ T clip(T v, T lo, T hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// The projection onto the degenerate set of the adjoint updates (admm_adjoint.hip, the adjoint rows of admm_rows.hip): {0} where the
+// The projection onto the degenerate set of the adjoint updates (admm.hip, the adjoint rows of admm_rows.hip): {0} where the
 // forward multiplier yf is not zero (a NaN included), the whole line elsewhere.  clip(v, +0, +0): a NaN v stays NaN, v = -0 stays -0.
 template <typename T> __device__ __forceinline__ T pin(T v, T yf) { return yf != T(0) ? clip(v, T(0), T(0)) : v; }
 
@@ -42,7 +42,7 @@ template <typename T> __device__ __forceinline__ T soft_init(T w, T lo, T hi, T 
     return kappa == T(__builtin_huge_val()) ? clip(w, lo, hi) : w;
 }
 
-// The rows a soft update left SATURATED (admm_soft_grad.hip, the SOFT gradients of admm_lin_grad.hip): |yf| >= theta with the theta of
+// The rows a soft update left SATURATED (admm_box_grad.hip, the SOFT gradients of admm_lin_grad.hip): |yf| >= theta with the theta of
 // soft_clip, the same ONE division -- the update wrote +-theta itself, so the comparison is exact; a NaN yf fails it.
 __device__ __forceinline__ float abs_once(float a) { return __builtin_fabsf(a); }
 __device__ __forceinline__ double abs_once(double a) { return __builtin_fabs(a); }

@@ -262,17 +262,13 @@ template <typename T>
 hipError_t launch_admm_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *g, const T *lo, const T *hi, const T *rho,
                               const T *z, T *w, T *y, T *gt, T *res, hipStream_t s, bool init, const T *kappa = nullptr);
 
-// ---- admm_adjoint.hip : the backward pass of the hard box QP, the launch shape of admm.hip.  yf is the forward y, read only: the
-// mask m = (yf != 0) stands where lo, hi stand in the update, which then projects onto {0} where m and onto the line elsewhere:
+// (still admm.hip) The adjoint of that update, the backward pass of the hard box QP, same launch shape.  yf is the forward y, read
+// only: the mask m = (yf != 0) stands where lo, hi stand in the update, which then projects onto {0} where m and onto the line elsewhere:
 //     w <- m ? clip(az + y, 0, 0) : az + y, y <- (az + y) - w, gt <- fma(-rho_b, w - y, gz), res as in the update
 // the bits of launch_admm_update on the explicit box lo = hi = +0 where m, -Inf / +Inf elsewhere.  init: as there (az, res may be null).
-// grad_bounds: glo = yf < 0 ? -(rho_b ya) : +0, ghi = yf > 0 ? -(rho_b ya) : +0, elementwise over the layout of g.
 template <typename T>
 hipError_t launch_admm_adjoint_update(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *gz, const T *yf, const T *rho,
                                       const T *az, T *w, T *y, T *gt, T *res, hipStream_t s, bool init);
-template <typename T>
-hipError_t launch_admm_grad_bounds(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *yf, const T *rho, const T *ya, T *glo,
-                                   T *ghi, hipStream_t s);
 
 // ---- admm_rebalance.hip : adaptive rho by residual balancing in powers of two, one launch, one workgroup per problem.  From
 // r = res[2b], s = res[2b+1] and rho_b: rho_b <- rho_b 2^e with e in {+shift, -shift, 0} (the rule is in the head of the file and in
@@ -333,12 +329,16 @@ hipError_t launch_admm_lin_grad(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t 
                                 const T *yf, const T *ya, const T *rho, T *glo, T *ghi, T *gE, hipStream_t s, const T *E = nullptr,
                                 const T *kappa = nullptr, T *gkappa = nullptr);
 
-// ---- admm_soft_grad.hip : the elementwise launches of the backward pass of the soft box and rows QPs, the launch shape of
-// launch_admm_grad_bounds.  theta = kappa / rho_b is the one division of the soft update, sat = |yf| >= theta (a NaN yf fails):
-//     mask:        ym = sat ? +0 : yf over `len` elements per problem (nz: the box, nw: the rows); ym == yf is refused
-//     grad_bounds: glo = (yf < 0 && !sat) ? -(rho_b ya) : +0, ghi likewise with > 0, gkappa = sat ? (yf > 0 ? az : -az) : +0,
-//                  over the layout of g; each output may be null (not written), not all three
+// ---- admm_box_grad.hip : the elementwise launches of the backward passes around the adjoint loops, the launch shape of admm.hip.
+//     grad_bounds: glo = yf < 0 ? -(rho_b ya) : +0, ghi = yf > 0 ? -(rho_b ya) : +0, over the layout of g (the hard box)
+// The soft box and rows: theta = kappa / rho_b is the one division of the soft update, sat = |yf| >= theta (a NaN yf fails):
+//     mask:             ym = sat ? +0 : yf over `len` elements per problem (nz: the box, nw: the rows); ym == yf is refused
+//     soft_grad_bounds: glo = (yf < 0 && !sat) ? -(rho_b ya) : +0, ghi likewise with > 0, gkappa = sat ? (yf > 0 ? az : -az) : +0,
+//                       over the layout of g; each output may be null (not written), not all three
 // rho is the rho of the update that wrote yf.
+template <typename T>
+hipError_t launch_admm_grad_bounds(uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const T *yf, const T *rho, const T *ya, T *glo,
+                                   T *ghi, hipStream_t s);
 template <typename T>
 hipError_t launch_admm_soft_mask(uint64_t len, uint32_t batch, const T *yf, const T *kappa, const T *rho, T *ym, hipStream_t s);
 template <typename T>

@@ -1,4 +1,4 @@
-"""The backward pass of the hard box QP on the device (csrc/admm_adjoint.hip and its composite calls in csrc/api_kkt.hip, through the C
+"""The backward pass of the hard box QP on the device (the adjoint entry of csrc/admm.hip, csrc/admm_box_grad.hip and their composite calls in csrc/api_kkt.hip, through the C
 ABI): gbdpcg_admm_adjoint_init_*, gbdpcg_admm_adjoint_update_*, gbdpcg_admm_adjoint_step_* and its graph, gbdpcg_admm_grad_bounds_*.
 PARITY UNPINNED: the reference tree has no code, fixture or output for these steps.
 

@@ -1,4 +1,4 @@
-"""The backward pass of the soft (L1-penalised) box and rows QPs on the device (csrc/admm_soft_grad.hip, the SOFT instantiation of
+"""The backward pass of the soft (L1-penalised) box and rows QPs on the device (csrc/admm_box_grad.hip, the SOFT instantiation of
 csrc/admm_lin_grad.hip, through the C ABI): gbdpcg_admm_soft_mask_*, gbdpcg_admm_lin_soft_mask_*, gbdpcg_admm_soft_grad_bounds_*,
 gbdpcg_admm_lin_soft_grad_*.
 PARITY UNPINNED: the reference tree has no code, fixture or output for these steps.

@@ -2,13 +2,15 @@
 (z, lambda), on the pinned fixture of tests/admm_lin_adjoint_ref.py.  All seven gradients of l = gz' z + glam' lambda after K_FWD
 forward and K_ADJ adjoint iterations are held against the dense reference within admm_adjoint_ref.converged_bound (the bound of
 tests/test_gpu_admm_lin_adjoint.py); rho gets no gradient; a problem with zero cotangents gets exactly zero gradients and leaves its
-neighbours' bits alone; the arguments are validated as kkt_solve validates its own.  Run with -s for the figures."""
+neighbours' bits alone; the arguments are validated as kkt_solve validates its own; outputs and gradients are, bit for bit, those of
+the Solver calls the docstring names, in its order.  Run with -s for the figures."""
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
 import admm_lin_adjoint_ref as ar  # noqa: E402
+import admm_soft_adjoint_ref as sa  # noqa: E402
 from admm_util import dev, same  # noqa: E402
 from gbd_pcg_amd import autograd, binding  # noqa: E402
 
@@ -94,6 +96,50 @@ def test_zero_cotangents_give_zero_gradients_and_leave_the_neighbours_alone(solv
         assert not bool((part[1] != 0).any()), k
         assert bool(torch.isfinite(part).all()), k
         assert same(part[0], full[0]), k
+
+
+@pytest.mark.parametrize("dtype", [F32, F64])
+def test_autograd_is_the_composition_bit_for_bit(solver, dtype):
+    """The shape (5, 2, 3, 4) with rows (3, 2) and the bounds of tests/admm_soft_adjoint_ref.py taken hard, 5 forward and 5 adjoint
+    iterations (bits do not need convergence): z, lambda, res and the seven gradients against gbdpcg_admm_lin_form_*, gbdpcg_kkt_step_*,
+    gbdpcg_admm_lin_init_*, gbdpcg_admm_lin_step_*, gbdpcg_admm_lin_adjoint_init_*, gbdpcg_admm_lin_adjoint_step_*,
+    gbdpcg_admm_lin_grad_*, gbdpcg_kkt_grad_* on fresh buffers."""
+    K = 5
+    nx, nu, mx, mu, N, B = sa.dims("rows")
+    d, E, lo, hi, _, gz, glam = sa.fixture("rows")
+    arrays = dict(G=d["G"], C=d["C"], g=d["g"], c=d["c"], E=E, lo=lo, hi=hi)
+    t = {k: dev(arrays[k].astype(dtype).reshape(-1)).requires_grad_() for k in KEYS}
+    rho = dev(np.asarray(sa.FIXTURE_RHO["rows"], dtype))
+    gz, glam = dev(gz.astype(dtype).reshape(-1)), dev(glam.astype(dtype).reshape(-1))
+    kw = dict(tol=PCG_TOL[dtype], max_iter=200)
+    out, lam, res = autograd.lin_qp_solve(solver, nx, nu, mx, mu, N, *(t[k] for k in KEYS), rho, K, K, **kw)
+    grads = torch.autograd.grad((out * gz).sum() + (lam * glam).sum(), [t[k] for k in KEYS])
+
+    G, C, g, c, E, lo, hi = (t[k].detach() for k in KEYS)
+    S = torch.empty(B * 3 * nx * nx * N, dtype=g.dtype, device="cuda")
+    Pinv, Ginv, gamma = torch.empty_like(S), torch.empty_like(G), torch.empty_like(c)
+    lam2, z = torch.zeros_like(c), torch.empty_like(g)
+    w, y = torch.zeros_like(lo), torch.zeros_like(lo)
+    res2 = torch.zeros(B, 2, dtype=g.dtype, device="cuda")
+    Gt = solver.admm_lin_form(nx, nu, mx, mu, N, B, G, E, rho)
+    solver.kkt_step(nx, nu, N, B, Gt, C, g, c, S, gamma, Ginv, Pinv, lam2, z, **kw)
+    gt = solver.admm_lin_init(nx, nu, mx, mu, N, B, g, E, lo, hi, rho, w, y)
+    for _ in range(K):
+        solver.admm_lin_step(nx, nu, mx, mu, N, B, Ginv, C, g, c, E, lo, hi, rho, S, Pinv, gamma, lam2, z, w, y, gt, res=res2, **kw)
+    nglam = -glam
+    gamma2, alam, az = torch.empty_like(lam2), torch.zeros_like(lam2), torch.empty_like(g)
+    wa, ya = torch.zeros_like(y), torch.zeros_like(y)
+    res3 = torch.empty(B, 2, dtype=g.dtype, device="cuda")
+    gta = solver.admm_lin_adjoint_init(nx, nu, mx, mu, N, B, gz, E, y, rho, wa, ya)
+    for _ in range(K):
+        solver.admm_lin_adjoint_step(nx, nu, mx, mu, N, B, Ginv, C, gz, nglam, E, y, rho, S, Pinv, gamma2, alam, az, wa, ya, gta,
+                                     res=res3, **kw)
+    glo, ghi, gE = solver.admm_lin_grad(nx, nu, mx, mu, N, B, z, az, y, ya, rho)
+    gG, gC = solver.kkt_grad(nx, nu, N, B, z, lam2, az, alam)
+    torch.cuda.synchronize()
+    assert same(out, z) and same(lam, lam2) and same(res, res2)
+    for k, gr, want in zip(KEYS, grads, (gG, gC, az, -alam, gE, glo, ghi)):
+        assert same(gr, want), k
 
 
 def test_arguments_are_validated(solver):
