@@ -82,6 +82,9 @@ SYMBOLS = [
     # the backward pass of the soft box and rows QPs: the mask in front of the hard adjoint calls, the gradients with kappa
     *[f"gbdpcg_{name}_{suf}" for name in ("admm_soft_mask", "admm_lin_soft_mask", "admm_soft_grad_bounds", "admm_lin_soft_grad")
       for suf in ("f32", "f64")],
+    # the primal infeasibility certificate of the hard box and rows paths, from two iterates of the splitting
+    *[f"gbdpcg_{name}_{suf}" for name in ("admm_infeas", "admm_infeas_shared", "admm_lin_infeas", "admm_lin_infeas_shared")
+      for suf in ("f32", "f64")],
     "gbdpcg_demote_f32", "gbdpcg_kkt_defect_mixed", "gbdpcg_kkt_refine_apply", "gbdpcg_kkt_refine_step",
     "gbdpcg_graph_create_kkt_refine_step",
     "gbdpcg_kkt_defect_mixed_reg", "gbdpcg_kkt_defect_mixed_shared", "gbdpcg_kkt_refine_step_reg", "gbdpcg_kkt_refine_step_shared",
@@ -185,6 +188,11 @@ def _resolve_argtypes(lib):
         getattr(lib, f"gbdpcg_admm_lin_soft_mask_{suf}").argtypes = lsizes + [vp, vp, vp] + [vp] + [vp]
         getattr(lib, f"gbdpcg_admm_soft_grad_bounds_{suf}").argtypes = sizes + [vp, vp, vp, vp, vp] + [vp, vp, vp] + [vp]
         getattr(lib, f"gbdpcg_admm_lin_soft_grad_{suf}").argtypes = lsizes + [vp] * 7 + [vp] * 4 + [vp]
+        # the infeasibility certificate
+        #   h, nx, nu, [mx, mu], N, batch | C, c, [E], lo, hi, rho | lambda0, lambda1, y0, y1 | eps | cert, flag | stream
+        for name in ("infeas", "infeas_shared"):
+            getattr(lib, f"gbdpcg_admm_{name}_{suf}").argtypes = sizes + [vp] * 5 + [vp] * 4 + [ft] + [vp, vp] + [vp]
+            getattr(lib, f"gbdpcg_admm_lin_{name}_{suf}").argtypes = lsizes + [vp] * 6 + [vp] * 4 + [ft] + [vp, vp] + [vp]
 
     # mixed-precision refinement (no suffix: fp64 data and point, fp32 solve)
     head = [vp, u32, u32, u32, u32, vp, vp, vp, vp]                # h, nx, nu, N, batch, G, C, g, c (fp64)
@@ -1443,6 +1451,56 @@ class Solver:
         self._check(fn(self.h, nx, nu, mx, mu, N, batch, _p(z), _p(az), _p(yf), _p(ya), _p(self._rho(rho, batch, z)), _p(glo), _p(ghi),
                        _p(gE), self._stream(stream)), "admm_lin_grad")
         return glo, ghi, gE
+
+    # ---- the primal infeasibility certificate of the hard paths (include/gbdpcg.h): two iterates (lam0, y0), (lam1, y1) of the
+    # splitting in, per problem the scale n, the residual r, the support value sigma and the flag out
+    def _infeas(self, name, nx, nu, mx, mu, N, batch, C, c, E, lo, hi, rho, lam0, lam1, y0, y1, eps, cert, flag, want_flag, stream):
+        import torch
+        suf, _ = _suffix(c)
+        box, mats = "lin" not in name, 1 if name.endswith("shared") else batch
+        nw = (nx + nu) * N - nu if box else self._lin_sizes(nx, nu, mx, mu, N)[1]
+        ne = 0 if box else self._lin_sizes(nx, nu, mx, mu, N)[2]
+        if cert is None:
+            cert = torch.empty(batch, 3, dtype=c.dtype, device=c.device)
+        if flag is None and want_flag:
+            flag = torch.empty(batch, dtype=torch.uint8, device=c.device)
+        for t, cnt in ((c, batch * nx * N), (lam0, batch * nx * N), (lam1, batch * nx * N), (lo, batch * nw), (hi, batch * nw),
+                       (y0, batch * nw), (y1, batch * nw), (cert, 3 * batch)) + (() if box else ((E, mats * ne),)):
+            assert t is not None and t.is_cuda and t.is_contiguous() and t.numel() == cnt and t.dtype == c.dtype
+        assert (C is None and N == 1) or (C.is_cuda and C.is_contiguous() and C.dtype == c.dtype and
+                                          C.numel() == mats * nx * (nx + nu) * (N - 1))
+        assert flag is None or (flag.is_cuda and flag.is_contiguous() and flag.numel() == batch and flag.dtype == torch.uint8)
+        fn = getattr(self.lib, f"gbdpcg_{name}_{suf}")
+        head = (self.h, nx, nu, N, batch, _p(C), _p(c)) if box else (self.h, nx, nu, mx, mu, N, batch, _p(C), _p(c), _p(E))
+        self._check(fn(*head, _p(lo), _p(hi), _p(self._rho(rho, batch, c)), _p(lam0), _p(lam1), _p(y0), _p(y1), eps, _p(cert),
+                       _p(flag), self._stream(stream)), name)
+        return cert.view(batch, 3), flag
+
+    def admm_infeas(self, nx, nu, N, batch, C, c, lo, hi, rho, lam0, lam1, y0, y1, eps, cert=None, flag=None, want_flag=True,
+                    stream=None):
+        """gbdpcg_admm_infeas_*: (cert [batch, 3] = (n, r, sigma), flag [batch] uint8) of the hard box from two iterates of
+        gbdpcg_admm_step_*; flag = n > 0 and r <= eps n and sigma < -eps n.  want_flag=False passes NULL for the flag."""
+        return self._infeas("admm_infeas", nx, nu, 0, 0, N, batch, C, c, None, lo, hi, rho, lam0, lam1, y0, y1, eps, cert, flag,
+                            want_flag, stream)
+
+    def admm_infeas_shared(self, nx, nu, N, batch, C, c, lo, hi, rho, lam0, lam1, y0, y1, eps, cert=None, flag=None, want_flag=True,
+                           stream=None):
+        """gbdpcg_admm_infeas_shared_*: one problem's C, `batch` of everything else."""
+        return self._infeas("admm_infeas_shared", nx, nu, 0, 0, N, batch, C, c, None, lo, hi, rho, lam0, lam1, y0, y1, eps, cert, flag,
+                            want_flag, stream)
+
+    def admm_lin_infeas(self, nx, nu, mx, mu, N, batch, C, c, E, lo, hi, rho, lam0, lam1, y0, y1, eps, cert=None, flag=None,
+                        want_flag=True, stream=None):
+        """gbdpcg_admm_lin_infeas_*: the certificate of the hard linear rows lo <= E z <= hi from two iterates of
+        gbdpcg_admm_lin_step_*."""
+        return self._infeas("admm_lin_infeas", nx, nu, mx, mu, N, batch, C, c, E, lo, hi, rho, lam0, lam1, y0, y1, eps, cert, flag,
+                            want_flag, stream)
+
+    def admm_lin_infeas_shared(self, nx, nu, mx, mu, N, batch, C, c, E, lo, hi, rho, lam0, lam1, y0, y1, eps, cert=None, flag=None,
+                               want_flag=True, stream=None):
+        """gbdpcg_admm_lin_infeas_shared_*: one problem's C and E, `batch` of everything else."""
+        return self._infeas("admm_lin_infeas_shared", nx, nu, mx, mu, N, batch, C, c, E, lo, hi, rho, lam0, lam1, y0, y1, eps, cert,
+                            flag, want_flag, stream)
 
     # ---- the backward pass of the soft box and rows QPs (include/gbdpcg.h): the forward y splits the rows into free, held and
     # saturated; the mask turns it into the yf of the hard adjoint methods above, the gradient launches know of kappa

@@ -381,6 +381,31 @@ gbdpcg_status admm_lin_soft_grad_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t n
     return GBDPCG_OK;
 }
 
+// ---- the primal infeasibility certificate of the hard box and rows paths (admm_infeas.hip), one launch, no handle state.  box: no
+// E, no (mx, mu).  The two iterates must be two: lambda0 == lambda1 or y0 == y1 is refused with the null pointers.  The rows: the
+// refusals of the rows family, then the kernel's own knot (it stages [A | B] next to E).
+template <typename T>
+gbdpcg_status admm_infeas_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch,
+                               const T *d_C, const T *d_c, const T *d_E, const T *d_lo, const T *d_hi, const T *d_rho,
+                               const T *d_lambda0, const T *d_lambda1, const T *d_y0, const T *d_y1, T eps, T *d_cert, uint8_t *d_flag,
+                               void *stream, bool box, bool shared)
+{
+    if (!h || !d_c || (!box && !d_E) || !d_lo || !d_hi || !d_rho || !d_lambda0 || !d_lambda1 || !d_y0 || !d_y1 || !d_cert ||
+        (!d_C && N > 1) || nx == 0 || nu == 0 || N == 0 || batch == 0 || d_lambda0 == d_lambda1 || d_y0 == d_y1)
+        return GBDPCG_ERR_INVALID;
+    if (!box) {
+        AdmmOperands<T> a{};
+        a.mx = mx, a.mu = mu;
+        const gbdpcg_status st = admm_rows_status<T>(nx, nu, a, N);
+        if (st != GBDPCG_OK) return st;
+    }
+    if (!admm_infeas_shape_ok<T>(nx, nu, box ? nx : mx, box ? nu : mu, box)) return GBDPCG_ERR_UNSUPPORTED;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_admm_infeas<T>(nx, nu, mx, mu, N, batch, d_C, d_c, d_E, d_lo, d_hi, d_rho, d_lambda0, d_lambda1, d_y0, d_y1, eps,
+                                     d_cert, d_flag, (hipStream_t)stream, box, shared));
+    return GBDPCG_OK;
+}
+
 // ---- adaptive rho (admm_rebalance.hip): residual balancing in powers of two, and the iteration that refactors with the new rho
 // The rule of gbdpcg_admm*_rebalance_* and what it writes next to y: rho [batch] in place, expo [batch].
 template <typename T> struct RhoRule {
@@ -1054,6 +1079,31 @@ GBDPCG_PAIR_BOTH(admm_lin_adjoint_step, false, LIN_ADJOINT_STEP_PARAMS, LIN_ADJO
 GBDPCG_ADMM_SOFT_ADJOINT(f32, float)
 GBDPCG_ADMM_SOFT_ADJOINT(f64, double)
 #undef GBDPCG_ADMM_SOFT_ADJOINT
+
+// ---- the infeasibility certificate of the hard box and rows paths, with the _shared twins (one problem's C [and E])
+#define INFEAS_VECTORS(TYPE)                                                                                                        \
+    const TYPE *d_lo, const TYPE *d_hi, const TYPE *d_rho, const TYPE *d_lambda0, const TYPE *d_lambda1, const TYPE *d_y0,          \
+        const TYPE *d_y1, TYPE eps, TYPE *d_cert, uint8_t *d_flag, void *stream
+#define GBDPCG_ADMM_INFEAS(NAME, SHARED, SUF, TYPE)                                                                                 \
+    gbdpcg_status gbdpcg_admm_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,               \
+                                             const TYPE *d_C, const TYPE *d_c, INFEAS_VECTORS(TYPE))                                \
+    {                                                                                                                               \
+        return admm_infeas_impl<TYPE>(h, nx, nu, 0, 0, N, batch, d_C, d_c, nullptr, d_lo, d_hi, d_rho, d_lambda0, d_lambda1, d_y0,  \
+                                      d_y1, eps, d_cert, d_flag, stream, true, SHARED);                                             \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_lin_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, \
+                                                 uint32_t batch, const TYPE *d_C, const TYPE *d_c, const TYPE *d_E,                 \
+                                                 INFEAS_VECTORS(TYPE))                                                              \
+    {                                                                                                                               \
+        return admm_infeas_impl<TYPE>(h, nx, nu, mx, mu, N, batch, d_C, d_c, d_E, d_lo, d_hi, d_rho, d_lambda0, d_lambda1, d_y0,    \
+                                      d_y1, eps, d_cert, d_flag, stream, false, SHARED);                                            \
+    }
+GBDPCG_ADMM_INFEAS(infeas, false, f32, float)
+GBDPCG_ADMM_INFEAS(infeas, false, f64, double)
+GBDPCG_ADMM_INFEAS(infeas_shared, true, f32, float)
+GBDPCG_ADMM_INFEAS(infeas_shared, true, f64, double)
+#undef GBDPCG_ADMM_INFEAS
+#undef INFEAS_VECTORS
 
 // ---- the KKT backward pass: the adjoint solve + gradient launch as one call / one graph (the gradient launch alone is with the
 // single launches).  shared: one problem's Ginv, C, S, Pinv, and gG, gC summed over the batch.

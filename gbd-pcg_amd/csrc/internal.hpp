@@ -308,6 +308,19 @@ uint32_t admm_rows_knot_chunk(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu
 // (lx <= mx, lu <= mu; where a block has cone rows its q is not 0 and divides their number; q is ignored where it has none)
 bool admm_rows_classes_ok(uint32_t mx, uint32_t mu, const RowClasses &c);
 
+// ---- admm_infeas.hip : the primal infeasibility certificate of the hard ADMM paths from two iterates (lam0, y0), (lam1, y1) of the
+// splitting, one launch, one workgroup per problem; the lines that define every bit are in the head of the file.  cert [3 batch]:
+// the scale n, the residual r of C'dl + rho E'dy, the support value sigma; flag [batch] (may be null: not written):
+// n > 0 && r <= eps n && sigma < -(eps n).  box: no E (not looked at), mx, mu are not looked at, lo, hi, y0, y1 have the layout of g.
+// shared: C and E are one problem's blocks.  C may be null when N == 1.
+// (a knot's [A | B], E blocks and vectors within the kernel's LDS; hipErrorInvalidValue otherwise)
+template <typename T>
+hipError_t launch_admm_infeas(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *C, const T *c,
+                              const T *E, const T *lo, const T *hi, const T *rho, const T *lam0, const T *lam1, const T *y0,
+                              const T *y1, T eps, T *cert, uint8_t *flag, hipStream_t s, bool box, bool shared);
+template <typename T> bool admm_infeas_shape_ok(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, bool box);
+uint32_t admm_infeas_knot_chunk(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, bool box);
+
 // ---- kkt_grad.hip : the gradients of a scalar in the packed KKT blocks from the forward pair (z, lambda) and the adjoint pair
 // (az, alam), one launch.  gG has the layout of G, gC that of C; either may be null (not written):
 //     gQ_k = 1/2 (ax_k x_k' + x_k ax_k'), gR_k likewise with u;  [gA_k | gB_k] = -(alam_{k+1} z_k' + lam_{k+1} az_k')

@@ -1697,6 +1697,86 @@ gbdpcg_status gbdpcg_admm_lin_soft_grad_f64(gbdpcg_handle_t h, uint32_t nx, uint
                                             const double *d_yf, const double *d_ya, const double *d_kappa, const double *d_rho,
                                             double *d_glo, double *d_ghi, double *d_gkappa, double *d_gE, void *stream);
 
+/* The primal infeasibility certificate of the HARD ADMM paths (gbdpcg_admm_step_*, gbdpcg_admm_lin_step_*), on the device.  A hard
+ * iteration cannot tell an infeasible problem from a slow one: d_res[2b] stalls at the gap and y grows.  Problem b, min 1/2 z'Gz +
+ * g'z subject to Cz = c and lo <= E z <= hi, is infeasible iff some (dl, dm) satisfies (Farkas)
+ *     C'dl + E'dm = 0        and        c'dl + sum_r (dm_r > 0 ? hi_r dm_r : lo_r dm_r) < 0
+ * Every z-step of the splitting satisfies Gt z + gt + C'lambda = 0, so on an infeasible problem, where z and w settle and E z - w
+ * tends to the constant gap, the differences of two iterates dl = lambda1 - lambda0, dm = rho (y1 - y0) tend to such a pair.  The
+ * two iterates may be any number of steps apart: a wider window scales the pair and does not change the test.  The caller copies
+ * d_lambda and d_y aside with its own copy nodes (d_lambda0, d_y0), runs one or more steps, and hands both pairs to one launch,
+ * which answers per problem how close the differences are to a certificate.  (G + rho E'E is factored, so positive definite: the
+ * cost is never unbounded and there is no dual certificate to look for.)
+ * d_C, d_c, d_E, d_lo, d_hi, d_rho and the layouts of d_lambda*, d_y* are those of the gbdpcg_admm_lin_* family; the box calls
+ * (gbdpcg_admm_infeas_*) have no mx, mu, d_E, and d_lo, d_hi, d_y0, d_y1 have the layout of d_g.  d_C may be NULL when N == 1.
+ * _shared: d_C and d_E are ONE problem's, as in gbdpcg_admm_lin_step_shared_*, read with a zero problem stride; everything else
+ * stays per problem.
+ * Per problem b, every line ONE IEEE operation or a comparison, a chain being acc = fma(a_i, b_i, acc) in ascending i:
+ *     dl = fl(lambda1 - lambda0),   dy = fl(y1 - y0),   m_r = fl(rho_b dy_r)
+ *     x-part of knot k, entry r:   s = dl_k[r];   s = fma(A_k(q,r), -dl_{k+1}[q], s), q < nx ascending (absent at the last knot)
+ *     u-part of knot k, entry r:   s = +0;        s = fma(B_k(q,r), -dl_{k+1}[q], s), q < nx ascending
+ *                                  (the signs and the order of the C' terms of gbdpcg_kkt_residual_*)
+ *     u = chain over the rows i of Ex_k (Eu_k) of fma(E(i,r), dy_i, acc), seed +0;        q = fma(rho_b, u, s)
+ *     d_cert[3b]   = n = max(max |dl|, max_r |m_r|)        the scale
+ *     d_cert[3b+1] = r = max_j |q_j|                       the residual of the certificate
+ *                    (both maxima over bit patterns as in gbdpcg_kkt_residual_*: NaN on top, exact in any order)
+ *     t_k:  acc = +0;  over the knot's rows in storage order (x rows, then u rows):  dy_r > 0: acc = fma(hi_r, m_r, acc);
+ *           dy_r < 0: acc = fma(lo_r, m_r, acc);  otherwise nothing -- a zero or NaN dy_r never multiplies an infinite bound;
+ *           then acc = fma(c_k[i], dl_k[i], acc) for i < nx ascending
+ *     d_cert[3b+2] = sigma:  acc = +0;  acc = fl(acc + t_k) for k ascending       the support value (the two levels are part of
+ *                    the definition)
+ *     d_flag[b] = (n > 0 && r <= fl(eps n) && sigma < -fl(eps n)) ? 1 : 0         a NaN anywhere gives 0
+ * so the outputs are defined to the bit whatever the launch shape or the alignment of the pointers.  d_cert (3 batch elements of
+ * the call's precision) and d_flag (batch bytes; may be NULL: not written) are overwritten whatever they held.  The box calls
+ * take the single line u = fma(1, dy_r, +0) for the chain: THE BITS of the rows call with E = I, mx = nx, mu = nu on finite data,
+ * signed zeros included.  (A NaN or Inf dy_r stays in its own entry of q there; through the zero entries of an explicit I it
+ * reaches every entry of its block.)
+ * eps is the caller's: r / n falls and sigma / n settles at minus the gap over the scale.  On the pinned infeasible fixture
+ * (tests/admm_infeas_ref.py) eps = 0.1 flags every problem within 6 iterations in both precisions and never flags a feasible
+ * one, close to convergence included (there n falls to rounding noise, r with it, and r / n stays of order 1).
+ * One launch each, no handle state, asynchronous on `stream`, capturable inside a caller-owned capture; never allocates and needs
+ * nothing from gbdpcg_reserve.  d_lo, d_hi, d_rho and eps are not validated: bad values stay inside their own problem.
+ * NOT provided: cone rows (their certificate needs the dual cone); the soft families (always feasible in their soft rows); a
+ * device-side count over the batch; any change to the step graphs -- the copies of lambda and y are the caller's.
+ * Refusals, before anything is written: null handle or required pointer, nx, nu, N or batch == 0, no rows at all,
+ * d_lambda0 == d_lambda1, d_y0 == d_y1: GBDPCG_ERR_INVALID; mx or mu > 64, a knot ([A_k | B_k], its E blocks and vectors) that
+ * does not fit the LDS: GBDPCG_ERR_UNSUPPORTED; a batch of more than 2^31 - 1 problems: an error of the launch. */
+gbdpcg_status gbdpcg_admm_infeas_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_C,
+                                     const float *d_c, const float *d_lo, const float *d_hi, const float *d_rho,
+                                     const float *d_lambda0, const float *d_lambda1, const float *d_y0, const float *d_y1, float eps,
+                                     float *d_cert, uint8_t *d_flag, void *stream);
+gbdpcg_status gbdpcg_admm_infeas_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_C,
+                                     const double *d_c, const double *d_lo, const double *d_hi, const double *d_rho,
+                                     const double *d_lambda0, const double *d_lambda1, const double *d_y0, const double *d_y1,
+                                     double eps, double *d_cert, uint8_t *d_flag, void *stream);
+gbdpcg_status gbdpcg_admm_infeas_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_C,
+                                            const float *d_c, const float *d_lo, const float *d_hi, const float *d_rho,
+                                            const float *d_lambda0, const float *d_lambda1, const float *d_y0, const float *d_y1,
+                                            float eps, float *d_cert, uint8_t *d_flag, void *stream);
+gbdpcg_status gbdpcg_admm_infeas_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                            const double *d_C, const double *d_c, const double *d_lo, const double *d_hi,
+                                            const double *d_rho, const double *d_lambda0, const double *d_lambda1, const double *d_y0,
+                                            const double *d_y1, double eps, double *d_cert, uint8_t *d_flag, void *stream);
+gbdpcg_status gbdpcg_admm_lin_infeas_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                         uint32_t batch, const float *d_C, const float *d_c, const float *d_E, const float *d_lo,
+                                         const float *d_hi, const float *d_rho, const float *d_lambda0, const float *d_lambda1,
+                                         const float *d_y0, const float *d_y1, float eps, float *d_cert, uint8_t *d_flag, void *stream);
+gbdpcg_status gbdpcg_admm_lin_infeas_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                         uint32_t batch, const double *d_C, const double *d_c, const double *d_E, const double *d_lo,
+                                         const double *d_hi, const double *d_rho, const double *d_lambda0, const double *d_lambda1,
+                                         const double *d_y0, const double *d_y1, double eps, double *d_cert, uint8_t *d_flag,
+                                         void *stream);
+gbdpcg_status gbdpcg_admm_lin_infeas_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                                uint32_t batch, const float *d_C, const float *d_c, const float *d_E,
+                                                const float *d_lo, const float *d_hi, const float *d_rho, const float *d_lambda0,
+                                                const float *d_lambda1, const float *d_y0, const float *d_y1, float eps,
+                                                float *d_cert, uint8_t *d_flag, void *stream);
+gbdpcg_status gbdpcg_admm_lin_infeas_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                                uint32_t batch, const double *d_C, const double *d_c, const double *d_E,
+                                                const double *d_lo, const double *d_hi, const double *d_rho, const double *d_lambda0,
+                                                const double *d_lambda1, const double *d_y0, const double *d_y1, double eps,
+                                                double *d_cert, uint8_t *d_flag, void *stream);
+
 /* Mixed-precision refinement of a KKT point: fp32 solves on a kept fp32 factorisation, the defect and the point in fp64.
  * For a caller who needs more digits in the step than fp32 carries (SQP close to convergence, an adjoint solve, ADMM on a
  * kept factorisation) without the price of the fp64 pipeline: factor once in fp32 (gbdpcg_demote_f32 of G and C, then
