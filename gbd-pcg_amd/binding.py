@@ -85,6 +85,9 @@ SYMBOLS = [
     # the primal infeasibility certificate of the hard box and rows paths, from two iterates of the splitting
     *[f"gbdpcg_{name}_{suf}" for name in ("admm_infeas", "admm_infeas_shared", "admm_lin_infeas", "admm_lin_infeas_shared")
       for suf in ("f32", "f64")],
+    # the optimality test of every ADMM family: stationarity with the row multiplier, dynamics, consensus, each with its scale
+    *[f"gbdpcg_{name}_{suf}" for name in ("admm_optimality", "admm_optimality_shared", "admm_lin_optimality",
+                                           "admm_lin_optimality_shared") for suf in ("f32", "f64")],
     "gbdpcg_demote_f32", "gbdpcg_kkt_defect_mixed", "gbdpcg_kkt_refine_apply", "gbdpcg_kkt_refine_step",
     "gbdpcg_graph_create_kkt_refine_step",
     "gbdpcg_kkt_defect_mixed_reg", "gbdpcg_kkt_defect_mixed_shared", "gbdpcg_kkt_refine_step_reg", "gbdpcg_kkt_refine_step_shared",
@@ -193,6 +196,11 @@ def _resolve_argtypes(lib):
         for name in ("infeas", "infeas_shared"):
             getattr(lib, f"gbdpcg_admm_{name}_{suf}").argtypes = sizes + [vp] * 5 + [vp] * 4 + [ft] + [vp, vp] + [vp]
             getattr(lib, f"gbdpcg_admm_lin_{name}_{suf}").argtypes = lsizes + [vp] * 6 + [vp] * 4 + [ft] + [vp, vp] + [vp]
+        # the optimality test
+        #   h, nx, nu, [mx, mu], N, batch | G, C, g, c, [E], rho | z, lambda, w, y | eps_abs, eps_rel | opt, done | stream
+        for name in ("optimality", "optimality_shared"):
+            getattr(lib, f"gbdpcg_admm_{name}_{suf}").argtypes = sizes + [vp] * 5 + [vp] * 4 + [ft, ft] + [vp, vp] + [vp]
+            getattr(lib, f"gbdpcg_admm_lin_{name}_{suf}").argtypes = lsizes + [vp] * 6 + [vp] * 4 + [ft, ft] + [vp, vp] + [vp]
 
     # mixed-precision refinement (no suffix: fp64 data and point, fp32 solve)
     head = [vp, u32, u32, u32, u32, vp, vp, vp, vp]                # h, nx, nu, N, batch, G, C, g, c (fp64)
@@ -1501,6 +1509,58 @@ class Solver:
         """gbdpcg_admm_lin_infeas_shared_*: one problem's C and E, `batch` of everything else."""
         return self._infeas("admm_lin_infeas_shared", nx, nu, mx, mu, N, batch, C, c, E, lo, hi, rho, lam0, lam1, y0, y1, eps, cert,
                             flag, want_flag, stream)
+
+    # ---- the optimality test of every ADMM family (include/gbdpcg.h): the point (z, lam, w, y) in, per problem the residuals of
+    # stationarity (with the row multiplier rho y), dynamics and consensus, their scales and the flag out.  G is the Hessian.
+    def _optimality(self, name, nx, nu, mx, mu, N, batch, G, C, g, c, E, rho, z, lam, w, y, eps_abs, eps_rel, opt, done, want_done,
+                    stream):
+        import torch
+        suf, _ = _suffix(g)
+        box, mats = "lin" not in name, 1 if name.endswith("shared") else batch
+        nz = (nx + nu) * N - nu
+        nw = nz if box else self._lin_sizes(nx, nu, mx, mu, N)[1]
+        ne = 0 if box else self._lin_sizes(nx, nu, mx, mu, N)[2]
+        if opt is None:
+            opt = torch.empty(batch, 6, dtype=g.dtype, device=g.device)
+        if done is None and want_done:
+            done = torch.empty(batch, dtype=torch.uint8, device=g.device)
+        for t, cnt in ((G, mats * ((nx * nx + nu * nu) * N - nu * nu)), (g, batch * nz), (z, batch * nz), (c, batch * nx * N),
+                       (lam, batch * nx * N), (w, batch * nw), (y, batch * nw), (opt, 6 * batch)) + (() if box else ((E, mats * ne),)):
+            assert t is not None and t.is_cuda and t.is_contiguous() and t.numel() == cnt and t.dtype == g.dtype
+        assert (C is None and N == 1) or (C.is_cuda and C.is_contiguous() and C.dtype == g.dtype and
+                                          C.numel() == mats * nx * (nx + nu) * (N - 1))
+        assert done is None or (done.is_cuda and done.is_contiguous() and done.numel() == batch and done.dtype == torch.uint8)
+        fn = getattr(self.lib, f"gbdpcg_{name}_{suf}")
+        head = (self.h, nx, nu, N, batch) if box else (self.h, nx, nu, mx, mu, N, batch)
+        mid = (_p(G), _p(C), _p(g), _p(c)) + (() if box else (_p(E),))
+        self._check(fn(*head, *mid, _p(self._rho(rho, batch, g)), _p(z), _p(lam), _p(w), _p(y), eps_abs, eps_rel, _p(opt), _p(done),
+                       self._stream(stream)), name)
+        return opt.view(batch, 6), done
+
+    def admm_optimality(self, nx, nu, N, batch, G, C, g, c, rho, z, lam, w, y, eps_abs, eps_rel, opt=None, done=None, want_done=True,
+                        stream=None):
+        """gbdpcg_admm_optimality_*: (opt [batch, 6] = (r_s, r_e, r_r, n_s, n_e, n_r), done [batch] uint8) of the box families (hard
+        and soft) at (z, lam, w, y); done = every r <= eps_abs + eps_rel n.  want_done=False passes NULL for done."""
+        return self._optimality("admm_optimality", nx, nu, 0, 0, N, batch, G, C, g, c, None, rho, z, lam, w, y, eps_abs, eps_rel, opt,
+                                done, want_done, stream)
+
+    def admm_optimality_shared(self, nx, nu, N, batch, G, C, g, c, rho, z, lam, w, y, eps_abs, eps_rel, opt=None, done=None,
+                               want_done=True, stream=None):
+        """gbdpcg_admm_optimality_shared_*: one problem's G and C, `batch` of everything else."""
+        return self._optimality("admm_optimality_shared", nx, nu, 0, 0, N, batch, G, C, g, c, None, rho, z, lam, w, y, eps_abs, eps_rel,
+                                opt, done, want_done, stream)
+
+    def admm_lin_optimality(self, nx, nu, mx, mu, N, batch, G, C, g, c, E, rho, z, lam, w, y, eps_abs, eps_rel, opt=None, done=None,
+                            want_done=True, stream=None):
+        """gbdpcg_admm_lin_optimality_*: the test of the rows families (linear, soft, cones) at (z, lam, w, y)."""
+        return self._optimality("admm_lin_optimality", nx, nu, mx, mu, N, batch, G, C, g, c, E, rho, z, lam, w, y, eps_abs, eps_rel,
+                                opt, done, want_done, stream)
+
+    def admm_lin_optimality_shared(self, nx, nu, mx, mu, N, batch, G, C, g, c, E, rho, z, lam, w, y, eps_abs, eps_rel, opt=None,
+                                   done=None, want_done=True, stream=None):
+        """gbdpcg_admm_lin_optimality_shared_*: one problem's G, C and E, `batch` of everything else."""
+        return self._optimality("admm_lin_optimality_shared", nx, nu, mx, mu, N, batch, G, C, g, c, E, rho, z, lam, w, y, eps_abs,
+                                eps_rel, opt, done, want_done, stream)
 
     # ---- the backward pass of the soft box and rows QPs (include/gbdpcg.h): the forward y splits the rows into free, held and
     # saturated; the mask turns it into the yf of the hard adjoint methods above, the gradient launches know of kappa

@@ -406,6 +406,30 @@ gbdpcg_status admm_infeas_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint
     return GBDPCG_OK;
 }
 
+// ---- the optimality test of every ADMM family (admm_optimality.hip), one launch, no handle state.  box: no E, no (mx, mu).  The
+// rows: the refusals of the rows family, then the kernel's own knot (it stages Q, R and [A | B] next to E).
+template <typename T>
+gbdpcg_status admm_optimality_impl(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch,
+                                   const T *d_G, const T *d_C, const T *d_g, const T *d_c, const T *d_E, const T *d_rho, const T *d_z,
+                                   const T *d_lambda, const T *d_w, const T *d_y, T eps_abs, T eps_rel, T *d_opt, uint8_t *d_done,
+                                   void *stream, bool box, bool shared)
+{
+    if (!h || !d_G || !d_g || !d_c || (!box && !d_E) || !d_rho || !d_z || !d_lambda || !d_w || !d_y || !d_opt || (!d_C && N > 1) ||
+        nx == 0 || nu == 0 || N == 0 || batch == 0)
+        return GBDPCG_ERR_INVALID;
+    if (!box) {
+        AdmmOperands<T> a{};
+        a.mx = mx, a.mu = mu;
+        const gbdpcg_status st = admm_rows_status<T>(nx, nu, a, N);
+        if (st != GBDPCG_OK) return st;
+    }
+    if (!admm_optimality_shape_ok<T>(nx, nu, box ? nx : mx, box ? nu : mu, box)) return GBDPCG_ERR_UNSUPPORTED;
+    DEVICE_SCOPE(h);
+    HIP_TRY(h, launch_admm_optimality<T>(nx, nu, mx, mu, N, batch, d_G, d_C, d_g, d_c, d_E, d_rho, d_z, d_lambda, d_w, d_y, eps_abs,
+                                         eps_rel, d_opt, d_done, (hipStream_t)stream, box, shared));
+    return GBDPCG_OK;
+}
+
 // ---- adaptive rho (admm_rebalance.hip): residual balancing in powers of two, and the iteration that refactors with the new rho
 // The rule of gbdpcg_admm*_rebalance_* and what it writes next to y: rho [batch] in place, expo [batch].
 template <typename T> struct RhoRule {
@@ -1104,6 +1128,32 @@ GBDPCG_ADMM_INFEAS(infeas_shared, true, f32, float)
 GBDPCG_ADMM_INFEAS(infeas_shared, true, f64, double)
 #undef GBDPCG_ADMM_INFEAS
 #undef INFEAS_VECTORS
+
+// ---- the optimality test of every ADMM family, with the _shared twins (one problem's G, C [and E])
+#define OPTIMALITY_VECTORS(TYPE)                                                                                                    \
+    const TYPE *d_rho, const TYPE *d_z, const TYPE *d_lambda, const TYPE *d_w, const TYPE *d_y, TYPE eps_abs, TYPE eps_rel,         \
+        TYPE *d_opt, uint8_t *d_done, void *stream
+#define GBDPCG_ADMM_OPTIMALITY(NAME, SHARED, SUF, TYPE)                                                                             \
+    gbdpcg_status gbdpcg_admm_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,               \
+                                             const TYPE *d_G, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c,                    \
+                                             OPTIMALITY_VECTORS(TYPE))                                                              \
+    {                                                                                                                               \
+        return admm_optimality_impl<TYPE>(h, nx, nu, 0, 0, N, batch, d_G, d_C, d_g, d_c, nullptr, d_rho, d_z, d_lambda, d_w, d_y,   \
+                                          eps_abs, eps_rel, d_opt, d_done, stream, true, SHARED);                                   \
+    }                                                                                                                               \
+    gbdpcg_status gbdpcg_admm_lin_##NAME##_##SUF(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, \
+                                                 uint32_t batch, const TYPE *d_G, const TYPE *d_C, const TYPE *d_g, const TYPE *d_c, \
+                                                 const TYPE *d_E, OPTIMALITY_VECTORS(TYPE))                                         \
+    {                                                                                                                               \
+        return admm_optimality_impl<TYPE>(h, nx, nu, mx, mu, N, batch, d_G, d_C, d_g, d_c, d_E, d_rho, d_z, d_lambda, d_w, d_y,     \
+                                          eps_abs, eps_rel, d_opt, d_done, stream, false, SHARED);                                  \
+    }
+GBDPCG_ADMM_OPTIMALITY(optimality, false, f32, float)
+GBDPCG_ADMM_OPTIMALITY(optimality, false, f64, double)
+GBDPCG_ADMM_OPTIMALITY(optimality_shared, true, f32, float)
+GBDPCG_ADMM_OPTIMALITY(optimality_shared, true, f64, double)
+#undef GBDPCG_ADMM_OPTIMALITY
+#undef OPTIMALITY_VECTORS
 
 // ---- the KKT backward pass: the adjoint solve + gradient launch as one call / one graph (the gradient launch alone is with the
 // single launches).  shared: one problem's Ginv, C, S, Pinv, and gG, gC summed over the batch.

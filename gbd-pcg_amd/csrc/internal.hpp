@@ -321,6 +321,19 @@ hipError_t launch_admm_infeas(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu
 template <typename T> bool admm_infeas_shape_ok(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, bool box);
 uint32_t admm_infeas_knot_chunk(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, bool box);
 
+// ---- admm_optimality.hip : the optimality test of every ADMM family at (z, lambda, w, y), one launch, one workgroup per problem;
+// the lines that define every bit are in the head of the file.  opt [6 batch]: r_s, r_e, r_r (stationarity with the row multiplier,
+// dynamics, consensus) and their scales n_s, n_e, n_r; done [batch] (may be null: not written): r <= fma(eps_rel, n, eps_abs) for
+// all three.  G is the Hessian.  box: no E (not looked at), mx, mu are not looked at, w, y have the layout of g.  shared: G, C and E
+// are one problem's blocks.  C may be null when N == 1.
+// (a knot's Q, R, [A | B], E blocks and vectors within the kernel's LDS; hipErrorInvalidValue otherwise)
+template <typename T>
+hipError_t launch_admm_optimality(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N, uint32_t batch, const T *G, const T *C,
+                                  const T *g, const T *c, const T *E, const T *rho, const T *z, const T *lambda, const T *w, const T *y,
+                                  T eps_abs, T eps_rel, T *opt, uint8_t *done, hipStream_t s, bool box, bool shared);
+template <typename T> bool admm_optimality_shape_ok(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, bool box);
+uint32_t admm_optimality_knot_chunk(uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, bool box);
+
 // ---- kkt_grad.hip : the gradients of a scalar in the packed KKT blocks from the forward pair (z, lambda) and the adjoint pair
 // (az, alam), one launch.  gG has the layout of G, gC that of C; either may be null (not written):
 //     gQ_k = 1/2 (ax_k x_k' + x_k ax_k'), gR_k likewise with u;  [gA_k | gB_k] = -(alam_{k+1} z_k' + lam_{k+1} az_k')

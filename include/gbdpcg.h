@@ -1777,6 +1777,94 @@ gbdpcg_status gbdpcg_admm_lin_infeas_shared_f64(gbdpcg_handle_t h, uint32_t nx, 
                                                 const double *d_lambda1, const double *d_y0, const double *d_y1, double eps,
                                                 double *d_cert, uint8_t *d_flag, void *stream);
 
+/* The optimality test of the ADMM families, on the device: is (z, lambda, rho y) a solution of problem b,
+ *     min 1/2 z'Gz + g'z   subject to   Cz = c   and   E z in the rows' set (the box: E = I)?
+ * d_res of the updates cannot say: d_res[2b+1] = rho ||E'(w+ - w)|| is the stationarity residual only if the z-step solved
+ * Gt z + gt + C'lambda = 0 EXACTLY, and a warm-started PCG with a small max_iter does not -- its error, and ||Cz - c||, show up
+ * nowhere in d_res; and d_res is absolute, with no scale to build a relative test from.  Every update of every family (box, soft
+ * box, linear rows, soft rows, cones) writes w+ = P(s), y+ = s - w+ with P the projection (prox) of its set, so w lies in the set
+ * and rho y in the normal cone at w BY CONSTRUCTION: bounds, complementarity and the signs of the multipliers need no test, and
+ * this call reads no bound and no kappa -- one pair of entry points serves all five families.  Three conditions remain, each
+ * with the scale of the usual test r <= eps_abs + eps_rel * scale:
+ *     stationarity  G z + g + C'lambda + rho E'y = 0,      dynamics  C z = c,      consensus  E z = w.
+ * d_G holds the HESSIANS (not d_Ginv; for the rows families not d_Gt); every layout is that of gbdpcg_kkt_residual_* (d_G, d_C,
+ * d_g, d_c, d_z, d_lambda) and of gbdpcg_admm_lin_update_* (d_E, d_rho, d_w, d_y); the box calls (gbdpcg_admm_optimality_*) have no
+ * mx, mu, d_E, and d_w, d_y have the layout of d_g.  d_C may be NULL when N == 1.  _shared: d_G, d_C and d_E are ONE problem's,
+ * read with a zero problem stride; everything else stays per problem.
+ * Per problem b, rho = d_rho[b], every line ONE IEEE operation or a comparison, a chain being acc = fma(a_i, b_i, acc) in
+ * ascending i:
+ *     x-entry r of knot k:  s = fl(g + lambda_k[r]);  s = fma(Q_k(r,q), x_q, s), q < nx;  if k + 1 < N: s = fma(A_k(q,r),
+ *                           -lambda_{k+1}[q], s), q < nx                                (the chain of gbdpcg_kkt_residual_*)
+ *                           a = the same Q chain from +0;      t = lambda_k[r], then the same A' chain
+ *     u-entry r of knot k:  the same with R_k, B_k and the seeds s = g, a = +0, t = +0   (the last knot has no C' terms and no u)
+ *     u = chain over the rows i of Ex_k (Eu_k) of fma(E(i,r), y_i, acc), seed +0;      q = fma(rho, u, s);    p = fma(rho, u, t)
+ *     knot 0, entry r:      f = fl(x_0[r] - c_0[r]);   h = x_0[r]
+ *     knot k+1, entry r:    f = fl(x_{k+1}[r] - c_{k+1}[r]);  f = fma(A_k(r,q), -x_q, f), q < nx;  f = fma(B_k(r,q), -u_q, f), q < nu
+ *                           h = the same chain seeded x_{k+1}[r]
+ *     row r:                v_r = chain over the columns j of fma(E(r,j), z_j, acc), seed +0 (the update's);  d_r = fl(v_r - w_r)
+ *     d_opt[6b+0] = r_s = max |q|        d_opt[6b+3] = n_s = max(max |a|, max |p|, max |g|)
+ *     d_opt[6b+1] = r_e = max |f|        d_opt[6b+4] = n_e = max(max |h|, max |c|)
+ *     d_opt[6b+2] = r_r = max |d|        d_opt[6b+5] = n_r = max(max |v|, max |w|)
+ *                   (all maxima over bit patterns as in gbdpcg_kkt_residual_*: NaN on top, exact in any order)
+ *     d_done[b] = (r_s <= fma(eps_rel, n_s, eps_abs) && r_e <= fma(eps_rel, n_e, eps_abs) && r_r <= fma(eps_rel, n_r, eps_abs))
+ *                 ? 1 : 0                                                                     a NaN anywhere gives 0
+ * so the outputs are defined to the bit whatever the launch shape or the alignment of the pointers.  d_opt (6 batch elements of
+ * the call's precision) and d_done (batch bytes; may be NULL: not written) are overwritten whatever they held.  The box calls
+ * take u = fma(1, y_r, +0) and v_r = z_r.  What follows from the lines:
+ *   - with y = 0, r_s and r_e have THE BITS of gbdpcg_kkt_residual_* on (G, C, g, c, z, lambda);
+ *   - called directly behind an update or step of ANY family, r_r has the bits of that update's d_res[2b] (soft and hard, box
+ *     and rows; cone rows through the rows call, with zero offsets f -- the call knows of no offset);
+ *   - on finite data the box calls give the bits of the rows calls with E = I, mx = nx, mu = nu;
+ *   - _shared gives each problem the bits of the per-problem call on `batch` copies.
+ * eps_abs, eps_rel are the caller's.  tests/admm_optimality_ref.py pins, on a feasible fixture, the window of iterations in which
+ * the device's first d_done must fall.
+ * One launch each, no handle state, asynchronous on `stream`, capturable inside a caller-owned capture; never allocates and needs
+ * nothing from gbdpcg_reserve.  d_rho, eps_abs, eps_rel and the data are not validated: bad values stay inside their own problem.
+ * NOT provided: a device-side count over the batch; any change to the step graphs (put the call behind the replay); a
+ * dual-infeasibility test (Gt is factored, hence positive definite: the cost is never unbounded; primal infeasibility is
+ * gbdpcg_admm_infeas_*).
+ * Refusals, before anything is written: null handle or required pointer, nx, nu, N or batch == 0, rows forms with no row at all:
+ * GBDPCG_ERR_INVALID; mx or mu > 64, a knot (Q_k, R_k, [A_k | B_k], its E blocks and vectors) that does not fit the LDS:
+ * GBDPCG_ERR_UNSUPPORTED; a batch of more than 2^31 - 1 problems: an error of the launch. */
+gbdpcg_status gbdpcg_admm_optimality_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const float *d_G,
+                                         const float *d_C, const float *d_g, const float *d_c, const float *d_rho, const float *d_z,
+                                         const float *d_lambda, const float *d_w, const float *d_y, float eps_abs, float eps_rel,
+                                         float *d_opt, uint8_t *d_done, void *stream);
+gbdpcg_status gbdpcg_admm_optimality_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch, const double *d_G,
+                                         const double *d_C, const double *d_g, const double *d_c, const double *d_rho,
+                                         const double *d_z, const double *d_lambda, const double *d_w, const double *d_y,
+                                         double eps_abs, double eps_rel, double *d_opt, uint8_t *d_done, void *stream);
+gbdpcg_status gbdpcg_admm_optimality_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                const float *d_G, const float *d_C, const float *d_g, const float *d_c,
+                                                const float *d_rho, const float *d_z, const float *d_lambda, const float *d_w,
+                                                const float *d_y, float eps_abs, float eps_rel, float *d_opt, uint8_t *d_done,
+                                                void *stream);
+gbdpcg_status gbdpcg_admm_optimality_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t N, uint32_t batch,
+                                                const double *d_G, const double *d_C, const double *d_g, const double *d_c,
+                                                const double *d_rho, const double *d_z, const double *d_lambda, const double *d_w,
+                                                const double *d_y, double eps_abs, double eps_rel, double *d_opt, uint8_t *d_done,
+                                                void *stream);
+gbdpcg_status gbdpcg_admm_lin_optimality_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                             uint32_t batch, const float *d_G, const float *d_C, const float *d_g, const float *d_c,
+                                             const float *d_E, const float *d_rho, const float *d_z, const float *d_lambda,
+                                             const float *d_w, const float *d_y, float eps_abs, float eps_rel, float *d_opt,
+                                             uint8_t *d_done, void *stream);
+gbdpcg_status gbdpcg_admm_lin_optimality_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                             uint32_t batch, const double *d_G, const double *d_C, const double *d_g,
+                                             const double *d_c, const double *d_E, const double *d_rho, const double *d_z,
+                                             const double *d_lambda, const double *d_w, const double *d_y, double eps_abs,
+                                             double eps_rel, double *d_opt, uint8_t *d_done, void *stream);
+gbdpcg_status gbdpcg_admm_lin_optimality_shared_f32(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                                    uint32_t batch, const float *d_G, const float *d_C, const float *d_g,
+                                                    const float *d_c, const float *d_E, const float *d_rho, const float *d_z,
+                                                    const float *d_lambda, const float *d_w, const float *d_y, float eps_abs,
+                                                    float eps_rel, float *d_opt, uint8_t *d_done, void *stream);
+gbdpcg_status gbdpcg_admm_lin_optimality_shared_f64(gbdpcg_handle_t h, uint32_t nx, uint32_t nu, uint32_t mx, uint32_t mu, uint32_t N,
+                                                    uint32_t batch, const double *d_G, const double *d_C, const double *d_g,
+                                                    const double *d_c, const double *d_E, const double *d_rho, const double *d_z,
+                                                    const double *d_lambda, const double *d_w, const double *d_y, double eps_abs,
+                                                    double eps_rel, double *d_opt, uint8_t *d_done, void *stream);
+
 /* Mixed-precision refinement of a KKT point: fp32 solves on a kept fp32 factorisation, the defect and the point in fp64.
  * For a caller who needs more digits in the step than fp32 carries (SQP close to convergence, an adjoint solve, ADMM on a
  * kept factorisation) without the price of the fp64 pipeline: factor once in fp32 (gbdpcg_demote_f32 of G and C, then
